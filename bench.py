@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the EDM inpainting sampling hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--xi 0|0.25] [--batch 8] [--workload ...] [--gap-ms G]
+    python bench.py --gpus N --steps K --warmup W [--xi 0|0.25] [--batch 8] [--workload ...] [--gap-ms G] [--dump-outputs DIR]
 
 N > 1: either the driver's form (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
 127.0.0.1 ... bench.py --gpus N ...), or plain `python bench.py --gpus N`, which re-launches itself that way
@@ -39,6 +39,7 @@ network and branch at B=1 (rank 0, N=1 only): per thread placement (physical cor
 timed evaluation OF THE SAME BRANCH (a placement whose warm-up is already 1.5x slower is not timed again), then two more on the fastest placement; value = 1 / median of its three timings, `cores` = its thread count.
 """
 import argparse
+import errno
 import json
 import os
 import sys
@@ -57,11 +58,20 @@ WINO_EXEC = {"conv53_wino4r_kernel": 0.5, "conv53_wino4v_kernel": 0.5, "conv53_w
 
 def ensure_built() -> None:
     """Build libaid_hip.so when it is missing or older than its sources (a clean checkout: the .so is git-ignored).  Every rank takes the same file
-    lock, so one of them builds and the others find the library up to date; hipcc cross-compiles without a GPU."""
+    lock, so one of them builds and the others find the library up to date; hipcc cross-compiles without a GPU.  The tree may be read-only to the
+    user who runs the benchmark (built beforehand by another one): then there is no lock to take and nothing can be built, and build.build() only
+    confirms that the library is current -- it writes nothing in that case and fails otherwise."""
     import fcntl
     import build
-    os.makedirs(os.path.join(ROOT, "audio_inpainting_diffusion_amd", "csrc", "build"), exist_ok=True)
-    with open(os.path.join(ROOT, "audio_inpainting_diffusion_amd", "csrc", "build", ".lock"), "w") as lk:
+    try:
+        os.makedirs(os.path.join(ROOT, "audio_inpainting_diffusion_amd", "csrc", "build"), exist_ok=True)
+        lk = open(os.path.join(ROOT, "audio_inpainting_diffusion_amd", "csrc", "build", ".lock"), "w")
+    except OSError as e:
+        if e.errno not in (errno.EACCES, errno.EPERM, errno.EROFS):
+            raise
+        build.build(verbose=False)
+        return
+    with lk:
         fcntl.flock(lk, fcntl.LOCK_EX)
         try:
             build.build(verbose=False)
@@ -222,6 +232,26 @@ def family_table(timing, by_kernel=False):
     return out
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each [rows, ...] tensor as out_dir/<name>.npy in float32, so that two builds run with the same arguments (same seeded inputs)
+    can be compared output for output.  An array over its share of DUMP_MAX_BYTES keeps a fixed seeded sample of its rows (segments), and the row
+    indices go to out_dir/<name>_rows.npy (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    budget = (DUMP_MAX_BYTES - 2 ** 16) // len(arrays)          # (2 ** 16: headers and row-index files)
+    for name, t in arrays.items():
+        v = t.detach().float().cpu().numpy()
+        if v.nbytes > budget:
+            rows = np.sort(np.random.default_rng(0).choice(v.shape[0], budget // v[0].nbytes, replace=False))
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            v = v[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+        print(f"bench: wrote {name}.npy {v.shape} float32 to {out_dir}", file=sys.stderr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -265,6 +295,8 @@ def main():
     ap.add_argument("--cu-split", default="", help="EXPERIMENT (A/B): CUs per XCD for each sub-batch stream, e.g. 16,16 (disjoint halves) or 20,20 (overlapping) -- CU-masked sub-batch streams "
                     "without any cross-stream events (network.cu_split)")
     ap.add_argument("--conv-table", action="store_true", help="print per-shape conv kernel times (stderr)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step returned (the sampler state x of "
+                    "every segment, gathered over ranks) as DIR/<name>.npy in float32 (dump_outputs)")
     a = ap.parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -397,6 +429,10 @@ def main():
     wall_rank = wall = time.perf_counter() - t0
     wall = D.max_over_ranks(wall, dev)
     assert torch.isfinite(state["x"]).all()
+    if a.dump_outputs:                                 # (the roofline pass below steps the same state on: keep what the last timed step returned)
+        x_last = D.gather_outputs(state["x"], world * B)
+        if rank == 0:
+            dump_outputs(a.dump_outputs, {"x": x_last})
     # Kernel speeds are measured right after the timed region: the SAME sampler continues for one warm-up and ROOF_STEPS measured
     # Heun steps with the network forced onto one stream and eager launches (the product schedule overlaps kernels of different
     # sub-batches on concurrent HIP streams, or replays a captured HIP graph: a launch's start-to-end time there is not the kernel's speed).

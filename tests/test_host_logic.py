@@ -573,6 +573,26 @@ def test_bench_reports_pmc_traffic_only_for_the_same_build_and_names_kernels_as_
     assert len(bench._kernel_sources_sha16()) == 16
 
 
+def test_bench_dump_outputs_writes_float32_and_a_fixed_sample_within_the_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: an array within the budget is written whole in float32; one over it keeps a fixed seeded sample of its rows (the same
+    rows on every run, their indices beside it), and the files stay within DUMP_MAX_BYTES."""
+    import bench
+    g0 = torch.Generator().manual_seed(3)
+    x = torch.randn(8, 1000, generator=g0, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "a"), {"x": x})
+    v = np.load(tmp_path / "a" / "x.npy")
+    assert v.dtype == np.float32 and np.array_equal(v, x.float().numpy()) and not (tmp_path / "a" / "x_rows.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2 ** 16 + 5 * 4000 + 100)         # room for five rows of 1000 float32
+    big = torch.randn(64, 1000, generator=g0)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"x": big})
+    rows, v = np.load(tmp_path / "b" / "x_rows.npy"), np.load(tmp_path / "b" / "x.npy")
+    assert rows.dtype == np.float64 and len(rows) == 5 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(v, big.numpy()[rows.astype(int)])
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "x_rows.npy")) and np.array_equal(v, np.load(tmp_path / "c" / "x.npy"))
+    assert sum(f.stat().st_size for f in (tmp_path / "b").iterdir()) <= bench.DUMP_MAX_BYTES
+
+
 def test_lambda_degradation_is_the_jacobian_transpose_product_at_x_hat():
     """sampler.LambdaDegradation (Sampler.predict_resample, edm_sampler_inpainting.py:164-173): apply = the callable on a detached copy, adjoint = its VJP at the
     same point -- what the reference's torch.autograd.grad forms through `degradation(x_hat)` (:65-81) -- for a linear operator that changes the length and for a
