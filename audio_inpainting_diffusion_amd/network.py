@@ -21,7 +21,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Dict, List, Optional
+from typing import Callable, Dict, List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -30,10 +30,28 @@ import torch.nn as nn
 from . import _lib
 from .cqt import CQTransform
 
-# Winograd forms of a 5x3 layer -> aid_conv2d_params::x_wino / aid_scale_act_params::wino.  4 = F(4,3), 8 = F(8,3) (fused 1-D kernels); the non-fused 2-D forms:
-# 45 = F(4,5) x F(4,3) (48 planes), 85 = F(4,5) x F(8,3) (80 planes over groups of eight samples: round 6)
-XW_CODE = {0: 0, 4: 1, 8: 2, 45: 3, 85: 4}
-W2D_PLANES = {45: 48, 85: 80}
+
+class _Form(NamedTuple):
+    code: int                            # aid_conv2d_params::x_wino = aid_scale_act_params::wino
+    taps: int                            # taps / planes of the weight pack (0: the direct pack, kh * kw taps)
+    two_d: bool                          # non-fused 2-D form: the input is the flat V [taps][C][N], the GEMM output M goes through scratch
+    cols: Optional[Callable]             # 1-D forms: input columns for T outputs
+
+
+# Forms of a 5x3 layer, keyed by the number the builder speaks: 0 = plain activations, 4 = F(4,3), 8 = F(8,3) (fused 1-D kernels); the non-fused 2-D
+# forms 45 = F(4,5) x F(4,3) and 85 = F(4,5) x F(8,3) (over groups of eight samples: round 6)
+_FORMS = {0: _Form(0, 0, False, lambda T: T), 4: _Form(1, 30, False, lambda T: 6 * (T // 4)), 8: _Form(2, 50, False, lambda T: 10 * (T // 8)),
+          45: _Form(3, 48, True, None), 85: _Form(4, 80, True, None)}
+
+
+class _ConvPacks(NamedTuple):
+    """Kernel-side packs of one conv weight (aid_pack_conv_weight), form -> pack: ``fwd`` of the forward operator, ``dgrad`` of its transpose (the
+    input-gradient operator; empty for a launch without VJP).  Form 0 is the direct tap-major pack [kh*kw][Cin_pad][Cout_pad]."""
+    name: Optional[str]                  # parameter name (training: target of the weight gradient)
+    fwd: Dict[int, torch.Tensor]
+    dgrad: Dict[int, torch.Tensor]
+
+
 RSQRT2 = 1.0 / math.sqrt(2.0)
 SQRT2 = math.sqrt(2.0)
 _CUBIC = (-0.01171875, -0.03515625, 0.11328125, 0.43359375, 0.43359375, 0.11328125, -0.03515625, -0.01171875)
@@ -341,7 +359,7 @@ class _Builder:
             self.nbytes += ws.numel() * 8
             cp.stat_ws, cp.stat_n = ws.data_ptr(), ws_n
             src[3].also_writes(ws)                         # (the conv's epilogue now writes the partials this op folds)
-            if self.net.fuse_fin and self._fin_wanted(cp.B, cp.x_wino) and _lib.lib().aid_conv2d_fin_supported(cp.B, cp.Cin, cp.Cout, cp.F, cp.T, cp.dilF, cp.x_wino):
+            if self.net.fuse_fin and self._fin_wanted(cp.B, src[4]) and _lib.lib().aid_conv2d_fin_supported(cp.B, cp.Cin, cp.Cout, cp.F, cp.T, cp.dilF, cp.x_wino):
                 # the last tile of each sample folds the partials itself (aid_kernels.h: fin_mode = 1): no aid_group_stats launch at all
                 cnt = self._fin_count(src[3].lane)
                 cp.fin_mode, cp.fin_count, cp.fin_gamma, cp.fin_eps = 1, cnt.data_ptr(), gamma.data_ptr(), 1e-7
@@ -359,11 +377,11 @@ class _Builder:
         self._stats_train_hook(scale, gamma, mod, gname, stats, B, Cc)
 
     @staticmethod
-    def _fin_wanted(B, x_wino):
+    def _fin_wanted(B, form):
         """The output pass of the 2-D form has thousands of short blocks per sample, each of which would publish its partial past the L2 and bump the
         sample's arrival counter: measured neutral at batch 1 and -0.4 % at batch 8 (profiles/r05_fin2d_ab.txt) -- taken for launches of at most two
         samples, where the fold launch it removes is a larger share of the evaluation; the row-shared kernels (few large tiles) always take it."""
-        return x_wino not in (3, 4) or B <= 2
+        return not _FORMS[form].two_d or B <= 2
 
     def _fin_count(self, lane):
         """arrival counters of the fused finalisation (aid_kernels.h: fin_count): one zeroed word per sample and lane (launches of a lane are serial and
@@ -397,17 +415,18 @@ class _Builder:
         assert 0 <= off < self.mod.shape[1] and view.stride(0) == self.mod.stride(0)
         return self.dmod[:, off:off + view.shape[1]]
 
-    def _train_conv(self, x, gy, gd, wname, cin, cout, kh, kw, dil, in_scale, act, out_scale, alpha, wpw=None):
+    def _train_conv(self, x, gy, gd, rec, cin, cout, kh, kw, dil, in_scale, act, out_scale, alpha):
         """Parameter-gradient ops of one conv (weight, gate vector, and the <dL/du * scale, x> sums its input scale needs).
         5x3 layers with their F(4,3) weight pack take the Winograd form of the weight gradient (half the MFMAs): both operands are
         transformed first -- gy by aid_wino_gy, the conv input by the aid_scale_act(wino=1) pass that re-creates what the forward saw."""
         B, _, F, T = gy.shape
         K = kh * kw
+        wu, wname = rec.fwd.get(4), rec.name
         wino = bool(self.net.wgrad_wino and (kh, kw) == (5, 3) and T % 16 == 0 and cin >= 32 and cout >= 32
-                    and (out_scale is None or (wpw is not None and wpw.shape[0] == 30)))
+                    and (out_scale is None or wu is not None))
         xin, isc = x, in_scale
         if wino:
-            G6 = 6 * (T // 4)
+            G6 = _FORMS[4].cols(T)
             xin = self._scratch(("hww", B, cin, F, G6))
             sp = _lib.ScaleActParams(_lib.view4(x), _lib.view4(xin), _lib.ptr(in_scale) if act else None,
                                      in_scale.stride(0) if (act and in_scale is not None) else 0, B, cin, F, T, 1 if act else 0, 1)
@@ -427,7 +446,7 @@ class _Builder:
         tiles = int(_lib.lib().aid_conv2d_wgrad_tiles(cin, cout, kh, kw, int(wino)))
         S = max(1, min(F, 256 // (tiles * B)))            # about one workgroup per CU: every extra split is another partial to write and reduce
                                                           # (1024 / 768 / 512 / 256 workgroups: 250 / 238 / 227 / 221 ms per iteration at batch 4)
-        KP = 30 if wino else K                            # taps per (co, ci) in the partials (U domain: xi * 5 + kh)
+        KP = _FORMS[4].taps if wino else K                # taps per (co, ci) in the partials (U domain: xi * 5 + kh)
         P = self._scratch(("P", B * S * cout * cin * KP))
         wp = _lib.WgradParams(_lib.view4(gop), _lib.view4(xin), P.data_ptr(), B, cin, cout, F, T, kh, kw, dil, S, alpha, int(wino))
         self._add("aid_conv2d_wgrad", wp, gop, xin, P, flops=2 * B * F * T * cin * cout * K, writes=(P,))
@@ -436,9 +455,9 @@ class _Builder:
         rp = _lib.WgradReduceParams(P.data_ptr(), W.data_ptr(), _lib.ptr(out_scale), 0 if out_scale is None else out_scale.stride(0),
                                     _lib.ptr(isc), 0 if isc is None else isc.stride(0), self.pgrad[wname].data_ptr(), _lib.ptr(dg),
                                     0 if dg is None else dg.stride(0), B, S, cout, cin, K, 1, int(wino),
-                                    _lib.ptr(wpw) if wino else None, wpw.shape[1] if (wino and wpw is not None) else 0,
-                                    wpw.shape[2] if (wino and wpw is not None) else 0)
-        self._add("aid_wgrad_reduce", rp, P, W, out_scale, isc, dg, wpw, writes=(self.pgrad[wname], dg))
+                                    _lib.ptr(wu) if wino else None, wu.shape[1] if (wino and wu is not None) else 0,
+                                    wu.shape[2] if (wino and wu is not None) else 0)
+        self._add("aid_wgrad_reduce", rp, P, W, out_scale, isc, dg, wu, writes=(self.pgrad[wname], dg))
         if in_scale is not None and gd is not None:       # gd = dL/d(x*scale) * scale  ->  S[b,c] = sum gd * x  (aid_scale_bwd divides by scale)
             Sb = self.buf(B, cin)
             cp = _lib.ChannelDotParams(_lib.view4(gd), _lib.view4(x), Sb.data_ptr(), Sb.stride(0), B, cin, F, T)
@@ -446,20 +465,20 @@ class _Builder:
             self.S_of[in_scale.data_ptr()] = Sb
 
     def _conv_raw(self, x, y, wp, cin, cout, kh, kw, dil, in_scale, act, out_scale, res, res_scale, alpha, epi=0,
-                  aux=None, aux_scale=None, wpw=None, x_wino=0, dot=None, x2=None, fin_stats=None):
-        """``x_wino``: 0 plain activations, 4 / 8: ``x`` is the F(4,3) / F(8,3) input transform and ``wpw`` the matching 30- / 50-tap pack."""
+                  aux=None, aux_scale=None, wu=None, form=0, dot=None, x2=None, fin_stats=None):
+        """``form`` (_FORMS): the layout of ``x`` -- plain activations, the input transform of a 1-D form, or the flat V of a 2-D form -- and ``wu`` the
+        Winograd pack of that form.  Form 0 with the F(4,3) pack: aid_conv2d forms the F(4,3) input transform from its staged strip itself."""
         B, _, F, T = y.shape
-        x_wino = int(x_wino)
-        xw_code = XW_CODE[x_wino]                            # aid_conv2d_params::x_wino
+        fm = _FORMS[form]
         p = _lib.Conv2dParams()
-        nxi = W2D_PLANES.get(x_wino, 0)
+        nxi = fm.taps if fm.two_d else 0
         if nxi:                                              # 2-D form: x is the flat V [48 | 80][cin][N] of aid_scale_act(wino = 3 | 4)
-            npos = self._w2d_positions(x_wino, B, F, T, dil)
+            npos = self._w2d_positions(form, B, F, T, dil)
             assert x.dim() == 1 and x.numel() == nxi * cin * npos and x2 is None and in_scale is None and not act
             p.x = _lib.View(x.data_ptr(), 0, 0, 0)
         else:
             assert x.shape[1] + (0 if x2 is None else x2.shape[1]) == cin and y.shape[1] == cout and x.shape[0] == B and x.shape[2] == F
-            assert x.shape[3] == {0: T, 4: 6 * (T // 4), 8: 10 * (T // 8)}[x_wino]
+            assert x.shape[3] == fm.cols(T)
             p.x = _lib.view4(x)
         p.y, p.res, p.aux = _lib.view4(y), _lib.view4(res), _lib.view4(aux)
         p.wp = wp.data_ptr()
@@ -470,9 +489,9 @@ class _Builder:
         p.Cin_pad, p.Cout_pad = wp.shape[1], wp.shape[2]
         p.KH, p.KW, p.dilF, p.act, p.epi = kh, kw, dil, act, epi
         p.alpha, p.res_scale = alpha, res_scale
-        p.wp_wino = _lib.ptr(wpw)
-        p.wino_taps = 0 if wpw is None else wpw.shape[0]
-        p.x_wino = xw_code
+        p.wp_wino = _lib.ptr(wu)
+        p.wino_taps = 0 if wu is None else wu.shape[0]
+        p.x_wino = fm.code
         if dot is not None:                              # (buffer, partials per (b, group)): <y, aux> folded into the epilogue
             p.dot_ws, p.dot_n = dot[0].data_ptr(), dot[1]
         cnt = None
@@ -489,34 +508,34 @@ class _Builder:
         elif nxi:                                        # the GEMM's output M [48 | 80][cout][N], read back by the output-transform pass of the same call
             ws = self._scratch(("m45", nxi * cout * npos))
             p.ws, p.ws_bytes = ws.data_ptr(), ws.numel() * 4
-        elif x_wino == 4 and B == 1 and self.whole_batch:     # a WHOLE batch of one (never a sub-batch: a segment's bits must not depend on the split):
+        elif form == 4 and B == 1 and self.whole_batch:       # a WHOLE batch of one (never a sub-batch: a segment's bits must not depend on the split):
                                                          # launches with few tiles share the K axis of a tile between two workgroups
             need = int(_lib.lib().aid_conv2d_wino_split_ws_bytes(B, cin, cout, F, T, dil))
             if need:
                 ws = self._split_ws(need)
                 p.ws, p.ws_bytes = ws.data_ptr(), ws.numel() * 4
-        assert wp.shape[0] == kh * kw and (wpw is None or (wpw.shape[0] == {8: 50, 45: 48, 85: 80}.get(x_wino, 30) and wpw.shape[1:] == wp.shape[1:]))
+        assert wp.shape[0] == kh * kw and (wu is None or (wu.shape[0] == _FORMS[form or 4].taps and wu.shape[1:] == wp.shape[1:]))
         # algorithmic HBM bytes: x once, residual / aux once, y once, weights once
         nb = 4 * (B * F * T * (cin + cout * (1 + (res is not None) + (aux is not None))) + cin * cout * kh * kw)
         dws = None if dot is None else dot[0]
         if nxi:
             # (bookkeeping only: the launches whose GEMM folds the row-axis output transform write and re-read HALF of M -- the rule of w2d_fold_m in
             #  csrc/aid_wino2d.hip, restated here for the algorithmic byte counts bench.py reports; the library decides on its own)
-            mxi = nxi // 2 if (x_wino == 85 and cin <= 128 and 10 * (-(-npos // 64)) * (-(-cout // 128)) >= 768) else nxi
+            mxi = nxi // 2 if (form == 85 and cin <= 128 and 10 * (-(-npos // 64)) * (-(-cout // 128)) >= 768) else nxi
             # two plan nodes on one parameter block: the MFMA-bound batched GEMM M = U V (its FLOPs and the bytes of V + M are booked here) and the
             # HBM-bound output-transform pass with the epilogue (reads M, residual / aux; writes y and the partials)
-            self._add("aid_conv2d_wino2d_gemm", p, x, wpw, ws, flops=2 * B * F * T * cin * cout * kh * kw, nbytes=4 * npos * (nxi * cin + mxi * cout), writes=(ws,))
+            self._add("aid_conv2d_wino2d_gemm", p, x, wu, ws, flops=2 * B * F * T * cin * cout * kh * kw, nbytes=4 * npos * (nxi * cin + mxi * cout), writes=(ws,))
             op = self._add("aid_conv2d_wino2d_output", p, ws, y, res, out_scale, aux, aux_scale, dws, fin_stats, cnt,
                            nbytes=4 * (mxi * npos * cout + B * F * T * cout * (1 + (res is not None) + (aux is not None))), writes=(y, dws, cnt))
         else:
-            op = self._add("aid_conv2d", p, x, x2, y, res, wp, in_scale, out_scale, aux, aux_scale, wpw, ws, dws, fin_stats, cnt, flops=2 * B * F * T * cin * cout * kh * kw,
+            op = self._add("aid_conv2d", p, x, x2, y, res, wp, in_scale, out_scale, aux, aux_scale, wu, ws, dws, fin_stats, cnt, flops=2 * B * F * T * cin * cout * kh * kw,
                            nbytes=nb, writes=(y, ws, dws, cnt))
         self._wrote(y)
-        if not self._in_bwd and x_wino and epi == 0 and dot is None and self.net.epilogue_stats:
-            n = int(_lib.lib().aid_conv2d_stat_partials(B, cin, cout, F, T, dil, xw_code))
+        if not self._in_bwd and form and epi == 0 and dot is None and self.net.epilogue_stats:
+            n = int(_lib.lib().aid_conv2d_stat_partials(B, cin, cout, F, T, dil, fm.code))
             if n:                                         # a later stats(y) may ask this conv's epilogue for the partial sums
                 hi = y.data_ptr() + 4 * (1 + sum((m - 1) * st for m, st in zip(y.shape, y.stride())))
-                self._stat_src[self._vkey(y)] = (p, n, hi, op)
+                self._stat_src[self._vkey(y)] = (p, n, hi, op, form)
 
     def _dot_ws(self, n):
         """scratch for the per-tile <gd, x> partials written by the conv epilogue: [B*8, n] doubles + B*8 floats (coef)"""
@@ -533,65 +552,60 @@ class _Builder:
         n = int(_lib.lib().aid_conv2d_wino2d_positions(B, F, T, dil))
         return n // 2 if form == 85 else n
 
-    def _wino_input(self, cin, cout, T, wp, wpw, F=0, dil=1, wpw8=None, wpw2=None, wpw3=None):
-        """The Winograd form the pre-pass should write for this 5x3 layer (aid_scale_act wino = 1 / 2 -> aid_conv2d x_wino = 1 / 2): 8 = F(8,3)
-        (10 MFMAs per 8 outputs; needs the 50-tap pack), 4 = F(4,3), 0 = plain activations.  The library answers from the launch shape
-        (aid_conv2d_wino_form); ``net.wino_forms`` restricts the choice (A/B measurements, tests of the F(4,3) kernels)."""
-        if wpw is None or wpw.shape[0] != 30:
+    def _form(self, rec, dgrad, cin, cout, F, T, dil):
+        """The form (_FORMS) of a 5x3 launch of shape (cin, cout, F, T, dil) on the forward packs of ``rec`` or, with ``dgrad``, its transposed ones.  A form
+        needs its pack in ``rec``; the library answers from the launch shape for fb = net.form_batch or this batch; net.wino_forms (wf) restricts it.
+          * No F(4,3) pack: 0.  2-D forms where the 45 pack is held, 45 or 85 is in wf and aid_conv2d_wino2d_supported: on every such layer if wf is
+            (45,), (85,) or (45, 85), else if min(cin, cout) >= w2d_min_channels, T <= w2d_force_max_T or aid_conv2d_wino2d_wanted, and cout % 128 == 0 or
+            T <= w2d_c96_max_T.  Of those, 85 if its pack is held, 85 in wf, T % 32 == 0 and (45 not in wf, cout % 128 != 0 or aid_conv2d_wino2d_tform == 8).
+          * Else aid_conv2d_wino_form: its 8 becomes 4 without the 8 pack or 8 in wf; its 4 becomes 8 if 4 is not in wf, the 8 pack is held and
+            aid_conv2d_wino8_supported (wf = (8,): F(8,3) wherever its tiles fit).  4 then needs 4 in wf or one of the three 2-D sets above (those keep
+            F(4,3) where the 2-D form does not apply) and aid_conv2d_wino_input_ok -- asked for this builder's batch, not fb, as always; else 0."""
+        packs = rec.dgrad if dgrad else rec.fwd
+        if 4 not in packs:
             return 0
-        fb = int(self.net.form_batch or self.B)               # the batch the FORM is chosen for (network.form_batch; default: this launch's)
-        if wpw2 is not None and (45 in self.net.wino_forms or 85 in self.net.wino_forms) and _lib.lib().aid_conv2d_wino2d_supported(cin, cout, F, T, dil):
-            # the non-fused 2-D form F(4,5) x F(4,3) (csrc/aid_wino2d.hip: 3.0 products per output) where the library predicts it faster than the fused
-            # 1-D kernels (aid_conv2d_wino2d_wanted, a function of the launch shape); wino_forms = (45,): wherever it is supported (tests, A/B)
-            if tuple(self.net.wino_forms) in ((45,), (85,), (45, 85)) or (min(cin, cout) >= self.net.w2d_min_channels and (T <= self.net.w2d_force_max_T or _lib.lib().aid_conv2d_wino2d_wanted(fb, cin, cout, F, T, dil))
-                                                                            and (cout % 128 == 0 or T <= self.net.w2d_c96_max_T)):
-                # ... and which T form: F(8,3) along T (85: 2.5 products per output, 2.5 x the activation in V / M) where the library says so
-                # (aid_conv2d_wino2d_tform), F(4,3) (45) otherwise; wino_forms without 85 / 45 restricts the choice
-                if wpw3 is not None and 85 in self.net.wino_forms and T % 32 == 0 and (45 not in self.net.wino_forms or tuple(self.net.wino_forms) == (85,) or cout % 128 != 0
-                                                                                     or int(_lib.lib().aid_conv2d_wino2d_tform(fb, cin, cout, F, T, dil)) == 8):
-                    return 85
-                if 45 in self.net.wino_forms:
-                    return 45
-        form = int(_lib.lib().aid_conv2d_wino_form(fb, cin, cout, F, T, dil))
-        if form == 8 and (wpw8 is None or 8 not in self.net.wino_forms):
+        L, net, wf, fb = _lib.lib(), self.net, tuple(self.net.wino_forms), int(self.net.form_batch or self.B)
+        forced2d = wf in ((45,), (85,), (45, 85))
+        if 45 in packs and (45 in wf or 85 in wf) and L.aid_conv2d_wino2d_supported(cin, cout, F, T, dil) and (forced2d or (
+                min(cin, cout) >= net.w2d_min_channels and (T <= net.w2d_force_max_T or L.aid_conv2d_wino2d_wanted(fb, cin, cout, F, T, dil))
+                and (cout % 128 == 0 or T <= net.w2d_c96_max_T))):
+            if 85 in packs and 85 in wf and T % 32 == 0 and (45 not in wf or cout % 128 != 0 or int(L.aid_conv2d_wino2d_tform(fb, cin, cout, F, T, dil)) == 8):
+                return 85
+            if 45 in wf:
+                return 45
+        form = int(L.aid_conv2d_wino_form(fb, cin, cout, F, T, dil))
+        if form == 8 and (8 not in packs or 8 not in wf):
             form = 4
-        elif form == 4 and 4 not in self.net.wino_forms and wpw8 is not None and _lib.lib().aid_conv2d_wino8_supported(cin, cout, F, T, dil):
-            form = 8                                          # wino_forms = (8,): F(8,3) wherever its tiles fit (tests, A/B)
-        if form == 4 and not ((4 in self.net.wino_forms or tuple(self.net.wino_forms) in ((45,), (85,), (45, 85))) and bool(_lib.lib().aid_conv2d_wino_input_ok(self.B, cin, cout, F, T, dil))):
-            form = 0
-        return form
-
-    @staticmethod
-    def _wino_cols(form, T):
-        return {0: T, 4: 6 * (T // 4), 8: 10 * (T // 8)}[form]
+        elif form == 4 and 4 not in wf and 8 in packs and L.aid_conv2d_wino8_supported(cin, cout, F, T, dil):
+            form = 8
+        return 0 if form == 4 and not ((4 in wf or forced2d) and L.aid_conv2d_wino_input_ok(self.B, cin, cout, F, T, dil)) else form
 
     def _wino_scratch(self, tag, form, B, C, F, T, dil):
-        """scratch for the conv input the pre-pass writes: [B, C, F, cols] (plain / 1-D Winograd domain) or the flat V [48][C][N] of the 2-D form"""
-        if form in W2D_PLANES:
-            return self._scratch((tag + "45", W2D_PLANES[form] * C * self._w2d_positions(form, B, F, T, dil)))
-        return self._scratch((tag, B, C, F, self._wino_cols(form, T)))
+        """scratch for the conv input the pre-pass writes: [B, C, F, cols] (plain / 1-D Winograd domain) or the flat V [48 | 80][C][N] of a 2-D form"""
+        fm = _FORMS[form]
+        return self._scratch((tag + "45", fm.taps * C * self._w2d_positions(form, B, F, T, dil)) if fm.two_d else (tag, B, C, F, fm.cols(T)))
 
     @staticmethod
     def _sa_out(t):
         """aid_scale_act's output view: 4-D scratch, or the flat V of the 2-D form (strides unused)"""
         return _lib.View(t.data_ptr(), 0, 0, 0) if t.dim() == 1 else _lib.view4(t)
 
-    def conv(self, x, y, wp, cin, cout, kh=1, kw=1, dil=1, in_scale=None, act=0, out_scale=None, res=None,
-             res_scale=1.0, alpha=1.0, wpT=None, norm_stats=None, wpw=None, wpwT=None, res_nograd=False, wname=None, wpw8=None, wpw8T=None,
-             wpw2=None, wpw2T=None, wpw3=None, wpw3T=None):
-        """Forward conv + registration of its input-VJP.  ``norm_stats``: the (mean, 1/(std+eps)) buffer when
-        ``in_scale`` was produced by ``stats`` from this same ``x`` (the scale then depends on x)."""
+    def conv(self, x, y, w, cin, cout, kh=1, kw=1, dil=1, in_scale=None, act=0, out_scale=None, res=None,
+             res_scale=1.0, alpha=1.0, norm_stats=None, res_nograd=False):
+        """Forward conv + registration of its input-VJP.  ``w``: the weight's _ConvPacks, or its direct pack alone for a launch without VJP.
+        ``norm_stats``: the (mean, 1/(std+eps)) buffer when ``in_scale`` was produced by ``stats`` from this same ``x`` (the scale then depends on x)."""
+        rec = w if isinstance(w, _ConvPacks) else _ConvPacks(None, {0: w}, {})
+        B, _, F, T = x.shape
         if act and kh > 1:
             # evaluate norm*mod -> GELU once per element into a scratch tensor; the conv stages plain copies
-            xw = self._wino_input(cin, cout, x.shape[3], wp, wpw, x.shape[2], dil, wpw8, wpw2, wpw3)
-            hbuf = self._wino_scratch("h", xw, x.shape[0], cin, x.shape[2], x.shape[3], dil)
-            sp = _lib.ScaleActParams(_lib.view4(x), self._sa_out(hbuf), in_scale.data_ptr(), in_scale.stride(0), x.shape[0], cin,
-                                     x.shape[2], x.shape[3], 1, XW_CODE[xw], dil)
+            xw = self._form(rec, False, cin, cout, F, T, dil)
+            hbuf = self._wino_scratch("h", xw, B, cin, F, T, dil)
+            sp = _lib.ScaleActParams(_lib.view4(x), self._sa_out(hbuf), in_scale.data_ptr(), in_scale.stride(0), B, cin, F, T, 1, _FORMS[xw].code, dil)
             self._add("aid_scale_act", sp, x, hbuf, in_scale, writes=(hbuf,))
-            self._conv_raw(hbuf, y, wp, cin, cout, kh, kw, dil, None, 0, out_scale, res, res_scale, alpha, wpw={8: wpw8, 45: wpw2, 85: wpw3}.get(xw, wpw), x_wino=xw)
+            self._conv_raw(hbuf, y, rec.fwd[0], cin, cout, kh, kw, dil, None, 0, out_scale, res, res_scale, alpha, wu=rec.fwd.get(xw or 4), form=xw)
         else:
-            self._conv_raw(x, y, wp, cin, cout, kh, kw, dil, in_scale, act, out_scale, res, res_scale, alpha)
-        if wpT is None:
+            self._conv_raw(x, y, rec.fwd[0], cin, cout, kh, kw, dil, in_scale, act, out_scale, res, res_scale, alpha)
+        if not rec.dgrad:
             return
 
         def bw():
@@ -599,7 +613,6 @@ class _Builder:
             # the last dilated step of a block may read dL/dy THROUGH a pending scaled copy (see _defer_copy): its only readers here are the gate pre-pass
             # (aid_scale_act mul) and the normalisation backward's skip term (a)
             gy, gmul = self.Gsrc(y) if (kh > 1 and out_scale is not None and norm_stats is not None and fused_res and not self.train) else (self.G(y), 1.0)
-            B, _, F, T = x.shape
             if res is not None and not fused_res and not res_nograd:
                 gr = self.G(res)
                 if self._gacc(res):
@@ -610,19 +623,19 @@ class _Builder:
             if kh > 1 and out_scale is not None:
                 # 5x3 dgrad: apply the gate in a copy pass so the conv input needs no in-kernel prologue
                 # (keeps it on the direct-to-LDS kernel)
-                gw = self._wino_input(cout, cin, gy.shape[3], wpT, wpwT, gy.shape[2], dil, wpw8T, wpw2T, wpw3T) if norm_stats is not None else 0
+                gw = self._form(rec, True, cout, cin, gy.shape[2], gy.shape[3], dil) if norm_stats is not None else 0
                 gin = self._wino_scratch("g", gw, gy.shape[0], cout, gy.shape[2], gy.shape[3], dil)
-                nb = self._nb_src.pop(self._vkey(gy), None) if (gw in (4, 8, 45, 85) and self.net.fuse_norm_bwd_wino and gmul == 1.0) else None
+                nb = self._nb_src.pop(self._vkey(gy), None) if (gw and self.net.fuse_norm_bwd_wino and gmul == 1.0) else None
                 if nb is not None and nb[1] > self._g_last.get(gin.data_ptr(), -1) and nb[3].lane == self.lane:
                     # gy was written last by an aid_norm_bwd and nothing used this scratch since: that pass also writes gin (for the 2-D forms it then
                     # IS this layer's input pass: the normalisation backward folded into the transform, one read of gd / x / gy instead of two passes)
                     nb[0].wout, nb[0].wscale, nb[0].wscale_ld = self._sa_out(gin), out_scale.data_ptr(), out_scale.stride(0)
-                    nb[0].wform, nb[0].wdil = {4: 1, 8: 2, 45: 3, 85: 4}[gw], dil
+                    nb[0].wform, nb[0].wdil = _FORMS[gw].code, dil
                     self.plan.keep.extend((gin, out_scale))
                     nb[3].also_writes(gin)
                 else:
                     sp = _lib.ScaleActParams(_lib.view4(gy), self._sa_out(gin), out_scale.data_ptr(), out_scale.stride(0), gy.shape[0],
-                                             cout, gy.shape[2], gy.shape[3], 0, XW_CODE[gw], dil, 0.0 if gmul == 1.0 else gmul)
+                                             cout, gy.shape[2], gy.shape[3], 0, _FORMS[gw].code, dil, 0.0 if gmul == 1.0 else gmul)
                     self._add("aid_scale_act", sp, gy, gin, out_scale, writes=(gin,))
                 self._g_last[gin.data_ptr()] = len(self.plan.ops)      # (the dgrad conv below reads it)
                 gsc = None
@@ -630,22 +643,22 @@ class _Builder:
                 gd = self._scratch(x.shape)
                 # <gd, x> per (sample, group): folded into the dgrad conv's epilogue when it runs on the F(4,3) kernels
                 nd = 0
-                if act and kh == 5 and gsc is None and wpwT is not None and wpwT.shape[0] == 30:
-                    nd = int(_lib.lib().aid_conv2d_dot_partials(B, cout, cin, F, T, dil, XW_CODE[gw]))
+                if act and kh == 5 and gsc is None and 4 in rec.dgrad:
+                    nd = int(_lib.lib().aid_conv2d_dot_partials(B, cout, cin, F, T, dil, _FORMS[gw].code))
                 elif act and kh == 1 and kw == 1 and self.net.fuse_dot_1x1:        # 1x1 steps (init / out blocks): the direct-to-LDS kernel's epilogue
                     nd = int(_lib.lib().aid_conv2d_dot_partials_1x1(B, cout, cin, F, T))
                 dws = self._dot_ws(nd) if nd else self.stats_ws
                 # the last tile of each sample also folds the partials into the normalisation-backward coefficients (aid_kernels.h: fin_mode = 2)
-                fin = bool(nd and kh == 5 and gw in (4, 8, 45, 85) and self.net.fuse_fin and self._fin_wanted(B, XW_CODE[gw])
-                           and _lib.lib().aid_conv2d_fin_supported(B, cout, cin, F, T, dil, XW_CODE[gw]))
-                self._conv_raw(gin, gd, wpT, cout, cin, kh, kw, dil, gsc, 0, in_scale, None, 1.0, alpha,
-                               epi=1 if act else 0, aux=x if act else None, aux_scale=in_scale if act else None, wpw={8: wpw8T, 45: wpw2T, 85: wpw3T}.get(gw, wpwT), x_wino=gw,
+                fin = bool(nd and kh == 5 and gw and self.net.fuse_fin and self._fin_wanted(B, gw)
+                           and _lib.lib().aid_conv2d_fin_supported(B, cout, cin, F, T, dil, _FORMS[gw].code))
+                self._conv_raw(gin, gd, rec.dgrad[0], cout, cin, kh, kw, dil, gsc, 0, in_scale, None, 1.0, alpha,
+                               epi=1 if act else 0, aux=x if act else None, aux_scale=in_scale if act else None, wu=rec.dgrad.get(gw or 4), form=gw,
                                dot=(dws, nd) if nd else None, fin_stats=norm_stats if fin else None)
                 if not nd:
                     dp = _lib.GroupDotParams(_lib.view4(gd), _lib.view4(x), B, cin, F, T, 8, self.stats_ws.data_ptr())
                     self._add("aid_group_dot", dp, gd, x, self.stats_ws, writes=(self.stats_ws,))
-                if self.train and wname is not None:
-                    self._train_conv(x, gy, gd, wname, cin, cout, kh, kw, dil, in_scale, act, out_scale, alpha, wpw=wpw)
+                if self.train and rec.name is not None:
+                    self._train_conv(x, gy, gd, rec, cin, cout, kh, kw, dil, in_scale, act, out_scale, alpha)
                 npar = _lib.NormBwdParams(_lib.view4(gd), _lib.view4(x), _lib.view4(gy if fused_res else None), _lib.view4(self.G(x)),
                                           B, cin, F, T, 8, norm_stats.data_ptr(), dws.data_ptr(), 1e-7,
                                           alpha * res_scale * gmul, 1 if self._gacc(x) else 0, nd)
@@ -658,11 +671,11 @@ class _Builder:
                     self._nb_src[self._vkey(gxv)] = (npar, len(self.plan.ops) - 1, hi, nop)
             else:
                 gx = self.G(x)
-                self._conv_raw(gin, gx, wpT, cout, cin, kh, kw, dil, gsc, 0, in_scale, gx if self._gacc(x) else None, 1.0 / alpha, alpha,
+                self._conv_raw(gin, gx, rec.dgrad[0], cout, cin, kh, kw, dil, gsc, 0, in_scale, gx if self._gacc(x) else None, 1.0 / alpha, alpha,
                                epi=1 if act else 0, aux=x if act else None, aux_scale=in_scale if act else None)
-                if self.train and wname is not None:
+                if self.train and rec.name is not None:
                     assert in_scale is None, "a scaled conv input without its statistics buffer has no parameter-gradient path"
-                    self._train_conv(x, gy, None, wname, cin, cout, kh, kw, dil, None, act, out_scale, alpha, wpw=wpw)
+                    self._train_conv(x, gy, None, rec, cin, cout, kh, kw, dil, None, act, out_scale, alpha)
         self._reg_bwd(bw)
 
 
@@ -834,6 +847,7 @@ class Unet_CQT_oct_with_attention(nn.Module):
                 _ResBlock(dim_in, dim_out, self.num_dils[i], (5, 3), E, attention=bool(self.attention_layers[i]),
                           fdim=(i + 1) * bpo, **akw)]))
         self._packed: Dict[str, torch.Tensor] = {}
+        self._conv_packs: Dict[str, _ConvPacks] = {}
         self._packed_ver = None
         self._states: Dict[tuple, dict] = {}
         self._mod_layout = None
@@ -874,10 +888,9 @@ class Unet_CQT_oct_with_attention(nn.Module):
                 self._packed[key] = t.clone()
                 self._states.clear()             # cached launch plans hold raw pointers into the replaced pack
 
-        def ensure(key, shape):
-            t = self._packed.get(key)
+        def ensure(t, shape):
             if t is None or tuple(t.shape) != tuple(shape) or t.device != dev:
-                t = self._packed[key] = torch.empty(*shape, device=dev, dtype=torch.float32)
+                t = torch.empty(*shape, device=dev, dtype=torch.float32)
                 self._states.clear()
             return t
 
@@ -888,20 +901,20 @@ class Unet_CQT_oct_with_attention(nn.Module):
                 wd = w.detach()
                 co, ci = wd.shape[0], wd.shape[1]
                 kh, kw = (wd.shape[2], wd.shape[3]) if wd.dim() == 4 else (1, wd.shape[2])
-                wino = wd.dim() == 4 and (kh, kw) == (5, 3) and co >= 64 and ci >= 64       # Winograd F(4,3) packs
                 if wd.dtype != torch.float32 or not wd.is_contiguous():
                     wd = wd.float().contiguous()
+                wf = self.wino_forms
+                w4 = wd.dim() == 4 and (kh, kw) == (5, 3) and co >= 64 and ci >= 64                # Winograd packs (2-D ones: C >= 128 / 96 layers)
+                w2 = w4 and (45 in wf or 85 in wf) and ((co % 128 == 0 and ci % 128 == 0) or (self.w2d_c96_max_T > 0 and co % 96 == 0 and ci % 96 == 0))
+                forms = [f for f, on in ((0, True), (4, w4), (8, w4 and 8 in wf), (45, w2), (85, w2 and 85 in wf)) if on]
                 (cip, cop), (cipT, copT) = _lib.pack_dims(ci, co), _lib.pack_dims(co, ci)
-                w8 = wino and 8 in self.wino_forms                                            # F(8,3) packs (50 taps)
-                w2 = wino and (45 in self.wino_forms or 85 in self.wino_forms) and ((co % 128 == 0 and ci % 128 == 0) or (self.w2d_c96_max_T > 0 and co % 96 == 0 and ci % 96 == 0))       # 2-D F(4,5) x F(4,3) packs (48 planes; C >= 128 layers)
-                w3 = w2 and 85 in self.wino_forms                                              # ... and its F(8,3)-along-T variant (80 planes)
-                bufs = [ensure(name, (kh * kw, cip, cop)), ensure(name + "#T", (kh * kw, cipT, copT)),
-                        ensure(name + "#W", (30, cip, cop)) if wino else None, ensure(name + "#WT", (30, cipT, copT)) if wino else None,
-                        ensure(name + "#W8", (50, cip, cop)) if w8 else None, ensure(name + "#W8T", (50, cipT, copT)) if w8 else None,
-                        ensure(name + "#W2", (48, cip, cop)) if w2 else None, ensure(name + "#W2T", (48, cipT, copT)) if w2 else None,
-                        ensure(name + "#W3", (80, cip, cop)) if w3 else None, ensure(name + "#W3T", (80, cipT, copT)) if w3 else None]
-                pp = _lib.PackConvWeightParams(wd.data_ptr(), bufs[0].data_ptr(), bufs[1].data_ptr(), _lib.ptr(bufs[2]), _lib.ptr(bufs[3]),
-                                               co, ci, kh, kw, cip, cop, cipT, copT, _lib.ptr(bufs[4]), _lib.ptr(bufs[5]), _lib.ptr(bufs[6]), _lib.ptr(bufs[7]), _lib.ptr(bufs[8]), _lib.ptr(bufs[9]))
+                old = self._conv_packs.get(name, _ConvPacks(name, {}, {}))
+                rec = self._conv_packs[name] = _ConvPacks(name, {}, {})
+                for f in forms:
+                    taps = _FORMS[f].taps or kh * kw
+                    rec.fwd[f], rec.dgrad[f] = ensure(old.fwd.get(f), (taps, cip, cop)), ensure(old.dgrad.get(f), (taps, cipT, copT))
+                pk = [_lib.ptr(packs.get(f)) for f in _FORMS for packs in (rec.fwd, rec.dgrad)]      # (the struct's order: form by form, forward first)
+                pp = _lib.PackConvWeightParams(wd.data_ptr(), *pk[:4], co, ci, kh, kw, cip, cop, cipT, copT, *pk[4:])
                 _lib.call("aid_pack_conv_weight", pp)       # all layouts of this weight in one launch (same values as _lib.pack_conv_weight*)
             elif leaf == "gamma":
                 put(name, w.detach().reshape(-1).float())
@@ -910,7 +923,7 @@ class Unet_CQT_oct_with_attention(nn.Module):
         for pfx, blk in self._resblocks():
             if hasattr(blk, "proj_in") and hasattr(blk, "res_conv") and blk.proj_place == "before" and blk.N % 16 == 0 and blk.dim >= 32 and blk.dim % 16 == 0:
                 n = blk.N
-                a, b = self._packed[pfx + "proj_in.weight#T"], self._packed[pfx + "res_conv.weight#T"]
+                a, b = self._conv_packs[pfx + "proj_in.weight"].dgrad[0], self._conv_packs[pfx + "res_conv.weight"].dgrad[0]
                 cip, cop = _lib.pack_dims(2 * n, blk.dim)
                 assert a.shape[2] == cop and b.shape[2] == cop
                 t = torch.zeros(1, cip, cop, device=dev, dtype=torch.float32)
@@ -969,29 +982,26 @@ class Unet_CQT_oct_with_attention(nn.Module):
     def _emit_resblock(self, bd: _Builder, st, pfx: str, blk: _ResBlock, xin, yout, prev_out=None):
         B, _, F, T = xin.shape
         N, W = blk.N, self._packed
+        cw = lambda nm: self._conv_packs[pfx + nm + ".weight"]      # the packs of one conv weight of this block
         x = xin
         pair = ((pfx + "#pairT") in W and not bd.train and self.merge_pair_dgrad
                 and bool(_lib.lib().aid_conv2d_x2_supported(2 * N, N, blk.dim, F, T)))
         if hasattr(blk, "proj_in"):
             x = bd.buf(B, N, F, T)
+            bd.conv(xin, x, cw("proj_in").fwd[0] if pair else cw("proj_in"), blk.dim, N)
             if pair:                                     # forward as always; the input gradients of proj_in and res_conv are taken together
-                bd.conv(xin, x, W[pfx + "proj_in.weight"], blk.dim, N)
                 bd.pair_dgrad(xin, x, yout, W[pfx + "#pairT"], N, blk.dim)
-            else:
-                bd.conv(xin, x, W[pfx + "proj_in.weight"], blk.dim, N, wpT=W[pfx + "proj_in.weight#T"], wname=pfx + "proj_in.weight")
         if blk.has_attn:
             H = blk.heads
             assert F == blk.fdim, "attention block built for a different number of frequency rows"
             sc, stb = bd.buf(B, N), bd.buf(B, 8, 2)
             bd.stats(x, W[pfx + "norm2.gamma"], self._mod(st, pfx + "affine2"), sc, stb, gname=pfx + "norm2.gamma")
             xp = bd.buf(B, H, F, T)
-            bd.conv(x, xp, W[pfx + "attn_block.proj_in.weight"], N, H, in_scale=sc, wpT=W[pfx + "attn_block.proj_in.weight#T"],
-                    norm_stats=stb, wname=pfx + "attn_block.proj_in.weight")
+            bd.conv(x, xp, cw("attn_block.proj_in"), N, H, in_scale=sc, norm_stats=stb)
             qk = bd.buf(B, 2 * H * F, 1, T)
             qb = W.get(pfx + "attn_block.qk.bias#T")                         # bias_qkv (unet...py:321): rides on the conv's residual input
-            bd.conv(xp.view(B, H * F, 1, T), qk, W[pfx + "attn_block.qk.weight"], H * F, 2 * H * F,
-                    wpT=W[pfx + "attn_block.qk.weight#T"],
-                    res=None if qb is None else qb.view(1, 2 * H * F, 1, T).expand(B, -1, -1, -1), res_nograd=True, wname=pfx + "attn_block.qk.weight")
+            bd.conv(xp.view(B, H * F, 1, T), qk, cw("attn_block.qk"), H * F, 2 * H * F,
+                    res=None if qb is None else qb.view(1, 2 * H * F, 1, T).expand(B, -1, -1, -1), res_nograd=True)
             if bd.train and qb is not None:
                 bd.bias_grad(qk, pfx + "attn_block.qk.bias")
             att = bd.buf(B, H, F, T)
@@ -999,38 +1009,26 @@ class Unet_CQT_oct_with_attention(nn.Module):
             bd.attention(qk, xp, att, H, F, T, bias=rpb,                       # use_rel_pos (:364)
                          relpos=None if rpb is None else (W[pfx + "attn_block.rel_pos#bucket"], pfx + "attn_block.rel_pos.relative_attention_bias.weight"))
             x1 = bd.buf(B, N, F, T)
-            bd.conv(att, x1, W[pfx + "attn_block.proj_out.weight"], H, N, out_scale=self._mod(st, pfx + "gate2"), res=x,
-                    alpha=RSQRT2, wpT=W[pfx + "attn_block.proj_out.weight#T"], wname=pfx + "attn_block.proj_out.weight")
+            bd.conv(att, x1, cw("attn_block.proj_out"), H, N, out_scale=self._mod(st, pfx + "gate2"), res=x, alpha=RSQRT2)
             x = x1
         kh, kw = blk.ks
         for k in range(blk.num_dils):
             sc, stb = bd.buf(B, N), bd.buf(B, 8, 2)
             bd.stats(x, W[pfx + f"norm.{k}.gamma"], self._mod(st, pfx + f"affine.{k}"), sc, stb, gname=pfx + f"norm.{k}.gamma")
             xn = bd.buf(B, N, F, T)
-            bd.conv(x, xn, W[pfx + f"H.{k}.weight"], N, N, kh, kw, dil=(2 ** k if kh > 1 else 1), in_scale=sc, act=1,
-                    out_scale=self._mod(st, pfx + f"gate.{k}"), res=x, alpha=RSQRT2, wpT=W[pfx + f"H.{k}.weight#T"],
-                    norm_stats=stb, wpw=W.get(pfx + f"H.{k}.weight#W"), wpwT=W.get(pfx + f"H.{k}.weight#WT"), wname=pfx + f"H.{k}.weight",
-                    wpw8=W.get(pfx + f"H.{k}.weight#W8"), wpw8T=W.get(pfx + f"H.{k}.weight#W8T"),
-                    wpw2=W.get(pfx + f"H.{k}.weight#W2"), wpw2T=W.get(pfx + f"H.{k}.weight#W2T"),
-                    wpw3=W.get(pfx + f"H.{k}.weight#W3"), wpw3T=W.get(pfx + f"H.{k}.weight#W3T"))
+            bd.conv(x, xn, cw(f"H.{k}"), N, N, kh, kw, dil=(2 ** k if kh > 1 else 1), in_scale=sc, act=1,
+                    out_scale=self._mod(st, pfx + f"gate.{k}"), res=x, alpha=RSQRT2, norm_stats=stb)
             x = xn
         if blk.proj_place == "after":
             assert hasattr(blk, "proj_out") and hasattr(blk, "res_conv")
             t1 = bd.buf(B, blk.dim_out, F, T)
-            if prev_out is not None:   # (Xout + OutBlock(X))/sqrt2 folded in (unet...py:817)
-                bd.conv(xin, t1, W[pfx + "res_conv.weight"], blk.dim, blk.dim_out, res=prev_out, res_scale=SQRT2,
-                        wpT=W[pfx + "res_conv.weight#T"], wname=pfx + "res_conv.weight")
-                a2 = 0.5
-            else:
-                bd.conv(xin, t1, W[pfx + "res_conv.weight"], blk.dim, blk.dim_out, wpT=W[pfx + "res_conv.weight#T"], wname=pfx + "res_conv.weight")
-                a2 = RSQRT2
-            bd.conv(x, yout, W[pfx + "proj_out.weight"], N, blk.dim_out, res=t1, alpha=a2, wpT=W[pfx + "proj_out.weight#T"], wname=pfx + "proj_out.weight")
-        elif hasattr(blk, "res_conv") and pair:
-            bd.conv(xin, yout, W[pfx + "res_conv.weight"], blk.dim, blk.dim_out, res=x, alpha=RSQRT2)
-            bd.res_grad(x, yout, RSQRT2)
+            po = prev_out is not None  # (Xout + OutBlock(X))/sqrt2 folded in (unet...py:817)
+            bd.conv(xin, t1, cw("res_conv"), blk.dim, blk.dim_out, res=prev_out, res_scale=SQRT2 if po else 1.0)
+            bd.conv(x, yout, cw("proj_out"), N, blk.dim_out, res=t1, alpha=0.5 if po else RSQRT2)
         elif hasattr(blk, "res_conv"):
-            bd.conv(xin, yout, W[pfx + "res_conv.weight"], blk.dim, blk.dim_out, res=x, alpha=RSQRT2,
-                    wpT=W[pfx + "res_conv.weight#T"], wname=pfx + "res_conv.weight")
+            bd.conv(xin, yout, cw("res_conv").fwd[0] if pair else cw("res_conv"), blk.dim, blk.dim_out, res=x, alpha=RSQRT2)
+            if pair:                                     # (its input gradient is taken by pair_dgrad; the residual's is this)
+                bd.res_grad(x, yout, RSQRT2)
         else:
             bd.add2(x, xin, yout, RSQRT2, RSQRT2)
 
@@ -1122,14 +1120,14 @@ class Unet_CQT_oct_with_attention(nn.Module):
                     pyr = pyrL
             hs = D[i][:, Ns[i]:, :, :]
             self._emit_resblock(bd, st, f"downs.{i}.2.", self.downs[i][2], Xb[i], hs)
-            wpyr, wpyrT = W[f"downs.{i}.1.weight"], W[f"downs.{i}.1.weight#T"]
+            wpyr = self._conv_packs[f"downs.{i}.1.weight"]
             if i < n - 1:
                 Xd = bd.buf(B, Ns[i], Fl[i], Tl[i] // 2)
                 bd.resample(hs, Xd, up=0)
-                bd.conv(pyr, Xb[i + 1][:, :, bpo:, :], wpyr, 2, Ns[i], 5, 3, dil=1, res=Xd, alpha=RSQRT2, wpT=wpyrT, wname=f"downs.{i}.1.weight")   # (:794)
+                bd.conv(pyr, Xb[i + 1][:, :, bpo:, :], wpyr, 2, Ns[i], 5, 3, dil=1, res=Xd, alpha=RSQRT2)   # (:794)
             else:
                 Xmid = bd.buf(B, Ns[i], Fl[i], Tl[i])
-                bd.conv(pyr, Xmid, wpyr, 2, Ns[i], 5, 3, dil=1, res=hs, alpha=RSQRT2, wpT=wpyrT, wname=f"downs.{i}.1.weight")
+                bd.conv(pyr, Xmid, wpyr, 2, Ns[i], 5, 3, dil=1, res=hs, alpha=RSQRT2)
             pyr_prev = pyr
         # -- bottleneck (:800-804) --------------------------------------------------------------------------------
         Xcur = Xmid
