@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the EDM inpainting sampling hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--xi 0|0.25] [--batch 8] [--workload ...] [--gap-ms G] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--xi 0|0.25] [--batch 8] [--workload ...] [--gap-ms G] [--dump-outputs DIR] [--full]
 
 N > 1: either the driver's form (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
 127.0.0.1 ... bench.py --gpus N ...), or plain `python bench.py --gpus N`, which re-launches itself that way
@@ -20,7 +20,10 @@ segments; the only collective is the start-up weight broadcast (not timed).
 Default branch: xi=0.25 = reconstruction guidance, the reference tester's shipped setting: every evaluation is a
 forward pass PLUS the input-VJP through the whole denoiser (--xi 0 times the forward-only replacement branch).
 
-roofline (fp32 MFMA, peak 157.3 TFLOP/s): every aid_conv2d launch of a single-stream pass (forward and VJP plans) is
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, --dump-outputs, the result line.  --full adds what takes
+runs of its own after the timed region: the `roofline` section (with the per-kernel tables and --conv-table) and, at N=1, `cpu_baseline`.
+
+roofline (--full; fp32 MFMA, peak 157.3 TFLOP/s): every aid_conv2d launch of a single-stream pass (forward and VJP plans) is
 bracketed by HIP events on the launch stream and attributed to the device kernel it dispatched to (aid_last_kernel).
 The line reports the DOMINANT kernel BY ITS ROCPROF NAME (most GPU time: conv53_wino8r_kernel, the 5x3 layers in Winograd
 F(8,3) form; conv53_wino4r_kernel = F(4,3) takes the launches whose tiles quantise better that way), over ALL its template instances / tile
@@ -34,7 +37,7 @@ kinds (`families` keeps the sub-family table):
 of the dominant kernel from the PMC passes of this same command (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate runs, --streams 1, FETCH
 doubled for gfx950) committed under profiles/ -- counters cannot be read from inside this process; traffic_over_algorithmic relates it to this
 run's algorithmic bytes per launch.
-cpu_baseline: the CPU oracle (torch-CPU restatement of the reference path, oracle/) timed on this host's cores for the same
+cpu_baseline (--full): the CPU oracle (torch-CPU restatement of the reference path, oracle/) timed on this host's cores for the same
 network and branch at B=1 (rank 0, N=1 only): per thread placement (physical cores of one socket / all physical cores) one warm-up and one
 timed evaluation OF THE SAME BRANCH (a placement whose warm-up is already 1.5x slower is not timed again), then two more on the fastest placement; value = 1 / median of its three timings, `cores` = its thread count.
 """
@@ -270,8 +273,10 @@ def main():
     ap.add_argument("--gap-ms", type=float, default=0.0, help="gap length in ms (default by workload: 300 / 50 / 1500; "
                                                               "configs[3] sweeps 25 / 50 / 100, conf/tester/inpainting_tester_shortgaps.yaml:74-75)")
     ap.add_argument("--streams", type=int, default=0, help="sub-batch HIP streams per evaluation (default: automatic, network._n_split; 1 = plain single-stream schedule)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--roof-steps", type=int, default=3, help="Heun steps of the single-stream roofline pass after the timed region (>= 1; 3 by default)")
+    ap.add_argument("--full", action="store_true", help="after the timed region also run the single-stream roofline pass and, at --gpus 1, the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--roof-steps", type=int, default=3, help="Heun steps of the single-stream roofline pass after the timed region (--full; >= 1; 3 by default). "
+                    "The schedule positions it needs are reserved with or without --full, so the timed steps do not depend on --full")
     ap.add_argument("--no-graphs", action="store_true", help="(the default since round 5) eager launches at small batches")
     ap.add_argument("--graphs", action="store_true", help="A/B: HIP-graph replay of the evaluation at small batches (network.use_graphs; the default until round 4)")
     ap.add_argument("--no-pair-merge", action="store_true", help="A/B: separate input-gradient convs for proj_in and res_conv")
@@ -294,10 +299,12 @@ def main():
                     "on the last N / 8 CUs of every XCD, on CU-masked streams (network.cu_partition, streams.py); 0 = free-running sub-batch streams (the product schedule)")
     ap.add_argument("--cu-split", default="", help="EXPERIMENT (A/B): CUs per XCD for each sub-batch stream, e.g. 16,16 (disjoint halves) or 20,20 (overlapping) -- CU-masked sub-batch streams "
                     "without any cross-stream events (network.cu_split)")
-    ap.add_argument("--conv-table", action="store_true", help="print per-shape conv kernel times (stderr)")
+    ap.add_argument("--conv-table", action="store_true", help="print per-shape conv kernel times of the roofline pass (stderr; needs --full)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step returned (the sampler state x of "
                     "every segment, gathered over ranks) as DIR/<name>.npy in float32 (dump_outputs)")
     a = ap.parse_args()
+    if a.conv_table and not a.full:
+        ap.error("--conv-table needs --full")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started as a plain process: become the launcher of N ranks of this same command
@@ -393,7 +400,8 @@ def main():
 
     # Every timed step is a Heun step (2 evaluations; the last step of a schedule is Euler): positions 0 .. T-4 of the schedule are walked,
     # and when --warmup + --steps exceed them the sampler starts the next batch's trajectory (smp.begin) inside the run, as a job over many
-    # batches of segments does.  Two positions stay in reserve for the single-stream roofline pass.
+    # batches of segments does.  ROOF_STEPS + 1 positions stay in reserve for the single-stream roofline pass, with or without --full: the
+    # timed steps walk the same positions either way.
     ROOF_STEPS = max(1, a.roof_steps)                  # Heun steps of the single-stream roofline pass (after one warm-up step)
     span = T - 2 - (ROOF_STEPS + 1)
     if a.cu_split or a.cu_partition:
@@ -433,28 +441,30 @@ def main():
         x_last = D.gather_outputs(state["x"], world * B)
         if rank == 0:
             dump_outputs(a.dump_outputs, {"x": x_last})
-    # Kernel speeds are measured right after the timed region: the SAME sampler continues for one warm-up and ROOF_STEPS measured
-    # Heun steps with the network forced onto one stream and eager launches (the product schedule overlaps kernels of different
-    # sub-batches on concurrent HIP streams, or replays a captured HIP graph: a launch's start-to-end time there is not the kernel's speed).
-    roofline_pass = ("separate single-stream pass of eager launches: 1 warm-up + %d measured Heun steps (steps %d..%d of the same run) right after "
-                     "the timed region, %s" % (ROOF_STEPS, jlast + 2, jlast + 1 + ROOF_STEPS,
-                                                "which replays a captured HIP graph per evaluation" if graphs else
-                                                ("whose %d sub-batch streams overlap kernels" % n_split if n_split > 1 else "which runs the same single-stream schedule")))
-    assert jlast + 1 + ROOF_STEPS <= T - 2
-    net.split_streams, use_graphs = 1, net.use_graphs
-    net.use_graphs = False
-    smp.step(state, jlast + 1)
-    for pl in net.timed_plans(B, a.xi > 0):
-        pl.timing = timing
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for k in range(ROOF_STEPS):
-        smp.step(state, jlast + 2 + k)
-    torch.cuda.synchronize()
-    wall_serial = (time.perf_counter() - t1) / ROOF_STEPS
-    for pl in net.timed_plans(B, a.xi > 0):
-        pl.timing = None
-    net.split_streams, net.use_graphs = (a.streams or None), use_graphs
+    wall_serial = None
+    if a.full:
+        # Kernel speeds are measured right after the timed region: the SAME sampler continues for one warm-up and ROOF_STEPS measured
+        # Heun steps with the network forced onto one stream and eager launches (the product schedule overlaps kernels of different
+        # sub-batches on concurrent HIP streams, or replays a captured HIP graph: a launch's start-to-end time there is not the kernel's speed).
+        roofline_pass = ("separate single-stream pass of eager launches: 1 warm-up + %d measured Heun steps (steps %d..%d of the same run) right after "
+                         "the timed region, %s" % (ROOF_STEPS, jlast + 2, jlast + 1 + ROOF_STEPS,
+                                                    "which replays a captured HIP graph per evaluation" if graphs else
+                                                    ("whose %d sub-batch streams overlap kernels" % n_split if n_split > 1 else "which runs the same single-stream schedule")))
+        assert jlast + 1 + ROOF_STEPS <= T - 2
+        net.split_streams, use_graphs = 1, net.use_graphs
+        net.use_graphs = False
+        smp.step(state, jlast + 1)
+        for pl in net.timed_plans(B, a.xi > 0):
+            pl.timing = timing
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for k in range(ROOF_STEPS):
+            smp.step(state, jlast + 2 + k)
+        torch.cuda.synchronize()
+        wall_serial = (time.perf_counter() - t1) / ROOF_STEPS
+        for pl in net.timed_plans(B, a.xi > 0):
+            pl.timing = None
+        net.split_streams, net.use_graphs = (a.streams or None), use_graphs
 
     if a.conv_table and rank == 0:
         agg = {}
@@ -465,23 +475,15 @@ def main():
         for d, (n, ms, f) in sorted(agg.items(), key=lambda kv: -kv[1][1]):
             print("%-100s n=%3d  %8.3f ms/launch  %6.1f TF/s  %5.1f%% of conv time" % (d, n, ms / n, f / ms / 1e9, 100 * ms / conv_ms), file=sys.stderr)
     evals = world * B * 2 * a.steps
-    # every rank's own line (where it ran, its own wall clock, broadcast time, single-stream step): a slow SCALE line can be read without a rerun
+    # every rank's own line (where it ran, its own wall clock, broadcast time, single-stream step under --full): a slow SCALE line can be read without a rerun
     ranks = D.gather_objects(D.rank_report(rank, local, wall_s=wall_rank, bcast_s=t_bcast, ms_per_step=1e3 * wall_rank / a.steps,
-                                           single_stream_ms_per_step=1e3 * wall_serial, segments=[lo, hi]))
+                                           single_stream_ms_per_step=(1e3 * wall_serial if a.full else None), segments=[lo, hi]))
     if rank == 0:
         problems = D.placement_problems(ranks, shared=bool(shared), shared_requested=bool(int(os.environ.get("AID_SHARED_GPU", "0"))),
                                         visible_gpus=torch.cuda.device_count())
         for msg in problems["warnings"]:
             print("bench: WARNING: " + msg, file=sys.stderr)
         assert not problems["errors"], "; ".join(problems["errors"])
-        fams = family_table(timing)
-        kerns = family_table(timing, by_kernel=True)
-        dom_name = next((k for k, v in kerns.items() if v["executed_mfma_tflops"] > 0), None)      # the MFMA kernel with the most GPU time (the 2-D form's output pass is timed as conv time but issues no MFMA)
-        dom = kerns.get(dom_name, {})
-        conv_ms = sum(v["time_ms"] for v in fams.values())
-        alg = sum(t[2] for t in timing)
-        exe = sum(t[2] * exec_fraction(t[5]) for t in timing)
-        sec = max(conv_ms * 1e-3, 1e-12)
         out = {
             "metric": "denoiser-steps/sec", "value": round(evals / wall, 3), "unit": "denoiser evaluations (one segment each) per second, whole job",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(1e3 * wall / a.steps, 2), "host_enqueue_ms_per_step": round(1e3 * host_enqueue / a.steps, 2),
@@ -502,30 +504,39 @@ def main():
                        "backend": (torch.distributed.get_backend() if world > 1 else "single process"), "rccl_version": D.rccl_version(),
                        "visible_gpus": torch.cuda.device_count()},
             "ranks": ranks,
-            "roofline": {"bound": "mfma", "kernel": dom_name, "measured_in": roofline_pass,
-                         "definition": "achieved = MFMA FLOPs issued by ALL launches of the dominant kernel (the MFMA-issuing conv / GEMM kernel with the most GPU time, by device-kernel name, every template instance / tile kind) "
-                                       "/ their summed duration (HIP events around each launch); Winograd F(4,3) issues 1/2, F(8,3) 5/12 and the 2-D forms (w2d_gemm_kernel: every 5x3 layer "
-                                       "of the C >= 128 levels 3-6 and the bottleneck that the library gives it) F(4,5) x F(4,3) 1/5 and F(4,5) x F(8,3) (instances named +t8) 1/6 of the direct-form FLOPs; the 2-D form's output-transform + epilogue pass "
-                                       "(w2d_output_kernel, HBM-bound, no FLOPs of its own) is timed as a conv launch too and counts in all_conv / conv_time_fraction_of_wall -- the fused 1-D kernels do that "
-                                       "work inside the timed kernel -- its input-transform pass is the counterpart of the fused kernels' aid_scale_act pre-pass and, like it, is not; "
-                                       "algorithmic_tflops = direct-form FLOPs / the same time; step_executed_frac = issued MFMA FLOPs of all conv / GEMM launches "
-                                       "of one step / ms_per_step of the timed region / peak; non_winograd_conv_time_fraction_single_stream = 1 - (time of ALL 5x3 Winograd MFMA kernels: "
-                                       "the fused 1-D kernels and the 2-D form's GEMM) / single-stream step time",
-                         "step_executed_frac": round(exe / ROOF_STEPS / (wall / a.steps) / 1e12 / PEAK_F32_MFMA, 4),
-                         "step_executed_tflops": round(exe / ROOF_STEPS / (wall / a.steps) / 1e12, 2),
-                         "non_winograd_conv_time_fraction_single_stream": round(1.0 - sum(v["time_ms"] for k, v in kerns.items() if k in WINO_EXEC) / ROOF_STEPS / (1e3 * wall_serial), 3),
-                         "non_dominant_kernel_time_fraction_single_stream": round(1.0 - dom.get("time_ms", 0.0) / ROOF_STEPS / (1e3 * wall_serial), 3),
-                         "achieved": dom.get("executed_mfma_tflops"), "peak": PEAK_F32_MFMA, "unit": "TFLOP/s", "frac": dom.get("frac_of_fp32_mfma_peak"),
-                         "algorithmic_tflops": dom.get("algorithmic_tflops"), "launches": dom.get("launches"), "avg_launch_us": dom.get("avg_launch_us"),
-                         "algorithmic_gflop_per_launch": dom.get("algorithmic_gflop_per_launch"),
-                         **_traffic_fields(dom_name, dom),
-                         "share_of_conv_time": round(dom.get("time_ms", 0.0) / max(conv_ms, 1e-9), 3),
-                         "all_conv": {"launches": len(timing), "executed_mfma_tflops": round(exe / sec / 1e12, 2), "frac_of_fp32_mfma_peak": round(exe / sec / 1e12 / PEAK_F32_MFMA, 4),
-                                      "algorithmic_tflops": round(alg / sec / 1e12, 2), "conv_time_fraction_of_wall": round(sec / (ROOF_STEPS * wall_serial), 3),
-                                      "single_stream_ms_per_step": round(1e3 * wall_serial, 2)},
-                         "kernels": kerns, "families": fams},
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full:
+            fams = family_table(timing)
+            kerns = family_table(timing, by_kernel=True)
+            dom_name = next((k for k, v in kerns.items() if v["executed_mfma_tflops"] > 0), None)      # the MFMA kernel with the most GPU time (the 2-D form's output pass is timed as conv time but issues no MFMA)
+            dom = kerns.get(dom_name, {})
+            conv_ms = sum(v["time_ms"] for v in fams.values())
+            alg = sum(t[2] for t in timing)
+            exe = sum(t[2] * exec_fraction(t[5]) for t in timing)
+            sec = max(conv_ms * 1e-3, 1e-12)
+            out["roofline"] = {"bound": "mfma", "kernel": dom_name, "measured_in": roofline_pass,
+                               "definition": "achieved = MFMA FLOPs issued by ALL launches of the dominant kernel (the MFMA-issuing conv / GEMM kernel with the most GPU time, by device-kernel name, every template instance / tile kind) "
+                                             "/ their summed duration (HIP events around each launch); Winograd F(4,3) issues 1/2, F(8,3) 5/12 and the 2-D forms (w2d_gemm_kernel: every 5x3 layer "
+                                             "of the C >= 128 levels 3-6 and the bottleneck that the library gives it) F(4,5) x F(4,3) 1/5 and F(4,5) x F(8,3) (instances named +t8) 1/6 of the direct-form FLOPs; the 2-D form's output-transform + epilogue pass "
+                                             "(w2d_output_kernel, HBM-bound, no FLOPs of its own) is timed as a conv launch too and counts in all_conv / conv_time_fraction_of_wall -- the fused 1-D kernels do that "
+                                             "work inside the timed kernel -- its input-transform pass is the counterpart of the fused kernels' aid_scale_act pre-pass and, like it, is not; "
+                                             "algorithmic_tflops = direct-form FLOPs / the same time; step_executed_frac = issued MFMA FLOPs of all conv / GEMM launches "
+                                             "of one step / ms_per_step of the timed region / peak; non_winograd_conv_time_fraction_single_stream = 1 - (time of ALL 5x3 Winograd MFMA kernels: "
+                                             "the fused 1-D kernels and the 2-D form's GEMM) / single-stream step time",
+                               "step_executed_frac": round(exe / ROOF_STEPS / (wall / a.steps) / 1e12 / PEAK_F32_MFMA, 4),
+                               "step_executed_tflops": round(exe / ROOF_STEPS / (wall / a.steps) / 1e12, 2),
+                               "non_winograd_conv_time_fraction_single_stream": round(1.0 - sum(v["time_ms"] for k, v in kerns.items() if k in WINO_EXEC) / ROOF_STEPS / (1e3 * wall_serial), 3),
+                               "non_dominant_kernel_time_fraction_single_stream": round(1.0 - dom.get("time_ms", 0.0) / ROOF_STEPS / (1e3 * wall_serial), 3),
+                               "achieved": dom.get("executed_mfma_tflops"), "peak": PEAK_F32_MFMA, "unit": "TFLOP/s", "frac": dom.get("frac_of_fp32_mfma_peak"),
+                               "algorithmic_tflops": dom.get("algorithmic_tflops"), "launches": dom.get("launches"), "avg_launch_us": dom.get("avg_launch_us"),
+                               "algorithmic_gflop_per_launch": dom.get("algorithmic_gflop_per_launch"),
+                               **_traffic_fields(dom_name, dom),
+                               "share_of_conv_time": round(dom.get("time_ms", 0.0) / max(conv_ms, 1e-9), 3),
+                               "all_conv": {"launches": len(timing), "executed_mfma_tflops": round(exe / sec / 1e12, 2), "frac_of_fp32_mfma_peak": round(exe / sec / 1e12 / PEAK_F32_MFMA, 4),
+                                            "algorithmic_tflops": round(alg / sec / 1e12, 2), "conv_time_fraction_of_wall": round(sec / (ROOF_STEPS * wall_serial), 3),
+                                            "single_stream_ms_per_step": round(1e3 * wall_serial, 2)},
+                               "kernels": kerns, "families": fams}
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(net, args, guided=a.xi > 0, spectral=a.task == "spectrogram")
             out["cpu_baseline"]["gpu_over_cpu"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
         print(json.dumps(out), flush=True)

@@ -510,9 +510,9 @@ def test_config2_job_shape_eight_ranks_several_segments_each_on_one_gpu():
 
 
 def test_bench_self_launches_eight_ranks_rank0_only_json():
-    """`python bench.py --gpus 8 --batch 1 --steps 1 --warmup 0` as the driver will start it (here: self-launched, 8 ranks on the visible GPUs):
-    ONE JSON line, from rank 0, n_gpus 8, whole-job value; every rank logs its backend / device / CPU share on stderr."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "0", "--batch", "1", "--roof-steps", "1", "--no-cpu-baseline"]
+    """`python bench.py --gpus 8 --batch 1 --steps 1 --warmup 0` as the driver will start it (here: self-launched, 8 ranks on the visible GPUs), with
+    --full for the roofline section: ONE JSON line, from rank 0, n_gpus 8, whole-job value; every rank logs its backend / device / CPU share on stderr."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "0", "--batch", "1", "--roof-steps", "1", "--no-cpu-baseline", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=2400, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -9,7 +9,7 @@ for v in 0 1; do
 done
 for i in 1 2; do for v in 0 1; do
   if [ $v = 0 ]; then unset AID_EXPERIMENT AID_LIB_PATH; else export AID_EXPERIMENT=1 AID_LIB_PATH=$PWD/tools/exp/libaid_n2.so; fi
-  echo "variant $v batch 8: $(timeout 900 python bench.py --steps 4 --warmup 2 --no-cpu-baseline 2>/dev/null | line)" >> $out
-  echo "variant $v batch 1: $(timeout 900 python bench.py --batch 1 --steps 4 --warmup 2 --no-cpu-baseline 2>/dev/null | line)" >> $out
+  echo "variant $v batch 8: $(timeout 900 python bench.py --steps 4 --warmup 2 --no-cpu-baseline --full 2>/dev/null | line)" >> $out
+  echo "variant $v batch 1: $(timeout 900 python bench.py --batch 1 --steps 4 --warmup 2 --no-cpu-baseline --full 2>/dev/null | line)" >> $out
 done; done
 cat $out

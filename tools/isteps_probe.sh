@@ -10,6 +10,6 @@ for v in 5 3 2 1; do
 done
 for i in 1 2; do for v in 5 3 2 1; do
   if [ $v = 5 ]; then unset AID_EXPERIMENT AID_LIB_PATH; else export AID_EXPERIMENT=1 AID_LIB_PATH=$PWD/tools/exp/libaid_i$v.so; fi
-  echo "issue steps $v: $(timeout 900 python bench.py --steps 4 --warmup 2 --no-cpu-baseline 2>/dev/null | line)" >> $out
+  echo "issue steps $v: $(timeout 900 python bench.py --steps 4 --warmup 2 --no-cpu-baseline --full 2>/dev/null | line)" >> $out
 done; done
 cat $out

@@ -2,7 +2,7 @@
 # Round-2 measurement sweep (run on the GPU box; everything lands in gpurun_out/r02_*; copy into profiles/ what should be judged).
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out
-run() { python bench.py --no-cpu-baseline "$@" 2>/dev/null; }
+run() { python bench.py --full --no-cpu-baseline "$@" 2>/dev/null; }
 {
   run --xi 0
   run --workload librispeech16k --gap-ms 25

@@ -4,10 +4,10 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out
 parts=${@:-bench variants small prof pmc pointwise traces e2e train c11}
-run() { python bench.py --no-cpu-baseline "$@" 2>/dev/null; }
+run() { python bench.py --full --no-cpu-baseline "$@" 2>/dev/null; }
 for part in $parts; do case $part in
 bench)
-  python bench.py 2>/dev/null > $O/r03_bench_guided.json                       # the driver's command (with the CPU baseline)
+  python bench.py --full 2>/dev/null > $O/r03_bench_guided.json                # the full line (with the CPU baseline)
   run --streams 1 > $O/r03_bench_streams1.json
   run --steps 20 > $O/r03_bench_steps20.json ;;
 variants)
@@ -44,7 +44,7 @@ traces)
   python tools/plan_trace.py 8 maestro22k --list > $O/r03_trace_b8.txt 2>/dev/null
   python tools/plan_trace.py 1 maestro22k --list > $O/r03_trace_b1.txt 2>/dev/null
   python tools/plan_trace.py 4 musicnet44k > $O/r03_trace_cfgB_b4.txt 2>/dev/null
-  python bench.py --no-cpu-baseline --streams 1 --conv-table > /dev/null 2> $O/r03_conv_table.txt ;;
+  python bench.py --full --no-cpu-baseline --streams 1 --conv-table > /dev/null 2> $O/r03_conv_table.txt ;;
 e2e)
   { python tools/e2e_run.py maestro22k 8; python tools/e2e_run.py maestro22k 1; python tools/e2e_run.py musicnet44k 4; python tools/e2e_run.py librispeech16k 16; } > $O/r03_e2e_full_runs.txt 2>/dev/null ;;
 c11)

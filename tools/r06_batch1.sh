@@ -6,7 +6,7 @@ python -m pytest tests/test_gpu_dist.py -x -q -m gpu -k "cu_partitioned" -s 2>&1
 python -m pytest tests/test_gpu_configs.py -x -q -m gpu -k "eight_free_running" -s 2>&1 | tail -60 > $O/r06_test_traj.txt
 timeout 600 python tools/cu_mask_probe.py 4 256 384 64 2 > $O/r06_cu_mask_probe.txt 2>&1
 timeout 300 python tools/cu_mask_probe.py 4 128 320 128 4 2>&1 | grep -A20 "== 3" >> $O/r06_cu_mask_probe.txt
-B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1"
+B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1 --full"
 run() { echo "### $*" >> $O/r06_cu_partition_ab.txt; timeout 600 $B "$@" 2>>$O/r06_cu_partition_err.txt | python -c "
 import sys, json
 for ln in sys.stdin:

@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.."
 O=gpurun_out; mkdir -p $O
 python -m pytest tests/test_gpu_wino2d.py tests/test_gpu_vjp.py tests/test_gpu_network.py -x -q -m gpu -k "wino2d or norm_bwd or unet_full_cfgA_vs or fused_passes or full_size_guided" 2>&1 | grep -v amdgpu | tail -5 > $O/r06_b10_tests.txt
 for b in 4; do for l in "L1 C96" "L2 C96"; do PROBE_ONLY="$l" PROBE_TF=8 timeout 300 python tools/w2d_probe.py layer $b | grep -v "^layer"; done; done 2>&1 | grep -v amdgpu > $O/r06_w2d_c96_tf8_probe3.txt
-B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1"
+B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1 --full"
 F=$O/r06_b10_bench_ab.txt
 run() { echo "### $*" >> $F; timeout 600 $B "$@" 2>>$O/r06_b10_err.txt | python -c "
 import sys, json

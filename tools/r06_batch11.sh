@@ -5,7 +5,7 @@ O=gpurun_out; mkdir -p $O
 python -m pytest tests/test_gpu_wino2d.py tests/test_gpu_vjp.py tests/test_gpu_network.py tests/test_gpu_configs.py -x -q -m gpu -k "wino2d or norm_bwd or unet_full_cfgA_vs or fused_passes or full_size_guided or eight_free_running or network_vjp or cfgB" 2>&1 | grep -v amdgpu | tail -6 > $O/r06_b11_tests.txt
 ( echo "=== product build (fold M for Cin <= 128 on the 80-plane form) ==="; timeout 600 python tools/w2d_tf_probe.py 4 1 2>&1 | grep -v amdgpu
   echo "=== no-fold build ==="; AID_EXPERIMENT=1 AID_LIB_PATH=tools/exp/libaid_nofold.so timeout 600 python tools/w2d_tf_probe.py 4 1 2>&1 | grep -v amdgpu ) > $O/r06_w2d_foldm_layer_ab.txt
-B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1"
+B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1 --full"
 F=$O/r06_b11_bench_ab.txt
 run() { echo "### $*" >> $F; timeout 600 "$@" 2>>$O/r06_b11_err.txt | python -c "
 import sys, json

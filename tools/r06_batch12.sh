@@ -2,7 +2,7 @@
 # round 6, GPU batch 12: which launches fold the row transform into the GEMM -- workgroup-count threshold 768 / 1024 (product) / 1900 against no fold
 cd "$(dirname "$0")/.."
 O=gpurun_out; mkdir -p $O
-B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1"
+B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1 --full"
 F=$O/r06_b12_bench_ab.txt
 run() { echo "### $*" >> $F; timeout 600 "$@" 2>>$O/r06_b12_err.txt | python -c "
 import sys, json

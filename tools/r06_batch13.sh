@@ -2,7 +2,7 @@
 # round 6, GPU batch 13: folded-GEMM variants: three workgroups per CU, fold on the K = 256 levels too, workgroup threshold 512 -- against the product (768, 2 per CU, Cin <= 128)
 cd "$(dirname "$0")/.."
 O=gpurun_out; mkdir -p $O
-B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1"
+B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1 --full"
 F=$O/r06_b13_bench_ab.txt
 run() { echo "### $*" >> $F; timeout 600 "$@" 2>>$O/r06_b13_err.txt | python -c "
 import sys, json

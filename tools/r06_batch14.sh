@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/.."
 O=gpurun_out; mkdir -p $O
 python -m pytest tests/test_gpu_wino2d.py tests/test_gpu_dist.py -x -q -m gpu -s -k "folded_gemm or self_launches_eight" 2>&1 | grep -v amdgpu | tail -6 > $O/r06_b14_tests.txt
-B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1"
+B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1 --full"
 F=$O/r06_b14_bench_ab.txt
 run() { echo "### $*" >> $F; timeout 600 "$@" 2>>$O/r06_b14_err.txt | python -c "
 import sys, json

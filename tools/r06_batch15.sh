@@ -6,7 +6,7 @@ O=gpurun_out; mkdir -p $O
 X() { if [ "$1" = product ]; then echo env; else echo "env AID_EXPERIMENT=1 AID_LIB_PATH=tools/exp/libaid_$1.so"; fi; }
 LIBS="product nb4 nb5 kc32 w3 w3nb4"
 for l in $LIBS; do echo "=== $l"; $(X $l) timeout 300 python -m pytest tests/test_gpu_wino2d.py -x -q -m gpu -s -k "folded_gemm" 2>&1 | grep -v amdgpu | grep "folded GEMM\|passed\|failed\|Error" ; done > $O/r06_b15_tests.txt
-B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1"
+B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1 --full"
 F=$O/r06_b15_bench_ab.txt
 run() { echo "### $*" >> $F; timeout 600 "$@" 2>>$O/r06_b15_err.txt | python -c "
 import sys, json

@@ -7,7 +7,7 @@ X() { if [ "$1" = product ]; then echo env; else echo "env AID_EXPERIMENT=1 AID_
 timeout 900 python -m pytest tests/test_gpu_wino2d.py tests/test_gpu_network.py -x -q -m gpu 2>&1 | grep -v amdgpu | tail -4 > $O/r06_b16_tests.txt
 timeout 300 python -m pytest tests/test_gpu_wino2d.py -x -q -m gpu -s -k "folded_gemm" 2>&1 | grep "folded GEMM\|passed\|failed\|Error" >> $O/r06_b16_tests.txt
 $(X w3k48) timeout 300 python -m pytest tests/test_gpu_wino2d.py -x -q -m gpu -s -k "folded_gemm and case1" 2>&1 | grep "folded GEMM\|passed\|failed\|Error" >> $O/r06_b16_tests.txt
-B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1"
+B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1 --full"
 F=$O/r06_b16_bench_ab.txt
 run() { echo "### $*" >> $F; timeout 600 "$@" 2>>$O/r06_b16_err.txt | python -c "
 import sys, json

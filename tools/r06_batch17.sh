@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.."
 O=gpurun_out; mkdir -p $O
 X() { if [ "$1" = product ]; then echo env; else echo "env AID_EXPERIMENT=1 AID_LIB_PATH=tools/exp/libaid_$1.so"; fi; }
 for l in u3a u3c; do echo "=== $l"; $(X $l) timeout 600 python -m pytest tests/test_gpu_wino2d.py -x -q -m gpu 2>&1 | grep -v amdgpu | tail -2; done > $O/r06_b17_tests.txt
-B="python bench.py --steps 4 --warmup 2 --no-cpu-baseline --roof-steps 1"
+B="python bench.py --steps 4 --warmup 2 --no-cpu-baseline --roof-steps 1 --full"
 F=$O/r06_b17_bench_ab.txt
 run() { echo "### $*" >> $F; timeout 600 "$@" 2>>$O/r06_b17_err.txt | python -c "
 import sys, json

@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.."
 O=gpurun_out; mkdir -p $O
 X() { if [ "$1" = product ]; then echo env; else echo "env AID_EXPERIMENT=1 AID_LIB_PATH=tools/exp/libaid_$1.so"; fi; }
 for l in c11k32b; do echo "=== $l"; $(X $l) timeout 900 python -m pytest tests/test_gpu_kernels.py -x -q -m gpu 2>&1 | grep -v amdgpu | tail -2; done > $O/r06_b18_tests.txt
-B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1"
+B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1 --full"
 F=$O/r06_b18_bench_ab.txt
 run() { echo "### $*" >> $F; timeout 600 "$@" 2>>$O/r06_b18_err.txt | python -c "
 import sys, json

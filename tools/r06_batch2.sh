@@ -2,7 +2,7 @@
 # round 6, GPU batch 2: CU-masked sub-batch streams WITHOUT events (cu_split) + the type-lane partition again with re-used events
 cd "$(dirname "$0")/.."
 O=gpurun_out; mkdir -p $O
-B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1"
+B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1 --full"
 F=$O/r06_cu_split_ab.txt
 run() { echo "### $*" >> $F; timeout 600 $B "$@" 2>>$O/r06_cu_split_err.txt | python -c "
 import sys, json

@@ -8,7 +8,7 @@ python -m pytest tests/test_gpu_wino2d.py -x -q -m gpu 2>&1 | tail -3 > $O/r06_b
 timeout 300 python tools/cu_mask_probe.py --launch-cost 2>&1 | grep -v amdgpu > $O/r06_cu_mask_launch_cost.txt
 timeout 600 python tools/plan_trace.py 8 2>&1 | grep -v amdgpu > $O/r06_trace_b8.txt
 timeout 600 python tools/plan_trace.py 1 2>&1 | grep -v amdgpu > $O/r06_trace_b1.txt
-B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1"
+B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1 --full"
 F=$O/r06_tf8_bench_ab2.txt
 run() { echo "### $*" >> $F; timeout 600 $B "$@" 2>>$O/r06_b4_err.txt | python -c "
 import sys, json

@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.."
 O=gpurun_out; mkdir -p $O
 python -m pytest tests/test_gpu_wino2d.py tests/test_gpu_vjp.py tests/test_gpu_configs.py tests/test_gpu_network.py -x -q -m gpu -s -k "wino2d or norm_bwd or fused_passes or full_size_guided or eight_free_running or unet_full_cfgA_vs or guided_whole_trajectory or network_vjp" 2>&1 | grep -v "^configs\[1\] B=8 item\|amdgpu" | tail -25 > $O/r06_b5_tests.txt
 timeout 300 python tools/cu_mask_probe.py --launch-cost 2>&1 | grep -v amdgpu > $O/r06_cu_mask_launch_cost.txt
-B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1"
+B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1 --full"
 F=$O/r06_b5_bench_ab.txt
 run() { echo "### $*" >> $F; timeout 600 $B "$@" 2>>$O/r06_b5_err.txt | python -c "
 import sys, json

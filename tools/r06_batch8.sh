@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.."
 O=gpurun_out; mkdir -p $O
 python -m pytest tests/test_gpu_wino2d.py -x -q -m gpu 2>&1 | tail -4 | grep -v amdgpu > $O/r06_b8_tests.txt
 for b in 4 1; do PROBE_ONLY="L1 C96" PROBE_TF=8 timeout 300 python tools/w2d_probe.py layer $b; PROBE_ONLY="L2 C96" PROBE_TF=8 timeout 300 python tools/w2d_probe.py layer $b; PROBE_ONLY="L3d C96" PROBE_TF=8 timeout 300 python tools/w2d_probe.py layer $b; done 2>&1 | grep -v amdgpu > $O/r06_w2d_c96_tf8_probe.txt
-B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1"
+B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1 --full"
 F=$O/r06_b8_bench_ab.txt
 run() { echo "### $*" >> $F; timeout 600 $B "$@" 2>>$O/r06_b8_err.txt | python -c "
 import sys, json

@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.."
 O=gpurun_out; mkdir -p $O
 python -m pytest tests/test_gpu_wino2d.py tests/test_gpu_vjp.py tests/test_gpu_configs.py tests/test_gpu_network.py -x -q -m gpu -s 2>&1 | grep -v "^configs\[1\] B=8 item\|amdgpu" | tail -25 > $O/r06_b9_tests.txt
 for b in 4 1; do for l in "L1 C96" "L2 C96" "L3d C96" "L3 C128" "L5 C256"; do PROBE_ONLY="$l" PROBE_TF=8 timeout 300 python tools/w2d_probe.py layer $b | grep -v "^layer"; done; done 2>&1 | grep -v amdgpu > $O/r06_w2d_c96_tf8_probe2.txt
-B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1"
+B="python bench.py --steps 6 --warmup 2 --no-cpu-baseline --roof-steps 1 --full"
 F=$O/r06_b9_bench_ab.txt
 run() { echo "### $*" >> $F; timeout 600 $B "$@" 2>>$O/r06_b9_err.txt | python -c "
 import sys, json
