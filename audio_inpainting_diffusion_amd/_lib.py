@@ -1,4 +1,4 @@
-"""ctypes binding of libaid_hip.so (the C ABI in include/aid_kernels.h).
+"""ctypes binding of libaid_hip.so (the C ABI in include/aid_kernels.h and include/aid_degrade.h).
 
 There is deliberately NO fallback: if the shared library is missing or a launcher returns an error code,
 ``AidError`` is raised.  Tensors are passed as raw device pointers + element strides; the stream is torch's
@@ -253,6 +253,30 @@ class SumsqParams(C.Structure):
 
 AID_SUMSQ_BLOCKS = 512
 
+
+# ---- include/aid_degrade.h (restoration degradations; a header and export list of their own) ----
+class FirParams(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("out", C.c_void_p), ("h", C.c_void_p), ("add1", C.c_void_p), ("add2", C.c_void_p), ("c0", C.c_float),
+                ("B", C.c_int), ("K", C.c_int), ("stride", C.c_int), ("pad_left", C.c_int), ("adjoint", C.c_int),
+                ("L", C.c_int64), ("L_out", C.c_int64), ("x_ld", C.c_int64), ("out_ld", C.c_int64)]
+
+
+class IirParams(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("out", C.c_void_p), ("pre", C.c_void_p), ("coef", C.c_void_p), ("H", C.c_void_p),
+                ("z", C.c_void_p), ("state", C.c_void_p), ("add1", C.c_void_p), ("add2", C.c_void_p), ("c0", C.c_float),
+                ("B", C.c_int), ("N", C.c_int), ("C", C.c_int), ("clamp", C.c_int), ("adjoint", C.c_int),
+                ("L", C.c_int64), ("x_ld", C.c_int64), ("out_ld", C.c_int64)]
+
+
+class ClipParams(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("xref", C.c_void_p), ("out", C.c_void_p), ("add1", C.c_void_p), ("add2", C.c_void_p),
+                ("c0", C.c_float), ("clip", C.c_float), ("B", C.c_int), ("adjoint", C.c_int),
+                ("L", C.c_int64), ("x_ld", C.c_int64), ("out_ld", C.c_int64)]
+
+
+AID_DEGRADE_ABI_VERSION = 1
+DEGRADE_EXPORTS = ["aid_degrade_abi_version", "aid_fir", "aid_iir", "aid_clip"]
+
 EXPORTS = ["aid_abi_version", "aid_last_error", "aid_last_kernel", "aid_group_stats", "aid_conv2d", "aid_conv2d_pack_dims", "aid_conv2d_stat_partials", "aid_pack_conv_weight", "aid_wino_gy", "aid_conv2d_wgrad_tiles", "aid_resample",
            "aid_time_attention", "aid_embed", "aid_modulation", "aid_cqt_analysis", "aid_cqt_synthesis",
            "aid_cqt_gather", "aid_axpby", "aid_score_step", "aid_add2", "aid_group_dot", "aid_norm_bwd",
@@ -319,6 +343,14 @@ def lib():
                 getattr(L, name).restype = C.c_int
         if L.aid_abi_version() != 14:
             raise AidError("ABI version mismatch")
+        for name in DEGRADE_EXPORTS:
+            if not hasattr(L, name):
+                raise AidError(f"libaid_hip.so does not export {name}")
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
+            getattr(L, name).restype = C.c_int
+        L.aid_degrade_abi_version.argtypes = []
+        if L.aid_degrade_abi_version() != AID_DEGRADE_ABI_VERSION:
+            raise AidError("include/aid_degrade.h ABI version mismatch")
         _lib = L
     return _lib
 

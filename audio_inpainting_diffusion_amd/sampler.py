@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .degrade import Decimate, FIRFilter, HardClip, IIRFilter
 from .stft import SpectralMask
 
 
@@ -77,6 +78,14 @@ class LambdaDegradation:
     def project(self, x, y):
         raise AttributeError("proj_convex_set is undefined for predict_resample (the reference defines it in predict_inpainting / "
                              "predict_spectrogram_inpainting only): set tester.data_consistency.use = False")
+
+
+def as_operator(degradation):
+    """An operator object (anything with ``apply`` and ``adjoint``: stft.SpectralMask, degrade.FIRFilter, ...) is installed as it is;
+    any other callable goes through LambdaDegradation."""
+    if hasattr(degradation, "apply") and hasattr(degradation, "adjoint"):
+        return degradation
+    return LambdaDegradation(degradation)
 
 
 class Sampler:
@@ -316,7 +325,8 @@ class Sampler:
 
     def predict_resample(self, y, shape, degradation):
         """y[B, ...] = observations, shape = (B, L) of the signal, degradation = torch callable x[B, L] -> y-shaped tensor   (:164-173): reconstruction
-        guidance through an arbitrary degradation (the reference's generic entry point; its inpainting methods are special cases of it)."""
+        guidance through an arbitrary degradation (the reference's generic entry point; its inpainting methods are special cases of it).
+        An operator object with ``apply`` / ``adjoint`` (degrade.py, stft.SpectralMask) is used directly, without torch autograd."""
         if y.dim() == 3 and self.args.tester.posterior_sampling.norm != "smoothl1" and type(self.model).__name__ != "GenericModelAdapter":
             # (:67-70: torch.linalg.norm(y - den, dim=(1, 2), ord=norm) over 3-D observations is the INDUCED matrix norm -- ord = 2 the largest singular
             #  value, ord = 1 the largest column sum -- not the element-wise norm aid_guidance_seed computes over the flattened item)
@@ -325,9 +335,42 @@ class Sampler:
                                 "flatten the observations to [B, N], or wrap the model in generic.GenericModelAdapter (torch autograd, reference semantics)")
         self.y = y.contiguous().float()
         self.mask = self.smask = None
-        self.spectral = LambdaDegradation(degradation)
+        self.spectral = as_operator(degradation)
         self.degradation = degradation
         return self.predict(tuple(shape), self.y.device)
+
+    def predict_conditional(self, y, degradation):
+        """(edm_sampler.py:157-164) predict_resample with the signal shape y.shape"""
+        return self.predict_resample(y, tuple(y.shape), degradation)
+
+    def predict_bwe(self, ylpf, filt, filt_type):
+        """Bandwidth extension (edm_sampler.py:266-300) through the native operators of degrade.py:
+        "firwin" / "firwin_hpf": taps [K], [1, K] or [1, 1, K] (conv1d padding="same");  "cheby1": (b, a) (lfilter, clamp=False);
+        "biquad": (b0, b1, b2, a0, a1, a2) (torchaudio's biquad, clamp=True);  "decimate": an integer factor, ylpf [B, ceil((L-1)/f)]
+        with L = args.exp.audio_len.  "resample" is not built."""
+        dev = ylpf.device
+        L = ylpf.shape[-1]
+        if filt_type in ("firwin", "firwin_hpf"):
+            op = FIRFilter(filt, L, device=dev)
+        elif filt_type == "cheby1":
+            b, a = filt
+            op = IIRFilter(b, a, L, clamp=False, device=dev)
+        elif filt_type == "biquad":
+            op = IIRFilter.biquad(*filt, audio_len=L, device=dev)
+        elif filt_type == "decimate":
+            op = Decimate(filt, self.args.exp.audio_len, device=dev)
+            return self.predict_resample(ylpf, (ylpf.shape[0], self.args.exp.audio_len), op)
+        elif filt_type == "resample":
+            raise _lib.AidError("predict_bwe: filt_type 'resample' is not built (it needs torchaudio's resampler and an adjoint of "
+                                "aid_resample_poly); use 'decimate' or pass a degradation lambda to predict_resample")
+        else:
+            raise NotImplementedError(f"predict_bwe: unknown filt_type {filt_type!r}")
+        return self.predict_conditional(ylpf, op)
+
+    def predict_declipping(self, y_clipped, clip_value):
+        """(SamplerDeclipping.predict_declipping, edm_sampler.py:370-385) guidance through hard clipping at +-clip_value; the reference
+        asserts data consistency off -- with tester.data_consistency.use the first projection raises."""
+        return self.predict_conditional(y_clipped, HardClip(clip_value))
 
     # ---- the remaining public methods of the reference class (its testers never call them; kept so that code written against
     # ---- testing.edm_sampler_inpainting.Sampler finds every name).  They run outside the sampling loop. ------------------------------
@@ -357,7 +400,7 @@ class Sampler:
     def get_score(self, x, y, t_i, degradation=None):
         """ONE evaluation of the score (x_hat - x) / t_i^2 exactly as the loop forms it (:115-153): unconditional for y None (DC/Nyquist projector
         only), reconstruction guidance for xi > 0, replacement + projection for xi == 0.  ``y`` / ``degradation`` other than the installed ones are
-        installed for this call (a callable degradation goes through LambdaDegradation).  With rid=True the guided branch returns the reference's
+        installed for this call (an operator object as it is, any other callable through LambdaDegradation).  With rid=True the guided branch returns the reference's
         5-tuple (score, denoised estimate, s * rec_grads, estimate after the guidance step, estimate after the projection; :106-108)."""
         t = torch.as_tensor(t_i, dtype=torch.float32).detach().reshape(()).cpu()
         x = x.detach().contiguous().float()
@@ -373,7 +416,7 @@ class Sampler:
                     self.y = y.contiguous().float()
                 if callable(degradation) and degradation != saved[4] and degradation is not saved[3]:      # (bound methods compare by ==)
                     self.mask = self.smask = None
-                    self.spectral, self.degradation = LambdaDegradation(degradation), degradation
+                    self.spectral, self.degradation = as_operator(degradation), degradation
             x_hat = self._denoise(x, t)
             keep, self.rid = self.rid, bool(self.rid and self.y is not None and self.xi > 0)
             try:

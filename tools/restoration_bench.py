@@ -1,0 +1,88 @@
+#!/usr/bin/env python
+"""Guided denoiser evaluations/s of the restoration entry points at the BASELINE.json configs[1] shape (B = 8, L = 184184,
+T = 36 schedule, xi = 0.25): one warm-up step, then --steps timed steps of each mode, alternated --rounds times.  Prints one
+JSON line.  Modes: predict_inpainting, predict_bwe firwin (K = 501), predict_bwe cheby1, predict_declipping, and
+predict_resample with the equivalent torch conv1d lambda (the generic single-stream path)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--cheby-order", type=int, default=8)
+    ap.add_argument("--cheby-fc", type=float, default=3000.0)
+    a = ap.parse_args()
+    import numpy as np
+    import scipy.signal
+    import torch
+    from audio_inpainting_diffusion_amd.config import make_args
+    from audio_inpainting_diffusion_amd.edm import EDM
+    from audio_inpainting_diffusion_amd.init import seeded_init_, seeded_normal
+    from audio_inpainting_diffusion_amd.masks import mask_from_args
+    from audio_inpainting_diffusion_amd.network import Unet_CQT_oct_with_attention
+    from audio_inpainting_diffusion_amd.sampler import Sampler
+    dev = torch.device("cuda", 0)
+    B, L = 8, 184184
+    args = make_args("maestro22k", audio_len=L, T=36, xi=0.25)
+    args.tester.data_consistency.use = False
+    net = seeded_init_(Unet_CQT_oct_with_attention(args, dev), 0)
+    net.prepare()
+    clean = torch.stack([torch.from_numpy(seeded_normal(7, g, L)) for g in range(B)]).float() * 0.063
+    taps = torch.from_numpy(scipy.signal.firwin(501, 4000, fs=22050).astype(np.float32)).view(1, 1, -1)
+    fir = lambda x: torch.nn.functional.conv1d(x.unsqueeze(1), taps.to(x.device), padding="same").squeeze(1)
+    ba = scipy.signal.cheby1(a.cheby_order, 0.05, a.cheby_fc, fs=22050)
+    mask = mask_from_args(args, generator=torch.Generator().manual_seed(99)).to(dev, torch.float32).reshape(1, L)   # as bench.py
+    y_fir = fir(clean).to(dev)
+    y_clip = clean.clamp(-0.05, 0.05).to(dev)
+    y_inp = (clean.to(dev) * mask)
+    smp = Sampler(model=net, diff_params=EDM(args), args=args)
+
+    def setup(mode):
+        from audio_inpainting_diffusion_amd.degrade import FIRFilter, HardClip, IIRFilter
+        smp.mask = smp.smask = None
+        if mode == "inpainting":
+            smp.setup_inpainting(y_inp, mask)
+            return
+        if mode == "bwe_firwin":
+            smp.y, smp.spectral = y_fir, FIRFilter(taps, L, device=dev)
+        elif mode == "bwe_cheby1":
+            op = IIRFilter(*ba, L, device=dev)
+            smp.y, smp.spectral = op.apply(clean.to(dev)), op
+        elif mode == "declipping":
+            smp.y, smp.spectral = y_clip, HardClip(0.05)
+        else:
+            from audio_inpainting_diffusion_amd.sampler import LambdaDegradation
+            smp.y, smp.spectral = y_fir, LambdaDegradation(fir)
+        smp.degradation = smp.spectral
+
+    modes = ["inpainting", "bwe_firwin", "bwe_cheby1", "declipping", "resample_lambda"]
+    rates = {m: [] for m in modes}
+    for _ in range(a.rounds):
+        for m in modes:
+            setup(m)
+            smp.seeds = list(range(B))
+            st = smp.begin((B, L), dev)
+            smp.step(st, 0)                                     # warm-up
+            torch.cuda.synchronize()
+            n0, t0 = smp.n_evals, time.perf_counter()
+            for i in range(1, 1 + a.steps):
+                smp.step(st, i)
+            torch.cuda.synchronize()
+            rates[m].append((smp.n_evals - n0) / (time.perf_counter() - t0))
+    best = {m: max(v) for m, v in rates.items()}
+    print(json.dumps({"metric": "guided denoiser evaluations/s", "shape": [B, L], "steps": a.steps, "rounds": a.rounds,
+                      "cheby1": {"order": a.cheby_order, "fc": a.cheby_fc, "fs": 22050}, "fir_taps": 501,
+                      "evals_per_s": {m: round(v, 2) for m, v in best.items()}, "all": {m: [round(x, 2) for x in v] for m, v in rates.items()},
+                      "vs_inpainting": {m: round(best[m] / best["inpainting"], 4) for m in modes}}))
+
+
+if __name__ == "__main__":
+    main()
