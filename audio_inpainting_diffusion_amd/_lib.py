@@ -1,4 +1,4 @@
-"""ctypes binding of libaid_hip.so (the C ABI in include/aid_kernels.h and include/aid_degrade.h).
+"""ctypes binding of libaid_hip.so (the C ABI in include/aid_kernels.h, include/aid_degrade.h and include/aid_phase.h).
 
 There is deliberately NO fallback: if the shared library is missing or a launcher returns an error code,
 ``AidError`` is raised.  Tensors are passed as raw device pointers + element strides; the stream is torch's
@@ -277,6 +277,22 @@ class ClipParams(C.Structure):
 AID_DEGRADE_ABI_VERSION = 1
 DEGRADE_EXPORTS = ["aid_degrade_abi_version", "aid_fir", "aid_iir", "aid_clip"]
 
+
+# ---- include/aid_phase.h (phase retrieval: STFT magnitude and the induced-matrix-norm seed; a header and export list of their own) ----
+class StftMagParams(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("g", C.c_void_p), ("out", C.c_void_p), ("frames", C.c_void_p), ("window", C.c_void_p), ("twiddle", C.c_void_p),
+                ("B", C.c_int), ("n_fft", C.c_int), ("hop", C.c_int), ("n_frames", C.c_int), ("adjoint", C.c_int),
+                ("L", C.c_int64), ("x_ld", C.c_int64), ("out_ld", C.c_int64)]
+
+
+class MatrixNormParams(C.Structure):
+    _fields_ = [("den", C.c_void_p), ("y", C.c_void_p), ("g", C.c_void_p), ("norm", C.c_void_p), ("r", C.c_void_p), ("diag", C.c_void_p),
+                ("B", C.c_int), ("F", C.c_int), ("T", C.c_int), ("ord", C.c_int), ("max_iter", C.c_int), ("tol", C.c_double)]
+
+
+AID_PHASE_ABI_VERSION = 1
+PHASE_EXPORTS = ["aid_phase_abi_version", "aid_stft_mag", "aid_matrix_norm_seed"]
+
 EXPORTS = ["aid_abi_version", "aid_last_error", "aid_last_kernel", "aid_group_stats", "aid_conv2d", "aid_conv2d_pack_dims", "aid_conv2d_stat_partials", "aid_pack_conv_weight", "aid_wino_gy", "aid_conv2d_wgrad_tiles", "aid_resample",
            "aid_time_attention", "aid_embed", "aid_modulation", "aid_cqt_analysis", "aid_cqt_synthesis",
            "aid_cqt_gather", "aid_axpby", "aid_score_step", "aid_add2", "aid_group_dot", "aid_norm_bwd",
@@ -351,6 +367,14 @@ def lib():
         L.aid_degrade_abi_version.argtypes = []
         if L.aid_degrade_abi_version() != AID_DEGRADE_ABI_VERSION:
             raise AidError("include/aid_degrade.h ABI version mismatch")
+        for name in PHASE_EXPORTS:
+            if not hasattr(L, name):
+                raise AidError(f"libaid_hip.so does not export {name}")
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
+            getattr(L, name).restype = C.c_int
+        L.aid_phase_abi_version.argtypes = []
+        if L.aid_phase_abi_version() != AID_PHASE_ABI_VERSION:
+            raise AidError("include/aid_phase.h ABI version mismatch")
         _lib = L
     return _lib
 

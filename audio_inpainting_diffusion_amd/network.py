@@ -1537,7 +1537,8 @@ class Unet_CQT_oct_with_attention(nn.Module):
         rec_grads = d/dx || y - A(x_hat) ||_2 (per item, edm_sampler_inpainting.py:60-81), computed with the
         hand-written input-VJP instead of torch.autograd.  A = time-domain mask (default) or any linear operator
         object with ``apply`` / ``adjoint`` (stft.SpectralMask).  norm_type: tester.posterior_sampling.norm -- 2, 1 or "smoothl1"
-        (beta = smoothl1_beta), all seeded analytically by aid_guidance_seed (:72-75).  cnoise .. cout: device [B] tensors or host floats.
+        (beta = smoothl1_beta), all seeded analytically by aid_guidance_seed (:72-75) -- or, for an operator that declares matrix_obs = (F, T)
+        (phase.STFTMagnitude), 2 / 1 as the induced matrix norm by aid_matrix_norm_seed (:67-70).  cnoise .. cout: device [B] tensors or host floats.
         Returns (x_hat, rec_grads, norm[B])."""
         nt = {2: 2, 1: 1, "smoothl1": 3, 3: 3}.get(norm_type)
         if nt is None:
@@ -1602,8 +1603,21 @@ class Unet_CQT_oct_with_attention(nn.Module):
                 raise _lib.AidError(f"denoise_guided: degradation(x_hat) {tuple(den.shape)} must be a contiguous float32 GPU tensor of the "
                                     f"observations' shape {tuple(y.shape)}")
             gd = g if Ld == L else torch.empty_like(den)
-            sp = _lib.GuidanceSeedParams(den.data_ptr(), y.data_ptr(), None, 0, gd.data_ptr(), norm.data_ptr(), B, Ld, nk[0], nk[1])
-            _lib.call("aid_guidance_seed", sp)
+            mobs = getattr(degradation, "matrix_obs", None)
+            if mobs is not None and nk[0] in (1, 2):         # 3-D observations: ord 1 / 2 is the induced matrix norm (:67-70), include/aid_phase.h
+                F, T = mobs
+                if tuple(den.shape) != (B, F, T):
+                    raise _lib.AidError(f"denoise_guided: degradation(x_hat) {tuple(den.shape)} does not match its matrix_obs {(B, F, T)}")
+                rbuf = torch.empty_like(den) if nk[0] == 2 else None
+                diag = torch.empty(B, 2, device=x.device, dtype=torch.float32) if getattr(degradation, "diagnostics", None) is not None else None
+                sp = _lib.MatrixNormParams(den.data_ptr(), y.data_ptr(), gd.data_ptr(), norm.data_ptr(), _lib.ptr(rbuf), _lib.ptr(diag),
+                                           B, F, T, nk[0], int(degradation.seed_max_iter), float(degradation.seed_tol))
+                _lib.call("aid_matrix_norm_seed", sp)
+                if diag is not None:
+                    degradation.diagnostics.append(diag)
+            else:
+                sp = _lib.GuidanceSeedParams(den.data_ptr(), y.data_ptr(), None, 0, gd.data_ptr(), norm.data_ptr(), B, Ld, nk[0], nk[1])
+                _lib.call("aid_guidance_seed", sp)
             g = degradation.adjoint(gd.view(den.shape))
             if not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and tuple(g.shape) == (B, L)):
                 raise _lib.AidError("denoise_guided: degradation.adjoint must return a contiguous float32 GPU tensor [B, L]")

@@ -24,6 +24,7 @@ import torch
 
 from . import _lib
 from .degrade import Decimate, FIRFilter, HardClip, IIRFilter
+from .phase import STFTMagnitude, observation_shape
 from .stft import SpectralMask
 
 
@@ -86,6 +87,17 @@ def as_operator(degradation):
     if hasattr(degradation, "apply") and hasattr(degradation, "adjoint"):
         return degradation
     return LambdaDegradation(degradation)
+
+
+def phase_retrieval_sizes(args):
+    """(win_size, hop_size) of phase retrieval: args.inference.phase_retrieval (where the reference reads them, edm_sampler.py:326-327)
+    when the config has it, else args.tester.phase_retrieval (where the shipped conf/tester yaml puts them)."""
+    node = getattr(getattr(args, "inference", None), "phase_retrieval", None)
+    if node is None:
+        node = getattr(args.tester, "phase_retrieval", None)
+    if node is None:
+        raise _lib.AidError("predict_pr: no phase_retrieval config (args.inference.phase_retrieval or args.tester.phase_retrieval)")
+    return node.win_size, node.hop_size
 
 
 class Sampler:
@@ -326,8 +338,9 @@ class Sampler:
     def predict_resample(self, y, shape, degradation):
         """y[B, ...] = observations, shape = (B, L) of the signal, degradation = torch callable x[B, L] -> y-shaped tensor   (:164-173): reconstruction
         guidance through an arbitrary degradation (the reference's generic entry point; its inpainting methods are special cases of it).
-        An operator object with ``apply`` / ``adjoint`` (degrade.py, stft.SpectralMask) is used directly, without torch autograd."""
-        if y.dim() == 3 and self.args.tester.posterior_sampling.norm != "smoothl1" and type(self.model).__name__ != "GenericModelAdapter":
+        An operator object with ``apply`` / ``adjoint`` (degrade.py, stft.SpectralMask, phase.STFTMagnitude) is used directly, without torch autograd."""
+        if (y.dim() == 3 and self.args.tester.posterior_sampling.norm != "smoothl1" and type(self.model).__name__ != "GenericModelAdapter"
+                and getattr(degradation, "matrix_obs", None) is None):       # (operators that declare matrix_obs get the induced-norm seed, phase.py)
             # (:67-70: torch.linalg.norm(y - den, dim=(1, 2), ord=norm) over 3-D observations is the INDUCED matrix norm -- ord = 2 the largest singular
             #  value, ord = 1 the largest column sum -- not the element-wise norm aid_guidance_seed computes over the flattened item)
             raise _lib.AidError("predict_resample: norm = 2 / 1 over 3-D observations is the induced matrix norm (spectral / max column sum) in the reference "
@@ -371,6 +384,19 @@ class Sampler:
         """(SamplerDeclipping.predict_declipping, edm_sampler.py:370-385) guidance through hard clipping at +-clip_value; the reference
         asserts data consistency off -- with tester.data_consistency.use the first projection raises."""
         return self.predict_conditional(y_clipped, HardClip(clip_value))
+
+    def predict_pr(self, y):
+        """Phase retrieval (SamplerPhaseRetrieval.predict_pr, edm_sampler.py:308-335): y [B, F, T] = |STFT| of the signal (win_size zeros
+        appended, periodic Hamming window, center=False), signal shape (B, args.exp.audio_len), through phase.STFTMagnitude.  win_size /
+        hop_size from args.inference.phase_retrieval when present, else args.tester.phase_retrieval.  The reference asserts xi > 0."""
+        if not self.xi > 0:
+            raise _lib.AidError("predict_pr needs reconstruction guidance: tester.posterior_sampling.xi must be > 0 (the reference asserts xi > 0)")
+        win, hop = phase_retrieval_sizes(self.args)
+        L = int(self.args.exp.audio_len)
+        F, T = observation_shape(win, hop, L)
+        if y.dim() != 3 or tuple(y.shape[1:]) != (F, T):
+            raise _lib.AidError(f"predict_pr: y must be [B, {F}, {T}] (|STFT| with win_size {win}, hop_size {hop} of {L} samples), got {tuple(y.shape)}")
+        return self.predict_resample(y, (y.shape[0], L), STFTMagnitude(win, hop, L, device=y.device))
 
     # ---- the remaining public methods of the reference class (its testers never call them; kept so that code written against
     # ---- testing.edm_sampler_inpainting.Sampler finds every name).  They run outside the sampling loop. ------------------------------

@@ -13,7 +13,7 @@ OUT = os.path.join(PKG, "libaid_hip.so")
 
 def build(force: bool = False, verbose: bool = True) -> str:
     srcs = sorted(glob.glob(os.path.join(SRC, "*.hip")))
-    deps = srcs + glob.glob(os.path.join(SRC, "*.h")) + [os.path.join(ROOT, "include", "aid_kernels.h")]
+    deps = srcs + glob.glob(os.path.join(SRC, "*.h")) + sorted(glob.glob(os.path.join(ROOT, "include", "*.h")))
     if not force and os.path.exists(OUT) and all(os.path.getmtime(OUT) >= os.path.getmtime(d) for d in deps):
         return OUT
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

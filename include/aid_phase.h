@@ -1,0 +1,67 @@
+/*
+ * aid_phase.h -- C ABI of the phase-retrieval pieces of libaid_hip.so (gfx950): the STFT-magnitude operator of the
+ * reference's SamplerPhaseRetrieval (testing/edm_sampler.py:308-335) with its vector-Jacobian product, and the guidance
+ * seed of the induced matrix norms that torch.linalg.norm(y - A(x_hat), dim=(1, 2), ord=1 | 2) takes over 3-D
+ * observations (testing/edm_sampler_inpainting.py:67-75).
+ *
+ * Same boundary contract as aid_kernels.h: raw device pointers, sizes and row strides in ELEMENTS, a hipStream_t
+ * passed as void*, 0 or a negative AID_E_* code, no allocation, no synchronisation.
+ */
+#ifndef AID_PHASE_H
+#define AID_PHASE_H
+
+#include <stdint.h>
+#include "aid_kernels.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define AID_PHASE_ABI_VERSION 1
+int aid_phase_abi_version(void);
+
+/* ---------------------------------------------------------------------------------------------------
+ * aid_stft_mag -- |STFT| of the zero-extended signal, center=False, one-sided, unnormalised:
+ *   X[b, k, t] = sum_{j<N} window[j] * x[b, t*hop + j] * exp(-2 pi i j k / N),  x = 0 at and past L
+ *   (torch.stft(cat(x, zeros(N)), N, hop, window, center=False): T = 1 + L / hop frames, F = N/2 + 1 bins)
+ *   adjoint = 0:  out[b, k, t] = |X[b, k, t]|                        x [B, L] (row stride x_ld) -> out [B, F, T] contiguous
+ *   adjoint = 1:  the VJP at x (the x_hat of the matching forward; X is recomputed from it):
+ *                 out[b, q] = sum_t window[q - t*hop] * Re( IFFT_N(Z_t) )[q - t*hop],  q < L   (IFFT unnormalised)
+ *                 Z_t[k] = g[b, k, t] * X[b, k, t] / |X[b, k, t]| for k <= N/2 (0 where |X| = 0), Z_t[k] = 0 above
+ *                 g [B, F, T] contiguous -> out [B, L] (row stride out_ld); frames [B, T, N] contiguous is scratch
+ *                 (written by the frame pass, read by the overlap-add gather; no atomics, deterministic).
+ *   window [N], twiddle [N/2] complex (cos, -sin)(2 pi m / N) as float2.
+ *   N = n_fft a power of two in [16, 8192]; 0 < hop <= N; n_frames = 1 + L / hop.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct {
+    const float* x; const float* g; float* out; float* frames;
+    const float* window; const float* twiddle;
+    int B, n_fft, hop, n_frames, adjoint;
+    int64_t L, x_ld, out_ld;
+} aid_stft_mag_params;
+int aid_stft_mag(const aid_stft_mag_params* p, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * aid_matrix_norm_seed -- induced norm of R_b = y_b - den_b, viewed as an F x T matrix per item, and its seed
+ *   g = d norm / d den = -d norm / d R (the sign convention of aid_guidance_seed).  One workgroup per item; the result
+ *   of item b does not depend on the other items.  den, y, g are [B, F, T] contiguous.
+ *   ord 1:  norm = max_t sum_f |R[f, t]| (fp64 sums); g = -sign(R) on the arg-max column, divided by the number of
+ *           columns that tie exactly (torch.amax's backward).
+ *   ord 2:  norm = sigma_1(R); g = -u_1 v_1^T.  Power iteration on R^T R in fp64 from v_0 = the column 2-norms of R
+ *           (data-derived, no state across calls), stopped when ||R^T u - sigma v|| / sigma <= tol (u = R v / ||R v||,
+ *           sigma = ||R v||) or after max_iter iterations; the triplet of the last iteration is used either way.
+ *           r [B, F, T] fp32 scratch receives R.  diag [B, 2] (optional): iterations run, final residual.
+ *   (F + T) * 8 + 256 bytes of LDS per workgroup: F + T <= 8160.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct {
+    const float* den; const float* y; float* g; float* norm;
+    float* r; float* diag;
+    int B, F, T, ord, max_iter;
+    double tol;
+} aid_matrix_norm_params;
+int aid_matrix_norm_seed(const aid_matrix_norm_params* p, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* AID_PHASE_H */

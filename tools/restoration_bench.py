@@ -1,8 +1,9 @@
 #!/usr/bin/env python
 """Guided denoiser evaluations/s of the restoration entry points at the BASELINE.json configs[1] shape (B = 8, L = 184184,
 T = 36 schedule, xi = 0.25): one warm-up step, then --steps timed steps of each mode, alternated --rounds times.  Prints one
-JSON line.  Modes: predict_inpainting, predict_bwe firwin (K = 501), predict_bwe cheby1, predict_declipping, and
-predict_resample with the equivalent torch conv1d lambda (the generic single-stream path)."""
+JSON line.  Modes: predict_inpainting, predict_bwe firwin (K = 501), predict_bwe cheby1, predict_declipping, predict_resample with the
+equivalent torch conv1d lambda (the generic single-stream path), and phase retrieval (predict_pr: |STFT| with N = 1024, hop = 256;
+norm 2 is the spectral norm there, seeded by power iteration -- its per-item iteration counts are reported)."""
 import argparse
 import json
 import os
@@ -19,6 +20,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--cheby-order", type=int, default=8)
     ap.add_argument("--cheby-fc", type=float, default=3000.0)
+    ap.add_argument("--modes", default="", help="comma-separated subset of the modes (default: all)")
+    ap.add_argument("--pr-trajectory", action="store_true", help="after timing, run phase retrieval over the whole schedule once and "
+                    "report the power-iteration counts of the spectral-norm seed per evaluation (from sigma_max down to the last step)")
     a = ap.parse_args()
     import numpy as np
     import scipy.signal
@@ -43,6 +47,10 @@ def main():
     y_fir = fir(clean).to(dev)
     y_clip = clean.clamp(-0.05, 0.05).to(dev)
     y_inp = (clean.to(dev) * mask)
+    from audio_inpainting_diffusion_amd.phase import STFTMagnitude
+    pr_op = STFTMagnitude(1024, 256, L, device=dev)
+    y_pr = pr_op.apply(clean.to(dev))
+    pr_op.diagnostics = []
     smp = Sampler(model=net, diff_params=EDM(args), args=args)
 
     def setup(mode):
@@ -58,12 +66,16 @@ def main():
             smp.y, smp.spectral = op.apply(clean.to(dev)), op
         elif mode == "declipping":
             smp.y, smp.spectral = y_clip, HardClip(0.05)
+        elif mode == "phase_retrieval":
+            smp.y, smp.spectral = y_pr, pr_op
         else:
             from audio_inpainting_diffusion_amd.sampler import LambdaDegradation
             smp.y, smp.spectral = y_fir, LambdaDegradation(fir)
         smp.degradation = smp.spectral
 
-    modes = ["inpainting", "bwe_firwin", "bwe_cheby1", "declipping", "resample_lambda"]
+    modes = ["inpainting", "bwe_firwin", "bwe_cheby1", "declipping", "resample_lambda", "phase_retrieval"]
+    if a.modes:
+        modes = [m for m in modes if m in a.modes.split(",")]
     rates = {m: [] for m in modes}
     for _ in range(a.rounds):
         for m in modes:
@@ -78,10 +90,27 @@ def main():
             torch.cuda.synchronize()
             rates[m].append((smp.n_evals - n0) / (time.perf_counter() - t0))
     best = {m: max(v) for m, v in rates.items()}
+    diag = torch.cat([d.cpu() for d in pr_op.diagnostics]) if pr_op.diagnostics else torch.zeros(0, 2)
+    it = diag[:, 0]
+    seed = {"norm": args.tester.posterior_sampling.norm, "tol": pr_op.seed_tol, "max_iter": pr_op.seed_max_iter, "item_evaluations": int(it.numel()),
+            "iterations_min": int(it.min()) if it.numel() else None, "iterations_median": float(it.median()) if it.numel() else None,
+            "iterations_max": int(it.max()) if it.numel() else None, "residual_max": float(diag[:, 1].max()) if it.numel() else None}
+    if a.pr_trajectory:
+        setup("phase_retrieval")
+        pr_op.diagnostics = []
+        smp.seeds = list(range(B))
+        out = smp.predict(tuple((B, L)), dev)
+        per_eval = [d.cpu() for d in pr_op.diagnostics]
+        it_all = torch.cat([d[:, 0] for d in per_eval])
+        seed["trajectory"] = {"steps": args.tester.T, "finite": bool(torch.isfinite(out).all()), "item_evaluations": int(it_all.numel()),
+                              "iterations_min": int(it_all.min()), "iterations_median": float(it_all.median()), "iterations_max": int(it_all.max()),
+                              "residual_max": float(torch.cat([d[:, 1] for d in per_eval]).max()),
+                              "iterations_max_per_launch": [int(d[:, 0].max()) for d in per_eval]}
     print(json.dumps({"metric": "guided denoiser evaluations/s", "shape": [B, L], "steps": a.steps, "rounds": a.rounds,
                       "cheby1": {"order": a.cheby_order, "fc": a.cheby_fc, "fs": 22050}, "fir_taps": 501,
+                      "phase_retrieval": {"win_size": 1024, "hop_size": 256, "seed": seed},
                       "evals_per_s": {m: round(v, 2) for m, v in best.items()}, "all": {m: [round(x, 2) for x in v] for m, v in rates.items()},
-                      "vs_inpainting": {m: round(best[m] / best["inpainting"], 4) for m in modes}}))
+                      "vs_inpainting": {m: round(best[m] / best["inpainting"], 4) for m in modes} if "inpainting" in best else None}))
 
 
 if __name__ == "__main__":
