@@ -1,4 +1,4 @@
-"""ctypes binding of libaid_hip.so (the C ABI in include/aid_kernels.h, include/aid_degrade.h and include/aid_phase.h).
+"""ctypes binding of libaid_hip.so (the C ABI in include/aid_kernels.h, include/aid_degrade.h, include/aid_phase.h and include/aid_autoregressive.h).
 
 There is deliberately NO fallback: if the shared library is missing or a launcher returns an error code,
 ``AidError`` is raised.  Tensors are passed as raw device pointers + element strides; the stream is torch's
@@ -293,6 +293,15 @@ class MatrixNormParams(C.Structure):
 AID_PHASE_ABI_VERSION = 1
 PHASE_EXPORTS = ["aid_phase_abi_version", "aid_stft_mag", "aid_matrix_norm_seed"]
 
+# ---- include/aid_autoregressive.h (the window carry of autoregressive generation; a header and export list of their own) ----
+class ArCarryParams(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("out", C.c_void_p), ("B", C.c_int), ("first", C.c_int),
+                ("L", C.c_int64), ("end", C.c_int64), ("off", C.c_int64), ("out_ld", C.c_int64)]
+
+
+AID_AR_ABI_VERSION = 1
+AR_EXPORTS = ["aid_ar_abi_version", "aid_ar_carry"]
+
 EXPORTS = ["aid_abi_version", "aid_last_error", "aid_last_kernel", "aid_group_stats", "aid_conv2d", "aid_conv2d_pack_dims", "aid_conv2d_stat_partials", "aid_pack_conv_weight", "aid_wino_gy", "aid_conv2d_wgrad_tiles", "aid_resample",
            "aid_time_attention", "aid_embed", "aid_modulation", "aid_cqt_analysis", "aid_cqt_synthesis",
            "aid_cqt_gather", "aid_axpby", "aid_score_step", "aid_add2", "aid_group_dot", "aid_norm_bwd",
@@ -375,6 +384,14 @@ def lib():
         L.aid_phase_abi_version.argtypes = []
         if L.aid_phase_abi_version() != AID_PHASE_ABI_VERSION:
             raise AidError("include/aid_phase.h ABI version mismatch")
+        for name in AR_EXPORTS:
+            if not hasattr(L, name):
+                raise AidError(f"libaid_hip.so does not export {name}")
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
+            getattr(L, name).restype = C.c_int
+        L.aid_ar_abi_version.argtypes = []
+        if L.aid_ar_abi_version() != AID_AR_ABI_VERSION:
+            raise AidError("include/aid_autoregressive.h ABI version mismatch")
         _lib = L
     return _lib
 

@@ -65,7 +65,9 @@ TESTER_LONG = dict(
                                 time_mask_length=2000, time_start_idx="None", min_masked_freq=300, max_masked_freq=2000),
     inpainting=dict(mask_mode="long", long=dict(gap_length=1500, start_gap_idx="None"),
                     short=dict(num_gaps=4, gap_length=25, start_gap_idx="None")),
-    phase_retrieval=dict(win_size=1024, hop_size=256))      # conf/tester/edm_2ndorder_stochastic.yaml:68-70
+    phase_retrieval=dict(win_size=1024, hop_size=256),      # conf/tester/edm_2ndorder_stochastic.yaml:68-70
+    autoregressive=dict(overlap=0.25, num_samples=4),       # the autoregressive / comp_sens nodes of both shipped tester yamls
+    comp_sens=dict(percentage=5))
 
 # conf/diff_params/edm.yaml
 DIFF_PARAMS = dict(callable="audio_inpainting_diffusion_amd.edm.EDM", sigma_data=0.063, sigma_min=1e-5,

@@ -103,6 +103,42 @@ def inpaint_long(sampler, files: Sequence[torch.Tensor], gap_ms: float, sample_r
     return out
 
 
+def generate_long(sampler, n_items: int, n_windows: int, seeds: Optional[Sequence[int]] = None, max_batch: int = 8,
+                  device="cuda") -> torch.Tensor:
+    """Generate ``n_items`` independent pieces of ``n_windows`` overlapping windows each (Sampler.predict_autoregressive; the counterpart of
+    inpaint_long for producing audio longer than one model segment) -> [n_items, L + (n_windows - 1) * (L - end)] on ``device``.
+    The items run in sub-batches of at most ``max_batch``; with an active process group every rank generates dist.shard_range of them and
+    one dist.gather_outputs collects the result, as the inpainting path shards segments.  ``seeds``: one RNG seed per item (item i's piece
+    then depends on seeds[i] alone, not on the grouping); None: dist.item_seeds(0, ...) under a process group, else the global generator."""
+    from . import dist as D
+    if n_items < 1 or max_batch < 1:
+        raise ValueError("generate_long: n_items and max_batch must be >= 1")
+    if seeds is not None and len(seeds) != n_items:
+        raise ValueError(f"generate_long: {len(seeds)} seeds for {n_items} items")
+    active = D._active()
+    rank, world = (torch.distributed.get_rank(), torch.distributed.get_world_size()) if active else (0, 1)
+    lo, hi = D.shard_range(n_items, rank, world)
+    if seeds is None and active:
+        seeds = D.item_seeds(0, 0, n_items)
+    L = int(sampler.args.exp.audio_len)
+    keep, parts = sampler.seeds, []
+    try:
+        for b0 in range(lo, hi, max_batch):
+            b1 = min(hi, b0 + max_batch)
+            sampler.seeds = None if seeds is None else [int(s) for s in seeds[b0:b1]]
+            parts.append(sampler.predict_autoregressive((b1 - b0, L), n_windows, device))
+    finally:
+        sampler.seeds = keep
+    if len(parts) == 1:
+        local = parts[0]
+    elif parts:
+        local = torch.cat(parts, dim=0)
+    else:                                                            # (a rank without items still takes part in the collective)
+        from .sampler import autoregressive_length, autoregressive_overlap
+        local = torch.zeros((0, autoregressive_length(L, int(autoregressive_overlap(sampler.args) * L), n_windows)), device=device)
+    return D.gather_outputs(local, n_items)
+
+
 # ---- waveform pre-/post-processing of the tester --------------------------------------------------------------------------------
 def _sinc_kernel(orig: int, new: int, lowpass_filter_width: int = 6, rolloff: float = 0.99):
     """Hann-windowed sinc per output phase, [new, 2*width + orig] float64 -- torchaudio's default resampling kernel."""

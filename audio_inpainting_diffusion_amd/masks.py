@@ -24,6 +24,19 @@ def short_gaps_mask(audio_len: int, sample_rate: float, gap_ms: float, num_gaps:
     return mask
 
 
+def compsens_mask(audio_len: int, percentage: float, generator=None) -> torch.Tensor:
+    """Compressed-sensing mask [1, L]: ones at ``round(percentage / 100 * audio_len)`` positions drawn without replacement
+    (the first entries of ``torch.randperm(audio_len, generator=generator)``), zeros elsewhere.  This definition is the
+    project's own: the reference tree has ``SamplerCompSens.predict_compsens(y_masked, mask)`` and the setting
+    ``comp_sens: percentage`` but no builder of the mask for this mode."""
+    if not 0 <= percentage <= 100:
+        raise ValueError(f"compsens_mask: percentage must be in [0, 100], got {percentage}")
+    keep = int(round(percentage / 100 * audio_len))
+    mask = torch.zeros((1, audio_len))
+    mask[0, torch.randperm(audio_len, generator=generator)[:keep]] = 1
+    return mask
+
+
 def mask_from_args(args, generator=None) -> torch.Tensor:
     inp = args.tester.inpainting
     if inp.mask_mode == "long":

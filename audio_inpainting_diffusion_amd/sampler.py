@@ -100,6 +100,22 @@ def phase_retrieval_sizes(args):
     return node.win_size, node.hop_size
 
 
+def autoregressive_overlap(args):
+    """Overlap fraction of autoregressive generation: args.inference.autoregressive.overlap (where the reference reads it, edm_sampler.py:391)
+    when the config has it, else args.tester.autoregressive.overlap (where the shipped conf/tester yaml puts it)."""
+    node = getattr(getattr(args, "inference", None), "autoregressive", None)
+    if node is None:
+        node = getattr(args.tester, "autoregressive", None)
+    if node is None:
+        raise _lib.AidError("predict_autoregressive: no autoregressive config (args.inference.autoregressive or args.tester.autoregressive)")
+    return node.overlap
+
+
+def autoregressive_length(L: int, end: int, N: int) -> int:
+    """Samples produced by N windows of L samples that share ``end`` samples with their predecessor (hard concatenation, edm_sampler.py:416)."""
+    return L + (N - 1) * (L - end)
+
+
 class Sampler:
     def __init__(self, model, diff_params, args, rid=False):
         self.model = model
@@ -119,6 +135,8 @@ class Sampler:
         self.spectral = None
         self.y = self.mask = self.smask = self.degradation = None      # installed by predict_* / setup_*
         self.seeds: Optional[List[int]] = None      # per-item RNG seeds; None -> global torch CPU generator
+        self._gens = None                           # the per-item generators of the run in progress (begin)
+        self._keep_gens = False                     # predict_autoregressive: begin() keeps the generators the run already made
         self.trace = None                           # set to [] to record every projected x_hat (tests)
         self.trace_in = None                        # set to [] to record (x, t) handed to every denoiser evaluation (teacher-forced tests)
         self.n_evals = 0
@@ -247,7 +265,10 @@ class Sampler:
             raise _lib.AidError("the MI355X sampler runs on the GPU only (no CPU fallback)")
         self._check_model()
         dp = self.diff_params
-        self._gens = None if self.seeds is None else [torch.Generator().manual_seed(int(s)) for s in self.seeds]
+        if self.seeds is None:
+            self._gens = None
+        elif not (self._keep_gens and self._gens is not None):   # (an autoregressive run carries ONE generator per item across its windows)
+            self._gens = [torch.Generator().manual_seed(int(s)) for s in self.seeds]
         t = dp.create_schedule(self.nb_steps)                 # host, float32
         gamma = dp.get_gamma(t)
         x = self._draw_to(shape, t[0], device)                # prior (edm.py:94)
@@ -397,6 +418,72 @@ class Sampler:
         if y.dim() != 3 or tuple(y.shape[1:]) != (F, T):
             raise _lib.AidError(f"predict_pr: y must be [B, {F}, {T}] (|STFT| with win_size {win}, hop_size {hop} of {L} samples), got {tuple(y.shape)}")
         return self.predict_resample(y, (y.shape[0], L), STFTMagnitude(win, hop, L, device=y.device))
+
+    def predict_compsens(self, y_masked, mask):
+        """Compressed sensing (SamplerCompSens.predict_compsens, edm_sampler.py:337-357): reconstruction from the few samples a mask keeps
+        (masks.compsens_mask).  The operator is inpainting's time-domain mask; the contract is guidance only -- the reference asserts
+        xi > 0 and data consistency off (:341-342) -- and is checked before anything is installed."""
+        if not self.xi > 0:
+            raise _lib.AidError("predict_compsens needs reconstruction guidance: tester.posterior_sampling.xi must be > 0 (the reference asserts xi > 0)")
+        if self.data_consistency or self.data_consistency_end:
+            raise _lib.AidError("predict_compsens runs without data consistency (the reference asserts data_consistency == False): "
+                                "set tester.data_consistency.use = False")
+        return self.predict_inpainting(y_masked, mask)
+
+    def ar_carry(self, x, end, y, out, off, first):
+        """One aid_ar_carry launch on the current stream: y[B, L] (or None) := the last ``end`` samples of window x[B, L], then zeros;
+        out[:, off:off + L - skip] := x[:, skip:], skip = 0 for the first window, ``end`` after it (include/aid_autoregressive.h)."""
+        B, L = x.shape
+        for t in (x, out) + (() if y is None else (y,)):
+            _lib._req(t)
+        if not (x.is_contiguous() and out.dim() == 2 and out.stride(1) == 1 and out.shape[0] == B and (y is None or (y.is_contiguous() and y.shape == x.shape))):
+            raise _lib.AidError("ar_carry: x / y contiguous [B, L], out [B, >= off + L - skip] with contiguous rows")
+        if off + L - (0 if first else end) > out.shape[1]:
+            raise _lib.AidError("ar_carry: the appended part does not fit into out")
+        _lib.call("aid_ar_carry", _lib.ArCarryParams(x.data_ptr(), _lib.ptr(y), out.data_ptr(), B, int(bool(first)), L, int(end), int(off), out.stride(0)))
+
+    def predict_autoregressive(self, shape, N, device):
+        """Autoregressive generation (SamplerAutoregressive.predict_autoregressive, edm_sampler.py:386-418): a piece of N windows, longer than one
+        model segment.  Window 0 is sampled unconditionally; every later window is inpainted (as predict_inpainting does it: guidance, and the
+        projection tester.data_consistency configures) with its first end = int(overlap * L) samples observed -- the tail of the window before it.
+        shape = (B, L) with L = args.exp.audio_len -> [B, L + (N - 1) * (L - end)] on ``device`` (hard concatenation, as the reference).
+        The B pieces advance together; between two windows ONE aid_ar_carry launch writes the next observations and appends to the result, which
+        never leaves the GPU.  RNG: seeds None -> the global CPU generator in the reference's order (prior, churn draws, next prior, ...);
+        seeds [...] -> item b owns one generator for the WHOLE piece, so it equals the B = 1 run with seeds [seeds[b]]."""
+        B, L = (int(v) for v in shape)
+        N = int(N)
+        if self.rid:
+            raise _lib.AidError("predict_autoregressive returns the piece only: rid must be False (the reference asserts rid == False)")
+        if N < 1:
+            raise _lib.AidError(f"predict_autoregressive: N must be >= 1, got {N}")
+        if L != int(self.args.exp.audio_len):
+            raise _lib.AidError(f"predict_autoregressive: shape[-1] = {L} must equal args.exp.audio_len = {self.args.exp.audio_len} "
+                                "(the reference builds the mask with audio_len and indexes it with shape[-1])")
+        end = int(autoregressive_overlap(self.args) * L)
+        if end < 1 or end >= L:
+            raise _lib.AidError(f"predict_autoregressive: int(overlap * L) = {end} must lie in [1, L - 1]")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise _lib.AidError("the MI355X sampler runs on the GPU only (no CPU fallback)")
+        self._check_model()
+        if N == 1:
+            return self.predict_unconditional((B, L), device)
+        step = L - end
+        out = torch.empty((B, autoregressive_length(L, end, N)), dtype=torch.float32, device=device)
+        y = torch.empty((B, L), dtype=torch.float32, device=device)
+        mask = torch.ones((1, L))
+        mask[:, end:] = 0
+        self._gens, self._keep_gens = None, True
+        try:
+            x = self.predict_unconditional((B, L), device)
+            self.ar_carry(x, end, y, out, 0, True)
+            self.setup_inpainting(y, mask)                    # once: mask and smoothed mask do not change; y is refilled in place by the carry
+            for w in range(1, N):
+                x = self.predict((B, L), device)
+                self.ar_carry(x, end, y if w < N - 1 else None, out, L + (w - 1) * step, False)
+        finally:
+            self._keep_gens = False
+        return out
 
     # ---- the remaining public methods of the reference class (its testers never call them; kept so that code written against
     # ---- testing.edm_sampler_inpainting.Sampler finds every name).  They run outside the sampling loop. ------------------------------
