@@ -1,0 +1,135 @@
+// Window gather / scatter of whole-recording restoration (include/aid_restore.h): one pass of the restoration gathers the observations
+// and masks of all its windows into one batch and, after the sampler ran, writes back the samples every window owns.  Pure streaming
+// copies: J * L floats of y and of m written per gather, as many read; at most J * L floats moved per scatter.
+//
+//   grid (tiles, J): block row j handles job j.  A row is written with float4 stores over the 16-byte-aligned body of the DESTINATION
+//   and scalar stores over its head (< 4 elements) and tail; a source is read as float4 where it is aligned at the same element and
+//   as four scalars otherwise (window starts, owned ranges and row strides are in general not multiples of 4).  A float4 of the
+//   gather that straddles the end of the leading observed part, the start of the trailing one or sample N goes element by element.
+//   The job table is device memory the launcher cannot inspect: every access is bounded here (r in [0, R), 0 <= s < N, q < N).
+#include "aid_common.h"
+#include "aid_restore.h"
+
+#define RS_THREADS 256
+
+struct rs_job { int64_t r, s, head, tail, lo, hi; bool ok; };
+
+__device__ __forceinline__ int64_t rs_clamp(int64_t v, int64_t hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+
+__device__ __forceinline__ rs_job rs_load_job(const int64_t* __restrict__ jobs, int j, int R, int64_t L, int64_t N) {
+    const int64_t* t = jobs + (int64_t)j * AID_RESTORE_JOB_FIELDS;
+    rs_job b;
+    b.r = t[0]; b.s = t[1];
+    b.head = rs_clamp(t[2], L); b.tail = rs_clamp(t[3], L); b.lo = rs_clamp(t[4], L); b.hi = rs_clamp(t[5], L);
+    b.ok = b.r >= 0 && b.r < R && b.s >= 0 && b.s < N;
+    return b;
+}
+
+__device__ __forceinline__ float4 rs_ld4(const float* __restrict__ p, bool aligned) {
+    return aligned ? *reinterpret_cast<const float4*>(p) : make_float4(p[0], p[1], p[2], p[3]);
+}
+
+__device__ __forceinline__ void rs_st4(float* __restrict__ p, bool aligned, float4 v) {
+    if (aligned) *reinterpret_cast<float4*>(p) = v;
+    else { p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w; }
+}
+
+// elements before the first 16-byte boundary of p, at most n
+__device__ __forceinline__ int64_t rs_lead(const float* p, int64_t n) {
+    const int64_t a = (int64_t)(((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) >> 2);
+    return a > n ? n : a;
+}
+
+__device__ __forceinline__ bool rs_al16(const float* p) { return (((uintptr_t)p) & 15u) == 0; }
+
+__global__ __launch_bounds__(RS_THREADS) void window_gather_kernel(const aid_window_gather_params p) {
+    const int j = blockIdx.y;
+    const int64_t L = p.L;
+    const int64_t tid = (int64_t)blockIdx.x * RS_THREADS + threadIdx.x, nthreads = (int64_t)gridDim.x * RS_THREADS;
+    const rs_job b = rs_load_job(p.jobs, j, p.R, L, p.N);
+    // i < n_in  <=>  sample s + i exists; an invalid job gathers zeros with mask 0
+    const int64_t n_in = b.ok ? (p.N - b.s < L ? p.N - b.s : L) : 0;
+    const int64_t head = b.ok ? b.head : 0, tail0 = L - (b.ok ? b.tail : 0);          // observed from out: i < head or i >= tail0
+    const int64_t r = b.ok ? b.r : 0, s = b.ok ? b.s : 0;
+    const float* __restrict__ rec = p.rec + r * p.rec_ld + s;                         // (dereferenced at i < n_in only)
+    const float* __restrict__ out = p.out + r * p.out_ld + s;
+    const float* __restrict__ mask = p.mask + r * p.mask_ld + s;
+    float* __restrict__ y = p.y + (int64_t)j * L;
+    float* __restrict__ m = p.m + (int64_t)j * L;
+
+    auto elem = [&](int64_t i, float& yv, float& mv) {
+        const bool in = i < n_in, edge = i < head || i >= tail0;
+        mv = edge ? 1.f : (in ? mask[i] : 0.f);
+        yv = mv * (in ? (edge ? out[i] : rec[i]) : 0.f);
+    };
+
+    const int64_t lead = rs_lead(y, L);
+    const int64_t nvec = (L - lead) >> 2, body_end = lead + nvec * 4;
+    const bool m_al = rs_al16(m + lead), rec_al = rs_al16(rec + lead), out_al = rs_al16(out + lead), mask_al = rs_al16(mask + lead);
+    for (int64_t v = tid; v < nvec; v += nthreads) {
+        const int64_t i = lead + 4 * v;
+        float4 yv, mv;
+        if (i + 4 <= n_in && (i + 4 <= head || i >= tail0)) {                       // wholly observed from the result so far
+            mv = make_float4(1.f, 1.f, 1.f, 1.f);
+            yv = rs_ld4(out + i, out_al);
+        } else if (i + 4 <= n_in && i >= head && i + 4 <= tail0) {                   // wholly the recording under its mask
+            mv = rs_ld4(mask + i, mask_al);
+            const float4 x = rs_ld4(rec + i, rec_al);
+            yv = make_float4(mv.x * x.x, mv.y * x.y, mv.z * x.z, mv.w * x.w);
+        } else {
+            elem(i, yv.x, mv.x); elem(i + 1, yv.y, mv.y); elem(i + 2, yv.z, mv.z); elem(i + 3, yv.w, mv.w);
+        }
+        *reinterpret_cast<float4*>(y + i) = yv;
+        rs_st4(m + i, m_al, mv);
+    }
+    if (tid < lead) elem(tid, y[tid], m[tid]);
+    if (tid < L - body_end) { const int64_t i = body_end + tid; elem(i, y[i], m[i]); }
+}
+
+// dst[i] = src[i] for i < n   (tid / nthreads: this lane's index and the lane count over the row)
+__device__ __forceinline__ void rs_copy_row(float* __restrict__ dst, const float* __restrict__ src, int64_t n, int64_t tid, int64_t nthreads) {
+    const int64_t lead = rs_lead(dst, n);
+    const int64_t nvec = (n - lead) >> 2, body_end = lead + nvec * 4;
+    const bool src_al = rs_al16(src + lead);
+    for (int64_t v = tid; v < nvec; v += nthreads) {
+        const int64_t i = lead + 4 * v;
+        *reinterpret_cast<float4*>(dst + i) = rs_ld4(src + i, src_al);
+    }
+    if (tid < lead) dst[tid] = src[tid];
+    if (tid < n - body_end) dst[body_end + tid] = src[body_end + tid];
+}
+
+__global__ __launch_bounds__(RS_THREADS) void window_scatter_kernel(const aid_window_scatter_params p) {
+    const int j = blockIdx.y;
+    const int64_t tid = (int64_t)blockIdx.x * RS_THREADS + threadIdx.x, nthreads = (int64_t)gridDim.x * RS_THREADS;
+    const rs_job b = rs_load_job(p.jobs, j, p.R, p.L, p.N);
+    if (!b.ok) return;
+    const int64_t hi = p.N - b.s < b.hi ? p.N - b.s : b.hi;                          // samples at or past N do not exist
+    if (hi <= b.lo) return;
+    rs_copy_row(p.out + b.r * p.out_ld + b.s + b.lo, p.x + (int64_t)j * p.L + b.lo, hi - b.lo, tid, nthreads);
+}
+
+extern "C" int aid_restore_abi_version(void) { return AID_RESTORE_ABI_VERSION; }
+
+static int rs_tiles(int64_t L) {
+    int gx = aid_cdiv(aid_cdiv(L, 4), RS_THREADS);                                   // >= 1 tile; every lane of tile 0 exists for the head / tail (< 4 elements each)
+    return gx > 1024 ? 1024 : gx;
+}
+
+extern "C" int aid_window_gather(const aid_window_gather_params* p, void* stream) {
+    AID_REQUIRE(p && p->rec && p->out && p->mask && p->y && p->m && p->jobs, "aid_window_gather: null pointer");
+    AID_REQUIRE(p->J > 0 && p->J <= 65535 && p->R > 0 && p->L > 0 && p->N > 0, "aid_window_gather: empty or oversized shape (1 <= J <= 65535)");
+    AID_REQUIRE(p->rec_ld >= p->N && p->out_ld >= p->N && (p->mask_ld == 0 || p->mask_ld >= p->N), "aid_window_gather: a row stride is shorter than N");
+    hipLaunchKernelGGL(window_gather_kernel, dim3(rs_tiles(p->L), p->J), dim3(RS_THREADS), 0, (hipStream_t)stream, *p);
+    AID_CHECK_LAUNCH();
+    return AID_OK;
+}
+
+extern "C" int aid_window_scatter(const aid_window_scatter_params* p, void* stream) {
+    AID_REQUIRE(p && p->x && p->out && p->jobs, "aid_window_scatter: null pointer");
+    AID_REQUIRE(p->J > 0 && p->J <= 65535 && p->R > 0 && p->L > 0 && p->N > 0, "aid_window_scatter: empty or oversized shape (1 <= J <= 65535)");
+    AID_REQUIRE(p->out_ld >= p->N, "aid_window_scatter: the row stride of out is shorter than N");
+    hipLaunchKernelGGL(window_scatter_kernel, dim3(rs_tiles(p->L), p->J), dim3(RS_THREADS), 0, (hipStream_t)stream, *p);
+    AID_CHECK_LAUNCH();
+    return AID_OK;
+}

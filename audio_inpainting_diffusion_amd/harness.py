@@ -8,6 +8,8 @@
 * ``centre_gap_window`` / ``inpaint_long`` -- the long-file path of the tester (:382-418): the gap sits at the centre of
   the file, a window of ``audio_len`` samples centred on it goes through the sampler, the result is stitched back.
   The reference handles one file per sampler call; here B files form one batch with per-item masks.
+* ``restore_long`` -- whole files of unequal lengths with gaps anywhere, through ``Sampler.predict_inpainting_long`` (restore.py: two
+  batched passes over windows on the autoregressive grid).
 No device code here; everything numerical happens in the sampler / network.
 """
 from __future__ import annotations
@@ -137,6 +139,31 @@ def generate_long(sampler, n_items: int, n_windows: int, seeds: Optional[Sequenc
         from .sampler import autoregressive_length, autoregressive_overlap
         local = torch.zeros((0, autoregressive_length(L, int(autoregressive_overlap(sampler.args) * L), n_windows)), device=device)
     return D.gather_outputs(local, n_items)
+
+
+def restore_long(sampler, files: Sequence[torch.Tensor], masks: Sequence[torch.Tensor], seeds: Optional[Sequence[int]] = None, max_batch: int = 8,
+                 device="cuda") -> List[torch.Tensor]:
+    """Restore every 1-D waveform of ``files`` (any lengths) where its mask (same length; 1 = observed, 0 = gap, gaps anywhere) is 0 and return the
+    full-length results on ``device``, in the order of ``files``.  Files of equal length go through ONE Sampler.predict_inpainting_long call, so
+    their windows share the two batched passes; every other length is a call of its own.  ``seeds``: one RNG seed per file (file i's result then
+    depends on seeds[i] alone, not on the grouping)."""
+    if len(masks) != len(files):
+        raise ValueError(f"restore_long: {len(masks)} masks for {len(files)} files")
+    if seeds is not None and len(seeds) != len(files):
+        raise ValueError(f"restore_long: {len(seeds)} seeds for {len(files)} files")
+    groups = {}
+    for i, (x, m) in enumerate(zip(files, masks)):
+        if x.numel() != m.numel():
+            raise ValueError(f"restore_long: file {i} has {x.numel()} samples, its mask {m.numel()}")
+        groups.setdefault(x.numel(), []).append(i)
+    out: List[Optional[torch.Tensor]] = [None] * len(files)
+    for idx in groups.values():
+        y = torch.stack([files[i].reshape(-1).float() for i in idx]).to(device)
+        m = torch.stack([masks[i].reshape(-1).float() for i in idx])
+        res = sampler.predict_inpainting_long(y, m, max_batch=max_batch, seeds=None if seeds is None else [int(seeds[i]) for i in idx])
+        for k, i in enumerate(idx):
+            out[i] = res[k]
+    return out
 
 
 # ---- waveform pre-/post-processing of the tester --------------------------------------------------------------------------------

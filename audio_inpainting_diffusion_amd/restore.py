@@ -1,0 +1,172 @@
+"""Restoration of whole recordings, longer than one model segment, with gaps anywhere -- in two batched sampler passes.
+
+Windows of L = args.exp.audio_len samples lie on the autoregressive grid: window w starts at w * step, step = L - end,
+end = int(overlap * L) (sampler.autoregressive_overlap), so neighbours share ``end`` samples.  Every sample of the recording is OWNED
+by exactly one window:
+
+    even w                      [s_w, s_w + L)                  the whole window
+    odd  w                      [s_w + end, s_w + L - end)      the middle its two even neighbours leave free
+    odd last w (no neighbour)   [s_w + end, s_w + L)
+
+Even windows do not overlap one another, so pass A inpaints all of them that hold a gap as ONE batch, each from its own observations.
+Pass B does the same for the odd windows; their first and last ``end`` samples are taken as observed from the result restored so far
+(what pass A wrote there, or the recording), the way a window of autoregressive generation is conditioned on the tail of the one before
+it.  A window whose owned range has no gap is no job and costs nothing.  Hard concatenation, no cross-fade (as the reference's
+autoregressive mode, testing/edm_sampler.py:416).
+
+``restore_plan`` is host code (the only part that looks at the mask on the host); ``window_gather`` / ``window_scatter`` launch the
+two HIP kernels of csrc/aid_restore.hip; ``restore_passes`` is the pass code, driven with anything that has ``predict_inpainting``.
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence, Tuple
+
+import torch
+
+from . import _lib
+
+Job = Tuple[int, int, int, int, int, int]            # (recording r, start s, head, tail, lo, hi)
+SEED_STRIDE = 65536                                  # the job of window w of recording r runs with seed seeds[r] * SEED_STRIDE + w
+
+
+def restore_windows(N: int, L: int, end: int) -> List[Tuple[int, int, int, int, int]]:
+    """(start s, head, tail, lo, hi) of every window of a recording of N samples; [lo, hi) is the owned range relative to s, cut at N."""
+    N, L, end = int(N), int(L), int(end)
+    if N < 1 or L < 1:
+        raise _lib.AidError(f"restore_plan: N = {N} and L = {L} must be >= 1")
+    if not (1 <= end and 2 * end < L):
+        raise _lib.AidError(f"restore_plan: the overlap end = {end} must lie in [1, L/2) for L = {L}, so that an odd window owns a non-empty middle")
+    step = L - end
+    W = max(1, -(-(N - L) // step) + 1)
+    wins = []
+    for w in range(W):
+        s = w * step
+        if w % 2 == 0:
+            head, tail, lo, hi = 0, 0, 0, L
+        elif w == W - 1:
+            head, tail, lo, hi = end, 0, end, L
+        else:
+            head, tail, lo, hi = end, end, end, L - end
+        wins.append((s, head, tail, lo, min(hi, N - s)))
+    return wins
+
+
+def restore_plan(mask: torch.Tensor, L: int, end: int, R: Optional[int] = None) -> Tuple[List[Job], List[Job], int]:
+    """mask [R, N] or [1, N] (1 = observed, 0 = gap; any dtype / device) -> (jobs_A, jobs_B, N_pad): the even / odd windows whose owned
+    range holds a zero of the mask, as (r, s, head, tail, lo, hi), ordered by recording and window; N_pad = L + (W - 1) * step is the
+    length the grid covers (samples from N on do not exist: nobody owns them and they make no window a job).
+    ``R``: number of recordings a one-row mask is shared by (its jobs are repeated for every recording); default mask.shape[0]."""
+    if mask.dim() == 1:
+        mask = mask.reshape(1, -1)
+    if mask.dim() != 2:
+        raise _lib.AidError(f"restore_plan: mask must be [R, N] or [1, N], got {tuple(mask.shape)}")
+    rows, N = mask.shape
+    R = rows if R is None else int(R)
+    if rows not in (1, R):
+        raise _lib.AidError(f"restore_plan: a mask of {rows} rows for {R} recordings")
+    wins = restore_windows(N, L, end)
+    gap = (mask.detach().to("cpu") == 0)
+    # zeros before sample q, per row: a window is active when the count differs between the ends of its owned range
+    cum = torch.zeros((rows, N + 1), dtype=torch.int64)
+    cum[:, 1:] = torch.cumsum(gap, dim=1)
+    jobs_A: List[Job] = []
+    jobs_B: List[Job] = []
+    for r in range(R):
+        c = cum[r if rows > 1 else 0]
+        for w, (s, head, tail, lo, hi) in enumerate(wins):
+            if int(c[s + hi]) > int(c[s + lo]):
+                (jobs_B if w % 2 else jobs_A).append((r, s, head, tail, lo, hi))
+    return jobs_A, jobs_B, L + (len(wins) - 1) * (L - end)
+
+
+def job_table(jobs: Sequence[Job], device) -> torch.Tensor:
+    """[J, 6] int64 on ``device``: the table aid_window_gather / aid_window_scatter read (include/aid_restore.h)"""
+    return torch.tensor(list(jobs), dtype=torch.int64).reshape(-1, _lib.AID_RESTORE_JOB_FIELDS).to(device)
+
+
+def _rows(t: torch.Tensor, what: str):
+    _lib._req(t)
+    if t.dim() != 2 or (t.stride(1) != 1 and t.shape[1] > 1):
+        raise _lib.AidError(f"{what} must be [rows, N] with contiguous rows")
+
+
+def _table(jobs: torch.Tensor):
+    if not (jobs.is_cuda and jobs.dtype == torch.int64 and jobs.dim() == 2 and jobs.shape[1] == _lib.AID_RESTORE_JOB_FIELDS and jobs.is_contiguous()):
+        raise _lib.AidError("the job table must be a contiguous [J, 6] int64 tensor on the GPU (restore.job_table)")
+
+
+def window_gather(rec: torch.Tensor, out: torch.Tensor, mask: torch.Tensor, jobs: torch.Tensor, L: int):
+    """One aid_window_gather launch on the current stream -> (y [J, L], m [J, L]): the observations and the mask of every job's window;
+    the first ``head`` / last ``tail`` samples observed from ``out``, the rest from ``rec`` under ``mask`` ([R, N] or [1, N], float32)."""
+    for t, what in ((rec, "rec"), (out, "out"), (mask, "mask")):
+        _rows(t, what)
+    _table(jobs)
+    R, N = rec.shape
+    if out.shape != rec.shape or mask.shape[1] != N or mask.shape[0] not in (1, R):
+        raise _lib.AidError(f"window_gather: rec {tuple(rec.shape)}, out {tuple(out.shape)} and mask {tuple(mask.shape)} do not match")
+    J = jobs.shape[0]
+    y = torch.empty((J, L), dtype=torch.float32, device=rec.device)
+    m = torch.empty((J, L), dtype=torch.float32, device=rec.device)
+    if J:
+        _lib.call("aid_window_gather", _lib.WindowGatherParams(rec.data_ptr(), out.data_ptr(), mask.data_ptr(), y.data_ptr(), m.data_ptr(), jobs.data_ptr(),
+                                                                J, R, int(L), N, rec.stride(0), out.stride(0), mask.stride(0) if mask.shape[0] > 1 else 0))
+    return y, m
+
+
+def window_scatter(x: torch.Tensor, out: torch.Tensor, jobs: torch.Tensor):
+    """One aid_window_scatter launch on the current stream: out[r_j, s_j + i] = x[j, i] over every job's owned range, below N."""
+    _rows(out, "out")
+    _lib._req(x)
+    _table(jobs)
+    J = jobs.shape[0]
+    if x.dim() != 2 or x.shape[0] != J or not x.is_contiguous():
+        raise _lib.AidError(f"window_scatter: x must be contiguous [J = {J}, L], got {tuple(x.shape)}")
+    if J:
+        _lib.call("aid_window_scatter", _lib.WindowScatterParams(x.data_ptr(), out.data_ptr(), jobs.data_ptr(), J, out.shape[0], x.shape[1], out.shape[1], out.stride(0)))
+
+
+def check_restore_args(y: torch.Tensor, mask: torch.Tensor, L: int, end: int, max_batch: int, seeds) -> torch.Tensor:
+    """The refusals of a restoration, all raised before anything is launched -> the mask as [1|R, N]."""
+    if not (torch.is_tensor(y) and y.is_cuda and y.dtype == torch.float32):
+        raise _lib.AidError("restoration of whole recordings runs on the GPU only (no CPU fallback): y must be a float32 tensor on the GPU")
+    if mask.dim() == 1:
+        mask = mask.reshape(1, -1)
+    if y.dim() != 2 or mask.dim() != 2 or mask.shape[1] != y.shape[1] or mask.shape[0] not in (1, y.shape[0]):
+        raise _lib.AidError(f"mask {tuple(mask.shape)} does not match recordings {tuple(y.shape)} (y [R, N], mask [1, N] or [R, N])")
+    if y.shape[1] > 1 and y.stride(1) != 1:
+        raise _lib.AidError("the rows of y must be contiguous")
+    restore_windows(y.shape[1], L, end)                               # (end in [1, L/2))
+    if max_batch < 1:
+        raise _lib.AidError(f"max_batch must be >= 1, got {max_batch}")
+    if seeds is not None and len(seeds) != y.shape[0]:
+        raise _lib.AidError(f"{len(seeds)} seeds for {y.shape[0]} recordings")
+    return mask
+
+
+def restore_passes(sampler, y: torch.Tensor, mask: torch.Tensor, L: int, end: int, max_batch: int = 8, seeds: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """The two passes over ``sampler.predict_inpainting(yw [B, L], mw [B, L]) -> [B, L]`` with B <= max_batch: y [R, N] recordings on the GPU
+    (rows contiguous, any row stride), mask [1|R, N] -> restored [R, N].  Per pass: one gather launch, the sampler calls, one scatter launch per
+    call.  Recordings, mask and result stay on the GPU; the plan is made on the host from the mask before pass A.  ``seeds`` [R]: the job of
+    window w of recording r runs with ``sampler.seeds = [seeds[r] * 65536 + w, ...]`` (None: sampler.seeds = None, the global generator)."""
+    mask = check_restore_args(y, mask, L, end, max_batch, seeds)
+    R, N = y.shape
+    jobs_A, jobs_B, _ = restore_plan(mask, L, end, R)
+    out = torch.empty((R, N), dtype=torch.float32, device=y.device)
+    out.copy_(y)
+    if not (jobs_A or jobs_B):
+        return out
+    dmask = mask.to(y.device, torch.float32).contiguous()
+    tables = [(jobs, job_table(jobs, y.device)) for jobs in (jobs_A, jobs_B) if jobs]
+    step = L - end
+    keep = getattr(sampler, "seeds", None)
+    try:
+        for jobs, table in tables:
+            yw, mw = window_gather(y, out, dmask, table, L)         # (pass B reads what pass A scattered: same stream, in order)
+            for c0 in range(0, len(jobs), max_batch):
+                c1 = min(len(jobs), c0 + max_batch)
+                sampler.seeds = None if seeds is None else [int(seeds[r]) * SEED_STRIDE + s // step for r, s, *_ in jobs[c0:c1]]
+                x = sampler.predict_inpainting(yw[c0:c1], mw[c0:c1])
+                window_scatter(x.contiguous(), out, table[c0:c1])
+    finally:
+        sampler.seeds = keep
+    return out

@@ -30,19 +30,24 @@ from .stft import SpectralMask
 
 def prepare_smooth_mask(mask: torch.Tensor, size: int) -> torch.Tensor:
     """Hann cross-fade of the mask edges, row by row (vectorised form of :302-325; the reference walks all L
-    samples of row 0 in a Python loop and re-uses the result for every item)."""
+    samples of row 0 in a Python loop and re-uses the result for every item).  A ramp that would reach past an end of the row -- where the
+    reference's slice assignment raises -- is cut there: the windows of a whole-recording restoration (restore.py) have gaps anywhere."""
     hann = torch.hann_window(size * 2)
     left, right = hann[0:size], hann[size:]
     m = mask.detach().to("cpu", torch.float32)
     out = m.clone()
+    n = m.shape[1]
     for r in range(m.shape[0]):
         row = m[r].numpy()
         prev = np.concatenate(([1.0], row[:-1]))
         for i in np.nonzero(row != prev)[0]:
+            i = int(i)
             if row[i] == 0:
-                out[r, i - size:i] = right
+                a = max(i - size, 0)
+                out[r, a:i] = right[size - (i - a):]
             if row[i] == 1:
-                out[r, i:i + size] = left
+                b = min(i + size, n)
+                out[r, i:b] = left[:b - i]
     return out
 
 
@@ -484,6 +489,22 @@ class Sampler:
         finally:
             self._keep_gens = False
         return out
+
+    def predict_inpainting_long(self, y, mask, max_batch=8, seeds=None):
+        """Restore whole recordings y[R, N] -- N any length, gaps wherever mask[1|R, N] is 0 -> [R, N] on y.device (restore.py).  Windows of
+        L = args.exp.audio_len samples on the autoregressive grid (end = int(overlap * L) shared samples, 1 <= end < L/2); the even windows that
+        hold a gap are inpainted as one batch, then the odd ones, conditioned on their neighbours' restored overlaps: two rounds of
+        predict_inpainting in chunks of at most ``max_batch`` windows, one aid_window_gather launch per round and one aid_window_scatter launch per
+        chunk.  Windows without a gap cost nothing; samples outside every gap's window stay the recording's.  ``seeds`` [R]: window w of recording
+        r runs with seed seeds[r] * 65536 + w, so a recording's result depends neither on the other recordings nor on max_batch."""
+        from . import restore
+        if self.rid:
+            raise _lib.AidError("predict_inpainting_long returns the restored recordings only: rid must be False")
+        L = int(self.args.exp.audio_len)
+        end = int(autoregressive_overlap(self.args) * L)
+        mask = restore.check_restore_args(y, mask, L, end, max_batch, seeds)
+        self._check_model()
+        return restore.restore_passes(self, y, mask, L, end, max_batch, seeds)
 
     # ---- the remaining public methods of the reference class (its testers never call them; kept so that code written against
     # ---- testing.edm_sampler_inpainting.Sampler finds every name).  They run outside the sampling loop. ------------------------------
