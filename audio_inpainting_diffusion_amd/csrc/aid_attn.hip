@@ -18,8 +18,7 @@
 // the same register / shuffle / LDS reductions, then dV = dO P, dQ = K dS^T, dK = Q dS as three [32 rows of F] x [T] x [T]
 // MFMA products per workgroup reading P and dS straight from L2.
 #include "aid_common.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "aid_mfma_dma.h"
 
 #define ATT_TMAX 128
 #define ATT_LDP 33            // leading dimension of the P^T exchange tile in LDS (conflict-free column access)

@@ -20,9 +20,8 @@
 //   fp32 MFMA is exact fp32 FMA arithmetic (cdna_hip_programming.md section 3), so parity with the reference's
 //   F.conv2d is limited only by summation order.
 #include "aid_common.h"
+#include "aid_mfma_dma.h"
 #include <stdlib.h>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct ConvDev {
     aid_conv2d_params p;

@@ -15,9 +15,8 @@
 //   * loads run PF k-steps ahead of the MFMAs that consume them (register ring).
 // Epilogue identical to conv_mfma_kernel: y = alpha*(res_scale*res + acc*out_scale[b,co]) or the dGELU form.
 #include "aid_common.h"
+#include "aid_mfma_dma.h"
 #include <stdlib.h>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct C1Dev {
     aid_conv2d_params p;

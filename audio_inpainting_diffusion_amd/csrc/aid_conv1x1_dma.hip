@@ -12,10 +12,10 @@
 //     conflict-free ds_read_b64 and the epilogue stores float2.
 // Per-(b,ci) prologue scale (in_scale) is applied to the A fragment (a tile never straddles two samples: host-checked).
 #include "aid_common.h"
+#include "aid_mfma_dma.h"
 #include <type_traits>
 #include <stdlib.h>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 int aid_conv_splitk_reduce(const aid_conv2d_params* p, const float* ws, int splits, hipStream_t st);      // aid_conv.hip
 
 struct C11Dev {
@@ -29,9 +29,6 @@ struct C11Dev {
 };
 
 __device__ float4 g_aid_zero_page_c11[16];
-
-#define GLDS16C(gptr, lptr) \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr), (__attribute__((address_space(3))) void*)(lptr), 16, 0, 0)
 
 // MT m-tiles (32 cout) x 2 interleaved position tiles per wave; WGM x WGN waves; N_BLK = 64 * WGN positions
 template <int MT, int WGM, int WGN, int RMAX, int KC, int MINW>
@@ -145,7 +142,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv11_dma_kernel(const 
         for (int i = 0; i < PPW; ++i) {
             if (plds[i] >= 0) {
                 const float* src = ch < a.nch1 ? psrc[i] + (int64_t)ch * pstride[i] : psrc2[i] + (int64_t)(ch - a.nch1) * pstride2[i];
-                GLDS16C(src, buf + plds[i]);
+                AID_GLDS16(src, buf + plds[i]);
             }
         }
     };

@@ -16,10 +16,9 @@
 //   * the epilogue (out_scale, dGELU(aux), residual, alpha, <y, aux> partials) is conv11_dma_kernel's, per wave.
 // The k-pairs are accumulated in increasing order into one accumulator per output, as in the other 1x1 kernels.
 #include "aid_common.h"
+#include "aid_mfma_dma.h"
 #include <stdint.h>
 #include <stdlib.h>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct C11RDev {
     aid_conv2d_params p;

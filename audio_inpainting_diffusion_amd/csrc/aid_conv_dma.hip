@@ -15,10 +15,9 @@
 //     `__syncthreads()` (vmcnt(0) + barrier) per chunk, priority-based progress balancing between the waves
 //     of a SIMD (see aid_conv.hip).
 #include "aid_common.h"
+#include "aid_mfma_dma.h"
 #include <type_traits>
 #include <stdlib.h>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct ConvDmaDev {
     aid_conv2d_params p;
@@ -27,9 +26,6 @@ struct ConvDmaDev {
 };
 
 __device__ float4 g_aid_zero_page[16];
-
-#define GLDS16(gptr, lptr) \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr), (__attribute__((address_space(3))) void*)(lptr), 16, 0, 0)
 
 template <int MT, int NT, int WGM, int WGN, int RMAX, int KC, int MINW>
 __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv53_dma_kernel(const ConvDmaDev a) {
@@ -170,7 +166,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv53_dma_kernel(const 
         for (int i = 0; i < PPW; ++i) {
             if (plds[i] >= 0) {                          // wave-uniform
                 const float* src = psrc[i] + (int64_t)ch * pstride[i];
-                GLDS16(src, buf + plds[i]);
+                AID_GLDS16(src, buf + plds[i]);
             }
         }
 #pragma unroll

@@ -12,12 +12,11 @@
 //   conv53_wino8r_ks_kernel : its K-group instance for launches of at most one tile per CU (small batches): eight waves on one tile, two K groups, sum through LDS
 // Which form takes a launch: wino_form_choice() / aid_conv2d_wino_form().
 #include "aid_common.h"
+#include "aid_mfma_dma.h"
 #include "aid_wino8.h"
 #include "aid_fin.h"
 #include <type_traits>
 #include <stdlib.h>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct ConvWinoDev {
     aid_conv2d_params p;
@@ -27,35 +26,6 @@ struct ConvWinoDev {
 };
 
 __device__ float4 g_aid_zero_page_w[16];   // (device symbols are per translation unit without -fgpu-rdc)
-
-#define GLDS16W(gptr, lptr) \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gptr), (__attribute__((address_space(3))) void*)(lptr), 16, 0, 0)
-
-// Direct-to-LDS loads issued through inline asm (used by the triple-buffered Winograd-domain-input kernel): the compiler's
-// waitcnt insertion cannot tell which LDS buffer a global_load_lds writes and would drain vmcnt before the next ds_read of
-// ANY buffer; issued this way it does not see them and the kernel places its own s_waitcnt vmcnt(n).  vmcnt completes in
-// order, so every wait the compiler emits for its own loads stays correct (it can only over-wait).  M0 is a reserved
-// register: nothing else in these kernels keeps a value in it.
-#define AID_LDS_ADDR(lptr) ((unsigned)(uintptr_t)(__attribute__((address_space(3))) const void*)(lptr))
-#define AID_DMA16_RAW(gptr, lds_addr) \
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(gptr), "s"(lds_addr) : "memory")
-// the same with a SCALAR 64-bit base and a 32-bit per-lane byte offset (one VGPR per piece instead of a 64-bit pointer and a per-lane stride)
-#define AID_DMA16_SBASE(voff, sbase, lds_addr) \
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(voff), "s"(sbase), "s"(lds_addr) : "memory")
-// s_waitcnt immediates (gfx9 encoding: vmcnt[3:0] | expcnt[6:4] | lgkmcnt[11:8] | vmcnt[5:4] << 14)
-#define AID_VMCNT(n) ((((n) & 15) | (7 << 4) | (15 << 8) | ((((n) >> 4) & 3) << 14)))
-#define AID_LGKMCNT0 (15 | (7 << 4) | (0 << 8) | (3 << 14))
-
-template <typename F, int... I>
-__device__ __forceinline__ void aid_static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, typename F>
-__device__ __forceinline__ void aid_static_for(F&& f) { aid_static_for_impl(f, std::make_integer_sequence<int, N>{}); }
-// s_waitcnt vmcnt(n) for a wave-uniform n in [0, NMAX] (the instruction takes an immediate)
-template <int NMAX>
-__device__ __forceinline__ void aid_wait_vmcnt_le(int n) {
-    if constexpr (NMAX == 0) { __builtin_amdgcn_s_waitcnt(AID_VMCNT(0)); }
-    else { if (n >= NMAX) __builtin_amdgcn_s_waitcnt(AID_VMCNT(NMAX)); else aid_wait_vmcnt_le<NMAX - 1>(n); }
-}
 
 // ---- F(4,3): 6 products per 4 outputs (2x fewer MFMAs than direct).  tau now indexes GROUPS of 4 output samples:
 //   V = B^T d (d = 6 samples 4g-1 .. 4g+4):  V0 = 4d0-5d2+d4, V1 = (d3+d4)-4(d1+d2), V2 = (d4-d3)+4(d1-d2),
@@ -215,7 +185,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv53_wino4_kernel(cons
         for (int i = 0; i < PPW; ++i) {
             if (plds[i] >= 0) {
                 const float* src = psrc[i] + (int64_t)ch * pstride[i];
-                GLDS16W(src, buf + plds[i]);
+                AID_GLDS16(src, buf + plds[i]);
             }
         }
 #pragma unroll
@@ -1286,53 +1256,28 @@ __global__ __launch_bounds__(512, 2) void conv53_wino8r_ks_kernel(const ConvWino
     }
 }
 
-template <int MT, int NTT, int WGM, int WGN, int RMAX, int KC, int MINW = 1>
-static int launch_wino4(const aid_conv2d_params* p, hipStream_t st) {
-    constexpr int M_BLK = 32 * MT * WGM;
-    constexpr int N_BLK = 128 * NTT * WGN;
+// the device zero page of this translation unit (looked up once); nullptr with the error set when the lookup fails
+static const float* wino_zero_page() {
     static const float* zero = nullptr;
     if (!zero) {
         void* z = nullptr;
-        if (hipGetSymbolAddress(&z, HIP_SYMBOL(g_aid_zero_page_w)) != hipSuccess) { aid_set_error("aid_conv2d: zero page lookup failed"); return AID_E_LAUNCH; }
+        if (hipGetSymbolAddress(&z, HIP_SYMBOL(g_aid_zero_page_w)) != hipSuccess) { aid_set_error("aid_conv2d: zero page lookup failed"); return nullptr; }
         zero = (const float*)z;
     }
-    ConvWinoDev a;
-    a.p = *p;
-    a.zero = zero;
-    int TT = aid_pow2ceil(p->T);
-    if (TT > N_BLK) TT = N_BLK;
-    a.tt_log2 = aid_ilog2(TT);
-    const int ROWS = N_BLK / TT;
-    if (ROWS > RMAX) return 1000;
-    a.rows_log2 = aid_ilog2(ROWS);
-    a.tiles_t = aid_cdiv(p->T, TT);
-    a.nrows = p->B * p->F;
-    a.nchunks = p->Cin / KC;
-    const int rgroups = aid_cdiv(a.nrows, ROWS);
-    dim3 grid((unsigned)(rgroups * a.tiles_t), (unsigned)(p->Cout_pad / M_BLK));
-    auto kern = conv53_wino4_kernel<MT, NTT, WGM, WGN, RMAX, KC, MINW>;      // LDS is static (see the kernel)
-    a.nx = (int)grid.x; a.ny = (int)grid.y;
-    a.per_xcd = (a.nx * a.ny + 7) / 8;                  // XCD-aware 1-D grid (see the kernel)
-    grid = dim3((unsigned)(8 * a.per_xcd), 1);
-    hipLaunchKernelGGL(kern, grid, dim3(64 * WGM * WGN), 0, st, a);
-    AID_CHECK_LAUNCH();
-    aid_note_kernel(M_BLK == 96 ? "conv53_wino4_kernel(96)" : ((M_BLK == 64 && N_BLK == 256) ? "conv53_wino4_kernel(64x256)" : "conv53_wino4_kernel"));
-    return AID_OK;
+    return zero;
 }
 
-template <int MT, int NTT, int WGM, int WGN, int RMAX, int KC, int MINW = 1>
-static int launch_wino4v(const aid_conv2d_params* p, hipStream_t st) {
+// The launcher of the two older F(4,3) kernels (conv53_wino4_kernel / conv53_wino4v_kernel: the same tile geometry and grid, different staging).
+// names: the noted name of the 64|128 x 512, the 96 x 512 and the 64 x 256 instance.
+struct Wino4Names { const char *plain, *m96, *small; };
+template <int MT, int NTT, int WGM, int WGN, int RMAX, int KC, typename Kern>
+static int launch_wino4_tiles(Kern kern, const Wino4Names& names, const aid_conv2d_params* p, hipStream_t st) {
     constexpr int M_BLK = 32 * MT * WGM;
     constexpr int N_BLK = 128 * NTT * WGN;
-    static const float* zero = nullptr;
-    if (!zero) {
-        void* z = nullptr;
-        if (hipGetSymbolAddress(&z, HIP_SYMBOL(g_aid_zero_page_w)) != hipSuccess) { aid_set_error("aid_conv2d: zero page lookup failed"); return AID_E_LAUNCH; }
-        zero = (const float*)z;
-    }
     ConvWinoDev a;
     a.p = *p;
-    a.zero = zero;
+    a.zero = wino_zero_page();
+    if (!a.zero) return AID_E_LAUNCH;
     int TT = aid_pow2ceil(p->T);
     if (TT > N_BLK) TT = N_BLK;
     a.tt_log2 = aid_ilog2(TT);
@@ -1343,15 +1288,22 @@ static int launch_wino4v(const aid_conv2d_params* p, hipStream_t st) {
     a.nrows = p->B * p->F;
     a.nchunks = p->Cin / KC;
     const int rgroups = aid_cdiv(a.nrows, ROWS);
-    dim3 grid((unsigned)(rgroups * a.tiles_t), (unsigned)(p->Cout_pad / M_BLK));
-    auto kern = conv53_wino4v_kernel<MT, NTT, WGM, WGN, RMAX, KC, MINW>;      // LDS is static (see the kernel)
-    a.nx = (int)grid.x; a.ny = (int)grid.y;
+    a.nx = rgroups * a.tiles_t; a.ny = p->Cout_pad / M_BLK;
     a.per_xcd = (a.nx * a.ny + 7) / 8;                  // XCD-aware 1-D grid (see the kernel)
-    grid = dim3((unsigned)(8 * a.per_xcd), 1);
-    hipLaunchKernelGGL(kern, grid, dim3(64 * WGM * WGN), 0, st, a);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(8 * a.per_xcd), 1), dim3(64 * WGM * WGN), 0, st, a);      // LDS is static (see the kernel)
     AID_CHECK_LAUNCH();
-    aid_note_kernel((M_BLK == 64 && N_BLK == 256) ? "conv53_wino4v_kernel(64x256)" : (M_BLK == 96 ? "conv53_wino4v_kernel(96)" : "conv53_wino4v_kernel"));
+    aid_note_kernel(M_BLK == 96 ? names.m96 : ((M_BLK == 64 && N_BLK == 256) ? names.small : names.plain));
     return AID_OK;
+}
+template <int MT, int NTT, int WGM, int WGN, int RMAX, int KC, int MINW = 1>
+static int launch_wino4(const aid_conv2d_params* p, hipStream_t st) {
+    return launch_wino4_tiles<MT, NTT, WGM, WGN, RMAX, KC>(conv53_wino4_kernel<MT, NTT, WGM, WGN, RMAX, KC, MINW>,
+                                                           {"conv53_wino4_kernel", "conv53_wino4_kernel(96)", "conv53_wino4_kernel(64x256)"}, p, st);
+}
+template <int MT, int NTT, int WGM, int WGN, int RMAX, int KC, int MINW = 1>
+static int launch_wino4v(const aid_conv2d_params* p, hipStream_t st) {
+    return launch_wino4_tiles<MT, NTT, WGM, WGN, RMAX, KC>(conv53_wino4v_kernel<MT, NTT, WGM, WGN, RMAX, KC, MINW>,
+                                                           {"conv53_wino4v_kernel", "conv53_wino4v_kernel(96)", "conv53_wino4v_kernel(64x256)"}, p, st);
 }
 
 // row-shared kernel: eligibility + launch.  Returns 1000 when the shape is better served by the 64|96 x 512 kernel.
@@ -1428,12 +1380,8 @@ static int wino_fin_check(const aid_conv2d_params* p) {
 }
 
 static int launch_wino4r(const aid_conv2d_params* p, hipStream_t st) {
-    static const float* zero = nullptr;
-    if (!zero) {
-        void* z = nullptr;
-        if (hipGetSymbolAddress(&z, HIP_SYMBOL(g_aid_zero_page_w)) != hipSuccess) { aid_set_error("aid_conv2d: zero page lookup failed"); return AID_E_LAUNCH; }
-        zero = (const float*)z;
-    }
+    const float* const zero = wino_zero_page();
+    if (!zero) return AID_E_LAUNCH;
     Wino4rPlan plan[2];
     const int nl = wino4r_geometry(p, plan);
     if (!nl) return 1000;
@@ -1598,12 +1546,8 @@ static bool wino8r_ks_wanted(int64_t ntiles) {
 
 
 static int launch_wino8r(const aid_conv2d_params* p, hipStream_t st) {
-    static const float* zero = nullptr;
-    if (!zero) {
-        void* z = nullptr;
-        if (hipGetSymbolAddress(&z, HIP_SYMBOL(g_aid_zero_page_w)) != hipSuccess) { aid_set_error("aid_conv2d: zero page lookup failed"); return AID_E_LAUNCH; }
-        zero = (const float*)z;
-    }
+    const float* const zero = wino_zero_page();
+    if (!zero) return AID_E_LAUNCH;
     Wino4rPlan plan[2];
     const int nl = wino8r_geometry(p, plan);
     AID_REQUIRE(nl, "aid_conv2d: x_wino = 2 (F(8,3)) needs a shape aid_conv2d_wino8_supported() answers 1 for");

@@ -17,10 +17,9 @@
 //   aid_adam / aid_ema / aid_sumsq       fused optimiser update, EMA update and gradient-norm partials over flat buffers
 // Everything is deterministic (fixed summation orders, no atomics).
 #include "aid_common.h"
+#include "aid_mfma_dma.h"
 #include "aid_wino8.h"
 #include "aid_wino45.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #define WG_TC 64                 // positions (t) per staged chunk
 #define WG_LDA (WG_TC + 1)       // gy rows in LDS

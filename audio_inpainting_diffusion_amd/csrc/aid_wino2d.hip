@@ -17,27 +17,11 @@
 // groups of TF samples (TG = T / TF), xi = xf * NTP + xt, position index as above with T/TF groups per row.  fp32 error 1.0e-5 (K = 128) / 1.3e-5 (K = 256)
 // per layer (tools/wino2d_fm5_error.py --tf 8, profiles/r06_wino2d_f45x83_error.txt) against 2.8 / 4.3e-6 for F(4,5) x F(4,3).
 #include "aid_common.h"
+#include "aid_mfma_dma.h"
 #include "aid_wino45.h"
 #include "aid_wino8.h"
 #include "aid_fin.h"
-#include <type_traits>
-#include <utility>
 #include <stdlib.h>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// direct-to-LDS load, scalar 64-bit base + 32-bit per-lane byte offset (see aid_conv_wino.hip: issued through inline asm so that the kernel,
-// not the compiler's waitcnt pass, decides how long the loads stay in flight)
-#define W2D_LDS_ADDR(lptr) ((unsigned)(uintptr_t)(__attribute__((address_space(3))) const void*)(lptr))
-#define W2D_DMA16_SBASE(voff, sbase, lds_addr) \
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(voff), "s"(sbase), "s"(lds_addr) : "memory")
-#define W2D_VMCNT(n) ((((n) & 15) | (7 << 4) | (15 << 8) | ((((n) >> 4) & 3) << 14)))
-#define W2D_LGKMCNT0 (15 | (7 << 4) | (0 << 8) | (3 << 14))
-
-template <typename F, int... I>
-__device__ __forceinline__ void w2d_static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, typename F>
-__device__ __forceinline__ void w2d_static_for(F&& f) { w2d_static_for_impl(f, std::make_integer_sequence<int, N>{}); }
 
 // =====================================================================================================================================
 // 2. the batched GEMM.  Per transform index xi:  C[m][n] = sum_k A[k][m] B[k][n],  A = U_xi [Cin][Cout_pad], B = V_xi [Cin][N], C = M_xi [Cout][N].
@@ -45,6 +29,8 @@ __device__ __forceinline__ void w2d_static_for(F&& f) { w2d_static_for_impl(f, s
 // the loads of chunk c + NBUF - 1 issued one piece per k-step while chunk c is multiplied); LDS images are [k][m] / [k][n] exactly as in memory,
 // a lane's MT (NT) fragments are INTERLEAVED rows (columns) m = MT*i + .. so that one ds_read_b64 / b128 feeds all of them and the epilogue
 // stores float4 along n.  Two workgroups per CU: one tile's 128-KB store epilogue runs under the other's K loop.
+// Three kernels (fp32 MFMA, the bf16-split variant, the row fold) are thin entries over ONE set of pieces: w2d_tile_of, w2d_piece_offsets,
+// w2d_issue_piece, w2d_chunk_wait, w2d_ksteps, w2d_store_tile.  A change to the pipeline is made there, once.
 // =====================================================================================================================================
 struct W2dGemmDev {
     const float* U; const float* V; float* Mo;
@@ -52,14 +38,16 @@ struct W2dGemmDev {
     int nchunks, ntn, ntm, ntiles, per_xcd;
 };
 
-template <int MT, int NT, int WGM, int WGN, int KC, int NBUF>
+template <int MT_, int NT_, int WGM_, int WGN_, int KC_, int NBUF_>
 struct W2dGemmShape {
+    static constexpr int MT = MT_, NT = NT_, WGM = WGM_, WGN = WGN_, KC = KC_, NBUF = NBUF_;
     static constexpr int NW = WGM * WGN;
     static constexpr int M_BLK = 32 * MT * WGM, N_BLK = 32 * NT * WGN;
     static constexpr int XSZ = KC * N_BLK, WSZ = KC * M_BLK, BUFSZ = XSZ + WSZ;
     static constexpr int NXP = XSZ / 256, NWP = WSZ / 256, NP = NXP + NWP;
     static constexpr int PPW = (NP + NW - 1) / NW;
     static constexpr int NSTEP = KC / 2;
+    static constexpr int AHEAD = NBUF - 1;                     // chunks in flight ahead of the one being multiplied
     static constexpr int LDS = NBUF * BUFSZ;
     static_assert(XSZ % 256 == 0 && WSZ % 256 == 0 && NP % NW == 0, "whole 1-KiB pieces, the same number for every wave");
 };
@@ -75,141 +63,193 @@ __device__ __forceinline__ float w2d_get(const float& v, int) { return v; }
 __device__ __forceinline__ float w2d_get(const float2& v, int i) { return i ? v.y : v.x; }
 __device__ __forceinline__ float w2d_get(const float4& v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : (i == 2 ? v.z : v.w)); }
 
-template <int NMAX>
-__device__ __forceinline__ void w2d_wait_vmcnt(int n) {
-    if constexpr (NMAX == 0) { __builtin_amdgcn_s_waitcnt(W2D_VMCNT(0)); }
-    else { if (n >= NMAX) __builtin_amdgcn_s_waitcnt(W2D_VMCNT(NMAX)); else w2d_wait_vmcnt<NMAX - 1>(n); }
+// ---- the pieces the three kernels share ---------------------------------------------------------------------------------------------
+struct W2dWave { int lane, wave, wm, wn, half; };          // wave (wm, wn) of the WGM x WGN workgroup; half = which 32 lanes
+template <class S>
+__device__ __forceinline__ W2dWave w2d_wave_of() {
+    W2dWave w;
+    const int tid = threadIdx.x;
+    w.lane = tid & 63;
+    w.wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    w.wm = w.wave / S::WGN; w.wn = w.wave % S::WGN;
+    w.half = w.lane >> 5;
+    return w;
 }
 
-template <int MT, int NT, int WGM, int WGN, int KC, int NBUF, int WPC>
-__global__ __launch_bounds__(64 * WGM * WGN, (WPC * WGM * WGN + 3) / 4) void w2d_gemm_kernel(const W2dGemmDev a) {
-    using S = W2dGemmShape<MT, NT, WGM, WGN, KC, NBUF>;
-    constexpr int NW = S::NW, M_BLK = S::M_BLK, N_BLK = S::N_BLK, XSZ = S::XSZ, BUFSZ = S::BUFSZ;
-    constexpr int NXP = S::NXP, PPW = S::PPW, NSTEP = S::NSTEP;
-    constexpr int ISTEPS = NSTEP < PPW ? NSTEP : PPW;          // k-steps of a chunk in which the pieces of a later chunk are issued
-    typedef typename W2dVec<MT>::type avec;
-    typedef typename W2dVec<NT>::type bvec;
-    __shared__ __attribute__((aligned(16))) float smem[S::LDS];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WGN, wn = wave % WGN;
-    const int half = lane >> 5;
-
-    // XCD-aware tile order (hardware deals consecutive workgroup ids round-robin to the 8 XCDs): every XCD walks ONE contiguous range of
-    // (xi, n tile, m tile) triples, m tile fastest -- the Cout tiles of the same V columns meet in one L2, and so do the tiles of one xi (its U slice).
-    const int Lt = (blockIdx.x & 7) * a.per_xcd + (blockIdx.x >> 3);
-    if (Lt >= a.ntiles) return;
+// XCD-aware tile order (hardware deals consecutive workgroup ids round-robin to the 8 XCDs): every XCD walks ONE contiguous range of
+// (plane, n tile, m tile) triples, m tile fastest -- the Cout tiles of the same V columns meet in one L2, and so do the tiles of one plane (its U slice).
+// The plane is xi, or xt for the fold kernel.  A workgroup whose index is not below a.ntiles has no tile and returns.
+struct W2dTile { int m0, n0, plane; };
+__device__ __forceinline__ int w2d_tile_index(const W2dGemmDev& a) { return (blockIdx.x & 7) * a.per_xcd + (blockIdx.x >> 3); }
+template <class S>
+__device__ __forceinline__ W2dTile w2d_tile_of(const W2dGemmDev& a, int Lt) {
+    W2dTile t;
     int rest = Lt;
     const int by = rest % a.ntm; rest /= a.ntm;
     const int bn = rest % a.ntn;
-    const int xi = rest / a.ntn;
-    const int m0 = by * M_BLK, n0 = bn * N_BLK;
+    t.plane = rest / a.ntn;
+    t.m0 = by * S::M_BLK; t.n0 = bn * S::N_BLK;
+    return t;
+}
 
-    // A piece = 1 KiB of LDS filled by one wave instruction (16 bytes per lane); per piece and lane ONE 32-bit byte offset from a wave-uniform base
-    // that advances by a scalar stride per chunk.  Columns past N (the last n tile) are clamped onto the last four real columns: every lane always
-    // loads (the per-chunk instruction count the vmcnt waits rely on is exact) and the duplicate columns are never stored.
-    unsigned poff[PPW];
-    int plds[PPW];
+// A piece = 1 KiB of LDS filled by one wave instruction (16 bytes per lane); per piece and lane ONE 32-bit byte offset from a wave-uniform base
+// that advances by a scalar stride per chunk.  Columns past N (the last n tile) are clamped onto the last four real columns: every lane always
+// loads (the per-chunk instruction count the vmcnt waits rely on is exact) and the duplicate columns are never stored.
+// CLAMP_M: a 96-channel panel on the 128-wide tile -- weight columns past Cout_pad re-read the last four (never stored).
+template <class S, bool CLAMP_M>
+__device__ __forceinline__ void w2d_piece_offsets(const W2dGemmDev& a, const int wave, const int lane, const int m0, const int n0, unsigned (&poff)[S::PPW], int (&plds)[S::PPW]) {
 #pragma unroll
-    for (int i = 0; i < PPW; ++i) {
-        const int pc = wave + i * NW;
+    for (int i = 0; i < S::PPW; ++i) {
+        const int pc = wave + i * S::NW;
         plds[i] = pc * 256;
-        if (pc < NXP) {
+        if (pc < S::NXP) {
             const int e = pc * 256 + 4 * lane;
-            const int k = e / N_BLK, nl = e % N_BLK;
+            const int k = e / S::N_BLK, nl = e % S::N_BLK;
             poff[i] = (unsigned)(4 * ((int64_t)k * a.N + min(n0 + nl, a.N - 4)));
         } else {
-            const int e = (pc - NXP) * 256 + 4 * lane;
-            const int k = e / M_BLK, col = e % M_BLK;
-            poff[i] = (unsigned)(4 * ((int64_t)k * a.Cout_pad + m0 + col));
+            const int e = (pc - S::NXP) * 256 + 4 * lane;
+            const int k = e / S::M_BLK, col = e % S::M_BLK;
+            poff[i] = (unsigned)(4 * ((int64_t)k * a.Cout_pad + (CLAMP_M ? min(m0 + col, a.Cout_pad - 4) : m0 + col)));
         }
     }
-    const int64_t xstep = (int64_t)KC * a.N * 4, wstep = (int64_t)KC * a.Cout_pad * 4;          // bytes per chunk (wave-uniform)
-    const char* const xbase = reinterpret_cast<const char*>(a.V + (int64_t)xi * a.Cin * a.N);
-    const char* const wbase = reinterpret_cast<const char*>(a.U + (int64_t)xi * a.Cin_pad * a.Cout_pad);
+}
 
-    const int vB = half * N_BLK + wn * (32 * NT) + NT * (lane & 31);
-    const int vA = XSZ + half * M_BLK + wm * (32 * MT) + MT * (lane & 31);
+// piece I of a chunk into buffer buf, from the wave-uniform base the kernel chose for it: a piece of V (w2d_piece_is_x) or of U
+template <class S, int I>
+__device__ __forceinline__ bool w2d_piece_is_x(const W2dWave& w) { return w.wave + I * S::NW < S::NXP; }          // (scalar)
+template <class S, int I>
+__device__ __forceinline__ void w2d_issue_piece(const unsigned (&poff)[S::PPW], const int (&plds)[S::PPW], const char* base, float* buf) {
+    const unsigned la = AID_LDS_ADDR(buf + plds[I]);
+    const unsigned off = poff[I];
+    AID_DMA16_SBASE(off, base, la);
+}
 
-    f32x16 acc[MT][NT];
+// float offsets within a buffer of this lane's B / A fragment row k = kh * half
+template <class S>
+__device__ __forceinline__ void w2d_frag_base(const W2dWave& w, int kh, int& vA, int& vB) {
+    vB = kh * w.half * S::N_BLK + w.wn * (32 * S::NT) + S::NT * (w.lane & 31);
+    vA = S::XSZ + kh * w.half * S::M_BLK + w.wm * (32 * S::MT) + S::MT * (w.lane & 31);
+}
+
+template <int MT, int NT>
+__device__ __forceinline__ void w2d_zero(f32x16 (&acc)[MT][NT]) {
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int j = 0; j < NT; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+}
 
-    auto issue_piece = [&](auto ic, int ch, float* buf) {
-        constexpr int i = decltype(ic)::value;
-        const char* base = (wave + i * NW < NXP) ? xbase + ch * xstep : wbase + ch * wstep;          // (scalar)
-        const unsigned la = W2D_LDS_ADDR(buf + plds[i]);
-        const unsigned off = poff[i];
-        W2D_DMA16_SBASE(off, base, la);
+// the fp32 k-steps of one chunk in buffer Bf: fragment loads one step ahead, MFMAs, and -- while `more` -- the pieces of a later chunk, one group per
+// k-step (issue(ic) issues piece ic of it)
+template <class S, class Issue>
+__device__ __forceinline__ void w2d_ksteps(const float* Bf, int vA, int vB, f32x16 (&acc)[S::MT][S::NT], bool more, Issue&& issue) {
+    constexpr int NSTEP = S::NSTEP;
+    constexpr int ISTEPS = NSTEP < S::PPW ? NSTEP : S::PPW;          // k-steps of a chunk in which the pieces of a later chunk are issued
+    typename W2dVec<S::NT>::type bv[2];
+    typename W2dVec<S::MT>::type av[2];
+    auto load_step = [&](int s, int q) {
+        bv[q] = *reinterpret_cast<const typename W2dVec<S::NT>::type*>(Bf + vB + 2 * s * S::N_BLK);
+        av[q] = *reinterpret_cast<const typename W2dVec<S::MT>::type*>(Bf + vA + 2 * s * S::M_BLK);
     };
-    auto issue_all = [&](int ch, float* buf) { w2d_static_for<PPW>([&](auto ic) { issue_piece(ic, ch, buf); }); };
-    auto issue_step = [&](auto sc, int ch, float* buf) {
-        w2d_static_for<PPW>([&](auto ic) {
-            if constexpr (decltype(sc)::value < ISTEPS && decltype(ic)::value % ISTEPS == decltype(sc)::value) issue_piece(ic, ch, buf);
+    load_step(0, 0);
+    aid_static_for<NSTEP>([&](auto sc) {
+        constexpr int s = decltype(sc)::value;
+        if (more) aid_static_for<S::PPW>([&](auto ic) {
+            if constexpr (s < ISTEPS && decltype(ic)::value % ISTEPS == s) issue(ic);
         });
-    };
-    const int nch = a.nchunks;
-    constexpr int AHEAD = NBUF - 1;
-    w2d_static_for<AHEAD>([&](auto qc) { if (decltype(qc)::value < nch) issue_all(decltype(qc)::value, smem + decltype(qc)::value * BUFSZ); });
-    __builtin_amdgcn_s_waitcnt(0);
-    __syncthreads();
-
-    auto chunk = [&](auto curc, int ch) {
-        constexpr int cur = decltype(curc)::value;
-        const float* Bf = smem + cur * BUFSZ;
-        float* Nx = smem + ((cur + AHEAD) % NBUF) * BUFSZ;      // read during the previous chunk (every wave is past that chunk's barrier)
-        const bool more = (ch + AHEAD) < nch;
-        bvec bv[2];
-        avec av[2];
-        auto load_step = [&](int s, int q) {
-            bv[q] = *reinterpret_cast<const bvec*>(Bf + vB + 2 * s * N_BLK);
-            av[q] = *reinterpret_cast<const avec*>(Bf + vA + 2 * s * M_BLK);
-        };
-        load_step(0, 0);
-        w2d_static_for<NSTEP>([&](auto sc) {
-            constexpr int s = decltype(sc)::value;
-            if (more) issue_step(sc, ch + AHEAD, Nx);
-            if (s + 1 < NSTEP) load_step(s + 1, (s + 1) & 1);
-            constexpr int q = s & 1;
+        if (s + 1 < NSTEP) load_step(s + 1, (s + 1) & 1);
+        constexpr int q = s & 1;
 #pragma unroll
-            for (int i = 0; i < MT; ++i)
+        for (int i = 0; i < S::MT; ++i)
 #pragma unroll
-                for (int j = 0; j < NT; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(w2d_get(av[q], i), w2d_get(bv[q], j), acc[i][j], 0, 0, 0);
-        });
-        asm volatile("" ::: "memory");
-        // the loads of chunk ch + 1 must have landed; with three or more buffers those issued during this chunk (PPW per wave) may stay in flight
-        if (NBUF >= 3 && more) __builtin_amdgcn_s_waitcnt(W2D_VMCNT(PPW * (AHEAD - 1)));
-        else if (NBUF >= 4 && (ch + AHEAD - 1) < nch) __builtin_amdgcn_s_waitcnt(W2D_VMCNT(PPW * (AHEAD - 2)));
-        else __builtin_amdgcn_s_waitcnt(W2D_VMCNT(0));
-        __builtin_amdgcn_s_waitcnt(W2D_LGKMCNT0);
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    };
-    for (int ch = 0; ch < nch; ch += NBUF)
-        w2d_static_for<NBUF>([&](auto qc) { if (ch + decltype(qc)::value < nch) chunk(qc, ch + decltype(qc)::value); });
+            for (int j = 0; j < S::NT; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(w2d_get(av[q], i), w2d_get(bv[q], j), acc[i][j], 0, 0, 0);
+    });
+}
 
-    // ---- epilogue: NT consecutive columns per lane and row ------------------------------------------------------------------------------
-    const int n = n0 + wn * (32 * NT) + NT * (lane & 31);
-    if (n >= a.N) return;
-    float* const cb = a.Mo + (int64_t)xi * a.Cout * a.N + n;
+// end of chunk ch of nct: its buffer is free and the next chunk's data is in LDS for every wave
+template <class S>
+__device__ __forceinline__ void w2d_chunk_wait(int ch, int nct) {
+    constexpr int NBUF = S::NBUF, AHEAD = S::AHEAD, PPW = S::PPW;
+    asm volatile("" ::: "memory");
+    // the loads of chunk ch + 1 must have landed; with three or more buffers those issued during this chunk (PPW per wave) may stay in flight
+    if (NBUF >= 3 && (ch + AHEAD) < nct) __builtin_amdgcn_s_waitcnt(AID_VMCNT(PPW * (AHEAD - 1)));
+    else if (NBUF >= 4 && (ch + AHEAD - 1) < nct) __builtin_amdgcn_s_waitcnt(AID_VMCNT(PPW * (AHEAD - 2)));
+    else __builtin_amdgcn_s_waitcnt(AID_VMCNT(0));
+    __builtin_amdgcn_s_waitcnt(AID_LGKMCNT0);
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+
+// the chunk stream over the ring of NBUF buffers: chunk(buffer index as a constant, chunk number)
+template <int NBUF, class Chunk>
+__device__ __forceinline__ void w2d_for_chunks(int nct, Chunk&& chunk) {
+    for (int ch = 0; ch < nct; ch += NBUF)
+        aid_static_for<NBUF>([&](auto qc) { if (ch + decltype(qc)::value < nct) chunk(qc, ch + decltype(qc)::value); });
+}
+
+// epilogue: the MT x 16 rows of this lane, NT consecutive columns per row, into the plane at cb (already at the lane's first column n < N)
+template <class S>
+__device__ __forceinline__ void w2d_store_tile(const W2dGemmDev& a, const W2dWave& w, const W2dTile& t, float* cb, const f32x16 (&acc)[S::MT][S::NT]) {
+    constexpr int MT = S::MT, NT = S::NT;
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int m = m0 + wm * (32 * MT) + MT * (4 * half + (r & 3) + 8 * (r >> 2)) + i;
+            const int m = t.m0 + w.wm * (32 * MT) + MT * (4 * w.half + (r & 3) + 8 * (r >> 2)) + i;
             if (m >= a.Cout) continue;
             float* q = cb + (int64_t)m * a.N;
             if constexpr (NT == 4) *reinterpret_cast<float4*>(q) = make_float4(acc[i][0][r], acc[i][1][r], acc[i][2][r], acc[i][3][r]);
             else if constexpr (NT == 2) *reinterpret_cast<float2*>(q) = make_float2(acc[i][0][r], acc[i][1][r]);
             else *q = acc[i][0][r];
         }
+}
+
+// ---- the fp32-MFMA kernel -----------------------------------------------------------------------------------------------------------------
+template <int MT, int NT, int WGM, int WGN, int KC, int NBUF, int WPC>
+__global__ __launch_bounds__(64 * WGM * WGN, (WPC * WGM * WGN + 3) / 4) void w2d_gemm_kernel(const W2dGemmDev a) {
+    using S = W2dGemmShape<MT, NT, WGM, WGN, KC, NBUF>;
+    constexpr int BUFSZ = S::BUFSZ, PPW = S::PPW, AHEAD = S::AHEAD;
+    __shared__ __attribute__((aligned(16))) float smem[S::LDS];
+    const W2dWave w = w2d_wave_of<S>();
+    const int Lt = w2d_tile_index(a);
+    if (Lt >= a.ntiles) return;
+    const W2dTile t = w2d_tile_of<S>(a, Lt);
+    const int xi = t.plane;
+    unsigned poff[PPW];
+    int plds[PPW];
+    w2d_piece_offsets<S, false>(a, w.wave, w.lane, t.m0, t.n0, poff, plds);
+    const int64_t xstep = (int64_t)KC * a.N * 4, wstep = (int64_t)KC * a.Cout_pad * 4;          // bytes per chunk (wave-uniform)
+    const char* const xbase = reinterpret_cast<const char*>(a.V + (int64_t)xi * a.Cin * a.N);
+    const char* const wbase = reinterpret_cast<const char*>(a.U + (int64_t)xi * a.Cin_pad * a.Cout_pad);
+    int vA, vB;
+    w2d_frag_base<S>(w, 1, vA, vB);
+    f32x16 acc[MT][NT];
+    w2d_zero(acc);
+
+    auto issue_piece = [&](auto ic, int ch, float* buf) {
+        constexpr int i = decltype(ic)::value;
+        w2d_issue_piece<S, i>(poff, plds, w2d_piece_is_x<S, i>(w) ? xbase + ch * xstep : wbase + ch * wstep, buf);
+    };
+    const int nch = a.nchunks;
+    aid_static_for<AHEAD>([&](auto qc) {
+        constexpr int q = decltype(qc)::value;
+        if (q < nch) aid_static_for<PPW>([&](auto ic) { issue_piece(ic, q, smem + q * BUFSZ); });
+    });
+    __builtin_amdgcn_s_waitcnt(0);
+    __syncthreads();
+    w2d_for_chunks<NBUF>(nch, [&](auto curc, int ch) {
+        constexpr int cur = decltype(curc)::value;
+        float* Nx = smem + ((cur + AHEAD) % NBUF) * BUFSZ;      // read during the previous chunk (every wave is past that chunk's barrier)
+        w2d_ksteps<S>(smem + cur * BUFSZ, vA, vB, acc, (ch + AHEAD) < nch, [&](auto ic) { issue_piece(ic, ch + AHEAD, Nx); });
+        w2d_chunk_wait<S>(ch, nch);
+    });
+
+    const int n = t.n0 + w.wn * (32 * NT) + NT * (w.lane & 31);
+    if (n >= a.N) return;
+    w2d_store_tile<S>(a, w, t, a.Mo + (int64_t)xi * a.Cout * a.N + n, acc);
 }
 
 // ---- LABELLED VARIANT (never the default, never the headline): the same batched GEMM with both fp32 operands SPLIT into three bf16
@@ -221,6 +261,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WPC * WGM * WGN + 3) / 4) void w2d
 // accumulating 16 exact products per instruction (fewer fp32 roundings of the running sum), not from exact products; the 3-product split is 6e-5: not built.
 // 6 MFMAs of 32 cycles per 16 k against 8 of 64: 0.375x the matrix-pipe time; the split is VALU work on the fragments (4 ops + 1.5 packs per value).
 // Same LDS images, same direct-to-LDS staging, one k-step of 16 per chunk: lane half h holds k = 8 h .. 8 h + 7 of BOTH fragments.
+// All pieces of the later chunk are issued at the chunk's start (there is one k-step to spread them over).
 typedef __bf16 w2d_bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned w2d_u32x4 __attribute__((ext_vector_type(4)));
 
@@ -244,76 +285,40 @@ template <int MT, int NT, int WGM, int WGN, int NBUF, int WPC>
 __global__ __launch_bounds__(64 * WGM * WGN, (WPC * WGM * WGN + 3) / 4) void w2d_gemm_s6_kernel(const W2dGemmDev a) {
     constexpr int KC = 16;
     using S = W2dGemmShape<MT, NT, WGM, WGN, KC, NBUF>;
-    constexpr int NW = S::NW, M_BLK = S::M_BLK, N_BLK = S::N_BLK, XSZ = S::XSZ, BUFSZ = S::BUFSZ;
-    constexpr int NXP = S::NXP, PPW = S::PPW;
+    constexpr int M_BLK = S::M_BLK, N_BLK = S::N_BLK, BUFSZ = S::BUFSZ, PPW = S::PPW, AHEAD = S::AHEAD;
     typedef typename W2dVec<MT>::type avec;
     typedef typename W2dVec<NT>::type bvec;
     __shared__ __attribute__((aligned(16))) float smem[S::LDS];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WGN, wn = wave % WGN;
-    const int half = lane >> 5;
-    const int Lt = (blockIdx.x & 7) * a.per_xcd + (blockIdx.x >> 3);
+    const W2dWave w = w2d_wave_of<S>();
+    const int Lt = w2d_tile_index(a);
     if (Lt >= a.ntiles) return;
-    int rest = Lt;
-    const int by = rest % a.ntm; rest /= a.ntm;
-    const int bn = rest % a.ntn;
-    const int xi = rest / a.ntn;
-    const int m0 = by * M_BLK, n0 = bn * N_BLK;
-
+    const W2dTile t = w2d_tile_of<S>(a, Lt);
+    const int xi = t.plane;
     unsigned poff[PPW];
     int plds[PPW];
-#pragma unroll
-    for (int i = 0; i < PPW; ++i) {
-        const int pc = wave + i * NW;
-        plds[i] = pc * 256;
-        if (pc < NXP) {
-            const int e = pc * 256 + 4 * lane;
-            const int k = e / N_BLK, nl = e % N_BLK;
-            poff[i] = (unsigned)(4 * ((int64_t)k * a.N + min(n0 + nl, a.N - 4)));
-        } else {
-            const int e = (pc - NXP) * 256 + 4 * lane;
-            const int k = e / M_BLK, col = e % M_BLK;
-            poff[i] = (unsigned)(4 * ((int64_t)k * a.Cout_pad + m0 + col));
-        }
-    }
+    w2d_piece_offsets<S, false>(a, w.wave, w.lane, t.m0, t.n0, poff, plds);
     const int64_t xstep = (int64_t)KC * a.N * 4, wstep = (int64_t)KC * a.Cout_pad * 4;
     const char* const xbase = reinterpret_cast<const char*>(a.V + (int64_t)xi * a.Cin * a.N);
     const char* const wbase = reinterpret_cast<const char*>(a.U + (int64_t)xi * a.Cin_pad * a.Cout_pad);
-    const int vB = (8 * half) * N_BLK + wn * (32 * NT) + NT * (lane & 31);
-    const int vA = XSZ + (8 * half) * M_BLK + wm * (32 * MT) + MT * (lane & 31);
-
+    int vA, vB;
+    w2d_frag_base<S>(w, 8, vA, vB);
     f32x16 acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    w2d_zero(acc);
 
     auto issue_all = [&](int ch, float* buf) {
-        w2d_static_for<PPW>([&](auto ic) {
+        aid_static_for<PPW>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
-            const char* base = (wave + i * NW < NXP) ? xbase + ch * xstep : wbase + ch * wstep;
-            const unsigned la = W2D_LDS_ADDR(buf + plds[i]);
-            const unsigned off = poff[i];
-            W2D_DMA16_SBASE(off, base, la);
+            w2d_issue_piece<S, i>(poff, plds, w2d_piece_is_x<S, i>(w) ? xbase + ch * xstep : wbase + ch * wstep, buf);
         });
     };
     const int nch = a.nchunks;
-    constexpr int AHEAD = NBUF - 1;
-    w2d_static_for<AHEAD>([&](auto qc) { if (decltype(qc)::value < nch) issue_all(decltype(qc)::value, smem + decltype(qc)::value * BUFSZ); });
+    aid_static_for<AHEAD>([&](auto qc) { if (decltype(qc)::value < nch) issue_all(decltype(qc)::value, smem + decltype(qc)::value * BUFSZ); });
     __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();
-
-    auto chunk = [&](auto curc, int ch) {
+    w2d_for_chunks<NBUF>(nch, [&](auto curc, int ch) {
         constexpr int cur = decltype(curc)::value;
         const float* Bf = smem + cur * BUFSZ;
-        float* Nx = smem + ((cur + AHEAD) % NBUF) * BUFSZ;
-        const bool more = (ch + AHEAD) < nch;
-        if (more) issue_all(ch + AHEAD, Nx);
+        if ((ch + AHEAD) < nch) issue_all(ch + AHEAD, smem + ((cur + AHEAD) % NBUF) * BUFSZ);
         avec av[8];
         bvec bv[8];
 #pragma unroll
@@ -345,51 +350,12 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WPC * WGM * WGN + 3) / 4) void w2d
                 acc[i][j] = c;
             }
         }
-        asm volatile("" ::: "memory");
-        if (NBUF >= 3 && more) __builtin_amdgcn_s_waitcnt(W2D_VMCNT(PPW * (AHEAD - 1)));
-        else if (NBUF >= 4 && (ch + AHEAD - 1) < nch) __builtin_amdgcn_s_waitcnt(W2D_VMCNT(PPW * (AHEAD - 2)));
-        else __builtin_amdgcn_s_waitcnt(W2D_VMCNT(0));
-        __builtin_amdgcn_s_waitcnt(W2D_LGKMCNT0);
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    };
-    for (int ch = 0; ch < nch; ch += NBUF)
-        w2d_static_for<NBUF>([&](auto qc) { if (ch + decltype(qc)::value < nch) chunk(qc, ch + decltype(qc)::value); });
+        w2d_chunk_wait<S>(ch, nch);
+    });
 
-    const int n = n0 + wn * (32 * NT) + NT * (lane & 31);
+    const int n = t.n0 + w.wn * (32 * NT) + NT * (w.lane & 31);
     if (n >= a.N) return;
-    float* const cb = a.Mo + (int64_t)xi * a.Cout * a.N + n;
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int m = m0 + wm * (32 * MT) + MT * (4 * half + (r & 3) + 8 * (r >> 2)) + i;
-            if (m >= a.Cout) continue;
-            float* q = cb + (int64_t)m * a.N;
-            if constexpr (NT == 4) *reinterpret_cast<float4*>(q) = make_float4(acc[i][0][r], acc[i][1][r], acc[i][2][r], acc[i][3][r]);
-            else if constexpr (NT == 2) *reinterpret_cast<float2*>(q) = make_float2(acc[i][0][r], acc[i][1][r]);
-            else *q = acc[i][0][r];
-        }
-}
-
-template <int MT, int NT, int WGM, int WGN, int NBUF, int WPC>
-static int w2d_launch_gemm_s6(const aid_wino2d_gemm_params* p, hipStream_t st, const char* name) {
-    using S = W2dGemmShape<MT, NT, WGM, WGN, 16, NBUF>;
-    AID_REQUIRE(p->Cin % 16 == 0, "aid_wino2d_gemm: Cin must be a multiple of the K chunk");
-    AID_REQUIRE(p->Cout_pad % S::M_BLK == 0, "aid_wino2d_gemm: Cout_pad must be a multiple of the M tile");
-    AID_REQUIRE((int64_t)p->Cin * p->N * 4 < (1LL << 32) && (int64_t)p->Cin_pad * p->Cout_pad * 4 < (1LL << 32), "aid_wino2d_gemm: one plane must stay below 4 GiB");
-    W2dGemmDev a;
-    a.U = p->U; a.V = p->V; a.Mo = p->M;
-    a.Cin = p->Cin; a.Cout = p->Cout; a.Cin_pad = p->Cin_pad; a.Cout_pad = p->Cout_pad; a.N = (int)p->N;
-    a.nchunks = p->Cin / 16;
-    a.ntn = aid_cdiv(p->N, S::N_BLK);
-    a.ntm = aid_cdiv(p->Cout, S::M_BLK);
-    a.ntiles = p->nxi * a.ntn * a.ntm;
-    a.per_xcd = aid_cdiv(a.ntiles, 8);
-    hipLaunchKernelGGL((w2d_gemm_s6_kernel<MT, NT, WGM, WGN, NBUF, WPC>), dim3((unsigned)(8 * a.per_xcd)), dim3(64 * S::NW), 0, st, a);
-    AID_CHECK_LAUNCH();
-    aid_note_kernel(name);
-    return AID_OK;
+    w2d_store_tile<S>(a, w, t, a.Mo + (int64_t)xi * a.Cout * a.N + n, acc);
 }
 
 // =====================================================================================================================================
@@ -407,116 +373,51 @@ __constant__ float w2d_atf[8][4] = {{1.f, 0.f, 0.f, 0.f}, {1.f, 1.f, 1.f, 1.f}, 
 template <int MT, int NT, int WGM, int WGN, int KC, int NBUF, int WPC>
 __global__ __launch_bounds__(64 * WGM * WGN, (WPC * WGM * WGN + 3) / 4) void w2d_gemm_fold_kernel(const W2dGemmDev a, const int ntp) {
     using S = W2dGemmShape<MT, NT, WGM, WGN, KC, NBUF>;
-    constexpr int NW = S::NW, M_BLK = S::M_BLK, N_BLK = S::N_BLK, XSZ = S::XSZ, BUFSZ = S::BUFSZ;
-    constexpr int NXP = S::NXP, PPW = S::PPW, NSTEP = S::NSTEP;
-    constexpr int ISTEPS = NSTEP < PPW ? NSTEP : PPW;
-    typedef typename W2dVec<MT>::type avec;
-    typedef typename W2dVec<NT>::type bvec;
+    constexpr int BUFSZ = S::BUFSZ, PPW = S::PPW, AHEAD = S::AHEAD;
     __shared__ __attribute__((aligned(16))) float smem[S::LDS];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WGN, wn = wave % WGN;
-    const int half = lane >> 5;
-
-    const int Lt = (blockIdx.x & 7) * a.per_xcd + (blockIdx.x >> 3);      // XCD-aware order: (xt, n tile, m tile), m fastest
+    const W2dWave w = w2d_wave_of<S>();
+    const int Lt = w2d_tile_index(a);
     if (Lt >= a.ntiles) return;
-    int rest = Lt;
-    const int by = rest % a.ntm; rest /= a.ntm;
-    const int bn = rest % a.ntn;
-    const int xt = rest / a.ntn;
-    const int m0 = by * M_BLK, n0 = bn * N_BLK;
-
+    const W2dTile t = w2d_tile_of<S>(a, Lt);                 // (xt, n tile, m tile)
+    const int xt = t.plane;
     unsigned poff[PPW];
     int plds[PPW];
-#pragma unroll
-    for (int i = 0; i < PPW; ++i) {
-        const int pc = wave + i * NW;
-        plds[i] = pc * 256;
-        if (pc < NXP) {
-            const int e = pc * 256 + 4 * lane;
-            const int k = e / N_BLK, nl = e % N_BLK;
-            poff[i] = (unsigned)(4 * ((int64_t)k * a.N + min(n0 + nl, a.N - 4)));
-        } else {
-            const int e = (pc - NXP) * 256 + 4 * lane;
-            const int k = e / M_BLK, col = e % M_BLK;
-            poff[i] = (unsigned)(4 * ((int64_t)k * a.Cout_pad + min(m0 + col, a.Cout_pad - 4)));      // a 96-channel panel on the 128-wide tile: columns past Cout_pad re-read the last four (never stored)
-        }
-    }
+    w2d_piece_offsets<S, true>(a, w.wave, w.lane, t.m0, t.n0, poff, plds);
     const int nch = a.nchunks, nct = 8 * nch;                // chunks per plane, chunks of the whole stream
     const int64_t xstep = (int64_t)KC * a.N * 4, wstep = (int64_t)KC * a.Cout_pad * 4;          // bytes per chunk
     const int64_t xplane = (int64_t)ntp * a.Cin * a.N * 4, wplane = (int64_t)ntp * a.Cin_pad * a.Cout_pad * 4;      // bytes from plane (xf, xt) to (xf + 1, xt)
     const char* const xbase = reinterpret_cast<const char*>(a.V + (int64_t)xt * a.Cin * a.N);
     const char* const wbase = reinterpret_cast<const char*>(a.U + (int64_t)xt * a.Cin_pad * a.Cout_pad);
-
-    const int vB = half * N_BLK + wn * (32 * NT) + NT * (lane & 31);
-    const int vA = XSZ + half * M_BLK + wm * (32 * MT) + MT * (lane & 31);
-
+    int vA, vB;
+    w2d_frag_base<S>(w, 1, vA, vB);
     f32x16 acc[MT][NT];
     f32x16 Y[4][MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { acc[i][j][r] = 0.f; Y[0][i][j][r] = 0.f; Y[1][i][j][r] = 0.f; Y[2][i][j][r] = 0.f; Y[3][i][j][r] = 0.f; }
+    w2d_zero(acc); w2d_zero(Y[0]); w2d_zero(Y[1]); w2d_zero(Y[2]); w2d_zero(Y[3]);
 
-    auto issue_piece = [&](auto ic, const char* xs, const char* ws, float* buf) {
-        constexpr int i = decltype(ic)::value;
-        const char* base = (wave + i * NW < NXP) ? xs : ws;          // (scalar)
-        const unsigned la = W2D_LDS_ADDR(buf + plds[i]);
-        const unsigned off = poff[i];
-        W2D_DMA16_SBASE(off, base, la);
-    };
     auto src_of = [&](int c, const char*& xs, const char*& ws) {      // (scalar) sources of stream chunk c
         const int xf = c / nch, kc = c - xf * nch;
         xs = xbase + xf * xplane + kc * xstep;
         ws = wbase + xf * wplane + kc * wstep;
     };
-    constexpr int AHEAD = NBUF - 1;
-    w2d_static_for<AHEAD>([&](auto qc) {
+    auto issue_piece = [&](auto ic, const char* xs, const char* ws, float* buf) {
+        constexpr int i = decltype(ic)::value;
+        w2d_issue_piece<S, i>(poff, plds, w2d_piece_is_x<S, i>(w) ? xs : ws, buf);
+    };
+    aid_static_for<AHEAD>([&](auto qc) {
         const char *xs, *ws;
         src_of(decltype(qc)::value, xs, ws);
-        w2d_static_for<PPW>([&](auto ic) { issue_piece(ic, xs, ws, smem + decltype(qc)::value * BUFSZ); });
+        aid_static_for<PPW>([&](auto ic) { issue_piece(ic, xs, ws, smem + decltype(qc)::value * BUFSZ); });
     });
     __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();
-
-    auto chunk = [&](auto curc, int ch) {
+    w2d_for_chunks<NBUF>(nct, [&](auto curc, int ch) {
         constexpr int cur = decltype(curc)::value;
-        const float* Bf = smem + cur * BUFSZ;
         float* Nx = smem + ((cur + AHEAD) % NBUF) * BUFSZ;
         const bool more = (ch + AHEAD) < nct;
         const char *xs = xbase, *ws = wbase;
         if (more) src_of(ch + AHEAD, xs, ws);
-        bvec bv[2];
-        avec av[2];
-        auto load_step = [&](int s_, int q) {
-            bv[q] = *reinterpret_cast<const bvec*>(Bf + vB + 2 * s_ * N_BLK);
-            av[q] = *reinterpret_cast<const avec*>(Bf + vA + 2 * s_ * M_BLK);
-        };
-        load_step(0, 0);
-        w2d_static_for<NSTEP>([&](auto sc) {
-            constexpr int s_ = decltype(sc)::value;
-            if (more) w2d_static_for<PPW>([&](auto ic) {
-                if constexpr (s_ < ISTEPS && decltype(ic)::value % ISTEPS == s_) issue_piece(ic, xs, ws, Nx);
-            });
-            if (s_ + 1 < NSTEP) load_step(s_ + 1, (s_ + 1) & 1);
-            constexpr int q = s_ & 1;
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < NT; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(w2d_get(av[q], i), w2d_get(bv[q], j), acc[i][j], 0, 0, 0);
-        });
-        asm volatile("" ::: "memory");
-        if (NBUF >= 3 && more) __builtin_amdgcn_s_waitcnt(W2D_VMCNT(PPW * (AHEAD - 1)));
-        else if (NBUF >= 4 && (ch + AHEAD - 1) < nct) __builtin_amdgcn_s_waitcnt(W2D_VMCNT(PPW * (AHEAD - 2)));
-        else __builtin_amdgcn_s_waitcnt(W2D_VMCNT(0));
-        __builtin_amdgcn_s_waitcnt(W2D_LGKMCNT0);
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        w2d_ksteps<S>(smem + cur * BUFSZ, vA, vB, acc, more, [&](auto ic) { issue_piece(ic, xs, ws, Nx); });
+        w2d_chunk_wait<S>(ch, nct);
         const int xf = ch / nch;
         if (ch - xf * nch == nch - 1) {                       // (wave-uniform) the K loop of plane xf is complete: fold it into the four output rows
             const float c0 = w2d_atf[xf][0], c1 = w2d_atf[xf][1], c2 = w2d_atf[xf][2], c3 = w2d_atf[xf][3];
@@ -531,47 +432,54 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WPC * WGM * WGN + 3) / 4) void w2d
                         acc[i][j][r] = 0.f;
                     }
         }
-    };
-    for (int ch = 0; ch < nct; ch += NBUF)
-        w2d_static_for<NBUF>([&](auto qc) { if (ch + decltype(qc)::value < nct) chunk(qc, ch + decltype(qc)::value); });
+    });
 
     // ---- epilogue: the four output-row planes j * ntp + xt ---------------------------------------------------------------------------------
-    const int n = n0 + wn * (32 * NT) + NT * (lane & 31);
+    const int n = t.n0 + w.wn * (32 * NT) + NT * (w.lane & 31);
     if (n >= a.N) return;
 #pragma unroll
-    for (int jr = 0; jr < 4; ++jr) {
-        float* const cb = a.Mo + (int64_t)(jr * ntp + xt) * a.Cout * a.N + n;
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm * (32 * MT) + MT * (4 * half + (r & 3) + 8 * (r >> 2)) + i;
-                if (m >= a.Cout) continue;
-                float* q = cb + (int64_t)m * a.N;
-                if constexpr (NT == 4) *reinterpret_cast<float4*>(q) = make_float4(Y[jr][i][0][r], Y[jr][i][1][r], Y[jr][i][2][r], Y[jr][i][3][r]);
-                else if constexpr (NT == 2) *reinterpret_cast<float2*>(q) = make_float2(Y[jr][i][0][r], Y[jr][i][1][r]);
-                else *q = Y[jr][i][0][r];
-            }
-    }
+    for (int jr = 0; jr < 4; ++jr) w2d_store_tile<S>(a, w, t, a.Mo + (int64_t)(jr * ntp + xt) * a.Cout * a.N + n, Y[jr]);
 }
 
-template <int MT, int NT, int WGM, int WGN, int KC, int NBUF, int WPC>
-static int w2d_launch_gemm_fold(const aid_wino2d_gemm_params* p, int ntp, hipStream_t st, const char* name) {
-    using S = W2dGemmShape<MT, NT, WGM, WGN, KC, NBUF>;
-    AID_REQUIRE(p->Cin % KC == 0 && p->Cout_pad % 32 == 0 && p->nxi == 8 * ntp, "w2d gemm (folded): Cin % KC, Cout_pad % 32, nxi = 8 ntp");
-    AID_REQUIRE((int64_t)p->Cin * p->N * 4 * p->nxi < (1LL << 40) && (int64_t)p->Cin * p->N * 4 < (1LL << 32), "w2d gemm (folded): plane size");
+// ---- the host launcher of all three: validate, fill W2dGemmDev, launch.  planes = what the grid walks (nxi; ntp for the fold kernel, which takes it as
+// its second argument and has its own conditions)
+template <class S, bool FOLD, class Kern>
+static int w2d_launch(Kern kern, const aid_wino2d_gemm_params* p, int planes, hipStream_t st, const char* name) {
+    if constexpr (FOLD) {
+        AID_REQUIRE(p->Cin % S::KC == 0 && p->Cout_pad % 32 == 0 && p->nxi == 8 * planes, "w2d gemm (folded): Cin % KC, Cout_pad % 32, nxi = 8 ntp");
+        AID_REQUIRE((int64_t)p->Cin * p->N * 4 * p->nxi < (1LL << 40) && (int64_t)p->Cin * p->N * 4 < (1LL << 32), "w2d gemm (folded): plane size");
+    } else {
+        AID_REQUIRE(p->Cin % S::KC == 0, "aid_wino2d_gemm: Cin must be a multiple of the K chunk");
+        AID_REQUIRE(p->Cout_pad % S::M_BLK == 0, "aid_wino2d_gemm: Cout_pad must be a multiple of the M tile");
+        AID_REQUIRE((int64_t)p->Cin * p->N * 4 < (1LL << 32) && (int64_t)p->Cin_pad * p->Cout_pad * 4 < (1LL << 32), "aid_wino2d_gemm: one plane must stay below 4 GiB");
+    }
     W2dGemmDev a;
     a.U = p->U; a.V = p->V; a.Mo = p->M;
     a.Cin = p->Cin; a.Cout = p->Cout; a.Cin_pad = p->Cin_pad; a.Cout_pad = p->Cout_pad; a.N = (int)p->N;
-    a.nchunks = p->Cin / KC;
+    a.nchunks = p->Cin / S::KC;
     a.ntn = aid_cdiv(p->N, S::N_BLK);
     a.ntm = aid_cdiv(p->Cout, S::M_BLK);
-    a.ntiles = ntp * a.ntn * a.ntm;
+    a.ntiles = planes * a.ntn * a.ntm;
     a.per_xcd = aid_cdiv(a.ntiles, 8);
-    hipLaunchKernelGGL((w2d_gemm_fold_kernel<MT, NT, WGM, WGN, KC, NBUF, WPC>), dim3((unsigned)(8 * a.per_xcd)), dim3(64 * S::NW), 0, st, a, ntp);
+    const dim3 grid((unsigned)(8 * a.per_xcd)), block(64 * S::NW);
+    if constexpr (FOLD) hipLaunchKernelGGL(kern, grid, block, 0, st, a, planes);
+    else hipLaunchKernelGGL(kern, grid, block, 0, st, a);
     AID_CHECK_LAUNCH();
     aid_note_kernel(name);
     return AID_OK;
+}
+template <int MT, int NT, int WGM, int WGN, int KC, int NBUF, int WPC>
+static int w2d_launch_gemm(const aid_wino2d_gemm_params* p, hipStream_t st, const char* name, const char* name8 = nullptr) {
+    // (bench.py prices the launch by the form: 48 planes = 1/5, 80 planes = 1/6 of the direct-form FLOPs)
+    return w2d_launch<W2dGemmShape<MT, NT, WGM, WGN, KC, NBUF>, false>(w2d_gemm_kernel<MT, NT, WGM, WGN, KC, NBUF, WPC>, p, p->nxi, st, (name8 && p->nxi == 80) ? name8 : name);
+}
+template <int MT, int NT, int WGM, int WGN, int NBUF, int WPC>
+static int w2d_launch_gemm_s6(const aid_wino2d_gemm_params* p, hipStream_t st, const char* name) {
+    return w2d_launch<W2dGemmShape<MT, NT, WGM, WGN, 16, NBUF>, false>(w2d_gemm_s6_kernel<MT, NT, WGM, WGN, NBUF, WPC>, p, p->nxi, st, name);
+}
+template <int MT, int NT, int WGM, int WGN, int KC, int NBUF, int WPC>
+static int w2d_launch_gemm_fold(const aid_wino2d_gemm_params* p, int ntp, hipStream_t st, const char* name) {
+    return w2d_launch<W2dGemmShape<MT, NT, WGM, WGN, KC, NBUF>, true>(w2d_gemm_fold_kernel<MT, NT, WGM, WGN, KC, NBUF, WPC>, p, ntp, st, name);
 }
 
 // the split-precision variant as a process-wide switch of aid_conv2d(x_wino = 3) (0: the fp32-MFMA product kernel; 6: the six-product bf16 split): set
@@ -580,27 +488,6 @@ static int g_w2d_split = 0;
 extern "C" int aid_wino2d_set_split(int pieces) {
     AID_REQUIRE(pieces == 0 || pieces == 6, "aid_wino2d_set_split: 0 (fp32 MFMA) or 6 (six bf16 products per fp32 product)");
     g_w2d_split = pieces;
-    return AID_OK;
-}
-
-template <int MT, int NT, int WGM, int WGN, int KC, int NBUF, int WPC>
-static int w2d_launch_gemm(const aid_wino2d_gemm_params* p, hipStream_t st, const char* name, const char* name8 = nullptr) {
-    if (!name8) name8 = name;
-    using S = W2dGemmShape<MT, NT, WGM, WGN, KC, NBUF>;
-    AID_REQUIRE(p->Cin % KC == 0, "aid_wino2d_gemm: Cin must be a multiple of the K chunk");
-    AID_REQUIRE(p->Cout_pad % S::M_BLK == 0, "aid_wino2d_gemm: Cout_pad must be a multiple of the M tile");
-    AID_REQUIRE((int64_t)p->Cin * p->N * 4 < (1LL << 32) && (int64_t)p->Cin_pad * p->Cout_pad * 4 < (1LL << 32), "aid_wino2d_gemm: one plane must stay below 4 GiB");
-    W2dGemmDev a;
-    a.U = p->U; a.V = p->V; a.Mo = p->M;
-    a.Cin = p->Cin; a.Cout = p->Cout; a.Cin_pad = p->Cin_pad; a.Cout_pad = p->Cout_pad; a.N = (int)p->N;
-    a.nchunks = p->Cin / KC;
-    a.ntn = aid_cdiv(p->N, S::N_BLK);
-    a.ntm = aid_cdiv(p->Cout, S::M_BLK);
-    a.ntiles = p->nxi * a.ntn * a.ntm;
-    a.per_xcd = aid_cdiv(a.ntiles, 8);
-    hipLaunchKernelGGL((w2d_gemm_kernel<MT, NT, WGM, WGN, KC, NBUF, WPC>), dim3((unsigned)(8 * a.per_xcd)), dim3(64 * S::NW), 0, st, a);
-    AID_CHECK_LAUNCH();
-    aid_note_kernel(p->nxi == 80 ? name8 : name);          // (bench.py prices the launch by the form: 48 planes = 1/5, 80 planes = 1/6 of the direct-form FLOPs)
     return AID_OK;
 }
 
@@ -867,6 +754,16 @@ struct W2dOutDev {
 #define W2D_GP8_TWO 0
 #endif
 static inline int w2d_gp(int TF, int TG) { return TF == 4 ? 2 : ((W2D_GP8_TWO > 0 && TG >= W2D_GP8_TWO && (TG % 2) == 0) ? 2 : 1); }
+static inline int w2d_nblk(int NB, int gp) { return (NB + 256 * gp - 1) / (256 * gp); }      // blocks of 256 threads x GP positions per sample and channel
+// What a launch of shape (B, F, T, dil) on T form TF is made of: planes, geometry, the output pass's groups per thread and blocks.
+// fold (the GEMM folds the row axis, w2d_fold_m) depends on the channels too: set by w2d_plan_of for an aid_conv2d call.
+struct W2dPlan { int TF, NTP; W2dGeo ge; int gp, nblk; bool fold; };
+static inline W2dPlan w2d_plan(int B, int F, int T, int dil, int TF) {
+    W2dPlan pl;
+    pl.TF = TF; pl.NTP = TF + 2; pl.ge = w2d_geo(B, F, T, dil, TF);
+    pl.gp = w2d_gp(TF, pl.ge.TG); pl.nblk = w2d_nblk(pl.ge.NB, pl.gp); pl.fold = false;
+    return pl;
+}
 // FOLD: M holds the 4 NTP planes j * NTP + xt the folded GEMM wrote (w2d_gemm_fold_kernel): only the T transform is left.
 template <int TF, int GP, bool FOLD>
 __global__ __launch_bounds__(256) void w2d_output_kernel(const W2dOutDev a) {
@@ -1016,8 +913,6 @@ __global__ __launch_bounds__(256) void w2d_output_kernel(const W2dOutDev a) {
     }
 }
 
-static inline int w2d_nblk(int NB, int TF, int TG) { return (NB + 256 * w2d_gp(TF, TG) - 1) / (256 * w2d_gp(TF, TG)); }      // blocks of 256 threads x GP positions per sample and channel
-
 extern "C" int aid_conv2d_wino2d_supported(int Cin, int Cout, int F, int T, int dilF) { return w2d_shape_ok(Cin, Cout, F, T, dilF) ? 1 : 0; }
 // Which launches take the 2-D form instead of the fused 1-D kernels.  Measured per layer (tools/w2d_probe.py layer, profiles/r05_w2d_passes_ab.txt,
 // the three passes together against the fused F(8,3) / F(4,3) kernel with its pre-pass):
@@ -1042,10 +937,9 @@ extern "C" int aid_conv2d_wino2d_wanted(int B, int Cin, int Cout, int F, int T, 
     if (T <= 256) return 1;
     return (int64_t)B * F * T <= 2 * 65536 ? 1 : 0;
 }
-extern "C" int aid_conv2d_wino2d_wanted(int B, int Cin, int Cout, int F, int T, int dilF);
 extern "C" int64_t aid_conv2d_wino2d_positions(int B, int F, int T, int dilF) { return (dilF >= 1 && F % dilF == 0 && T % 4 == 0) ? w2d_geo(B, F, T, dilF).N : 0; }
 // per-(sample, group) partial count of stat_ws / dot_ws for x_wino = 3
-int aid_w2d_partials(int Cout, int F, int T, int dilF, int TF) { const W2dGeo g = w2d_geo(1, F, T, dilF, TF); return (Cout >> 3) * w2d_nblk(g.NB, TF, g.TG); }
+int aid_w2d_partials(int Cout, int F, int T, int dilF, int TF) { return (Cout >> 3) * w2d_plan(1, F, T, dilF, TF).nblk; }
 
 // Which T form the 2-D form of a launch should take: 0 = the launch is not for the 2-D form at all (aid_conv2d_wino2d_wanted == 0), 4 = F(4,5) x F(4,3)
 // (x_wino = 3, 48 planes), 8 = F(4,5) x F(8,3) (x_wino = 4, 80 planes: 2.5 instead of 3.0 products per output and 2.5 x instead of 3 x the activation in V / M).
@@ -1060,29 +954,6 @@ extern "C" int aid_conv2d_wino2d_tform(int B, int Cin, int Cout, int F, int T, i
 }
 
 // aid_conv2d with x_wino = 3: x.p = V [48][Cin][N], wp_wino = U [48][Cin_pad][Cout_pad], ws = scratch for M [48][Cout][N]
-static int w2d_check(const aid_conv2d_params* p) {
-    const int TF = w2d_tf_of(p->x_wino), NXI = 8 * (TF + 2);
-    AID_REQUIRE(p->KH == 5 && p->KW == 3 && p->wp_wino && p->wino_taps == NXI, "aid_conv2d(x_wino=3|4): needs the 48- / 80-plane pack (aid_pack_conv_weight wpw2 / wpw3)");
-    AID_REQUIRE(w2d_shape_ok(p->Cin, p->Cout, p->F, p->T, p->dilF), "aid_conv2d(x_wino=3): shape not supported (aid_conv2d_wino2d_supported)");
-    AID_REQUIRE(!p->in_scale && p->act == 0 && !p->x2.p, "aid_conv2d(x_wino=3): no in-kernel prologue, no x2");
-    if (p->fin_mode) {                                       // the last block of a sample folds the partials (aid_conv2d_fin_supported(.., 3) == 1)
-        AID_REQUIRE(p->fin_mode == 1 || p->fin_mode == 2, "aid_conv2d: fin_mode is 0, 1 or 2");
-        AID_REQUIRE(p->fin_count && p->fin_scale && (p->Cout % 8) == 0, "aid_conv2d: fin_mode needs fin_count, fin_scale and Cout % 8 == 0");
-        if (p->fin_mode == 1) AID_REQUIRE(p->stat_ws && p->fin_gamma, "aid_conv2d: fin_mode = 1 folds the stat_ws partials and needs fin_gamma");
-        else AID_REQUIRE(p->dot_ws && p->fin_stats, "aid_conv2d: fin_mode = 2 folds the dot_ws partials and needs the forward statistics in fin_stats");
-    }
-    AID_REQUIRE(!(p->stat_ws && p->dot_ws), "aid_conv2d(x_wino=3): stat_ws and dot_ws are exclusive");
-    AID_REQUIRE(!p->dot_ws || p->epi == 1, "aid_conv2d(x_wino=3): dot_ws goes with the dGELU epilogue");
-    const W2dGeo ge = w2d_geo(p->B, p->F, p->T, p->dilF, TF);
-    AID_REQUIRE(p->ws && p->ws_bytes >= (int64_t)NXI * p->Cout * ge.N * 4 && (((uintptr_t)p->ws) & 15) == 0, "aid_conv2d(x_wino=3|4): ws must hold 48 (80) * Cout * N floats");
-    AID_REQUIRE((p->y.sB % 4) == 0 && (p->y.sC % 4) == 0 && (p->y.sF % 4) == 0 && (((uintptr_t)p->y.p) & 15) == 0, "aid_conv2d(x_wino=3): 16-byte aligned output rows");
-    AID_REQUIRE(!p->res.p || ((p->res.sB % 4) == 0 && (p->res.sC % 4) == 0 && (p->res.sF % 4) == 0 && (((uintptr_t)p->res.p) & 15) == 0), "aid_conv2d(x_wino=3): 16-byte aligned residual rows");
-    AID_REQUIRE(!p->aux.p || ((p->aux.sB % 4) == 0 && (p->aux.sC % 4) == 0 && (p->aux.sF % 4) == 0 && (((uintptr_t)p->aux.p) & 15) == 0), "aid_conv2d(x_wino=3): 16-byte aligned aux rows");
-    const int npart = aid_w2d_partials(p->Cout, p->F, p->T, p->dilF, TF);
-    AID_REQUIRE(!p->stat_ws || p->stat_n == npart, "aid_conv2d(x_wino=3): stat_n != aid_conv2d_stat_partials()");
-    AID_REQUIRE(!p->dot_ws || p->dot_n == npart, "aid_conv2d(x_wino=3): dot_n != aid_conv2d_dot_partials()");
-    return AID_OK;
-}
 // Which launches fold the row-axis output transform into the GEMM (M' with 4 NTP planes): the HBM-bound ones -- Cin <= 128 on the 80-plane form.
 // A function of the layer shape; the GEMM and the output pass of a launch both ask it.  (W2D_FOLD_M = 0: never -- experiment builds for the A/B.)
 #ifndef W2D_FOLD_M
@@ -1105,23 +976,53 @@ static int w2d_check(const aid_conv2d_params* p) {
 #endif
 #define W2D_STR2(x) #x
 #define W2D_STR(x) W2D_STR2(x)
-static inline bool w2d_fold_m(const aid_conv2d_params* p) {
+static_assert(!(W2D_GP8_TWO > 0 && W2D_FOLD_M), "W2D_GP8_TWO and W2D_FOLD_M: the folded output pass takes one group per thread (build the two-group experiment with -DW2D_FOLD_M=0)");
+static inline bool w2d_fold_m(const aid_conv2d_params* p, const W2dGeo& ge) {      // ge: the launch's geometry (x_wino == 4: groups of eight)
     if (!(W2D_FOLD_M && p->x_wino == 4 && p->Cin <= W2D_FOLD_MAX_CIN && (p->Cin % 16) == 0 && ((p->Cout_pad % 128) == 0 || (p->Cout_pad % 96) == 0))) return false;
     // the folded GEMM has an eighth of the workgroups (each walks eight planes) on 64-column tiles: it needs a launch that still fills the chip a few times --
     // per layer it wins 4-9 % at >= 1280 workgroups (level 3 at the product's sub-batch of four), ties at 800 and loses 10-50 % below 650 (batch 1;
     // profiles/r06_w2d_foldm_layer_ab.txt); end to end (profiles/r06_w2d_foldm_threshold_ab.txt, configs[1], alternating runs): no fold 61.48 / 61.52,
     // threshold 1900 61.63 / 61.41, 1024 62.38 / 62.04, 768 62.89 / 62.55 evaluations/s; batch 1 / 2 and configs[4] unchanged under 768
-    const W2dGeo ge = w2d_geo(p->B, p->F, p->T, p->dilF, 8);
     const int64_t wgs = (int64_t)10 * aid_cdiv(ge.N, 64) * aid_cdiv(p->Cout, 128);
     return wgs >= W2D_FOLD_MIN_WGS;
 }
-static int w2d_gemm_of(const aid_conv2d_params* p, hipStream_t st) {
-    const int TF = w2d_tf_of(p->x_wino);
-    const W2dGeo ge = w2d_geo(p->B, p->F, p->T, p->dilF, TF);
+// The launch decision of one aid_conv2d(x_wino = 3 | 4) call, made once (by w2d_check, AFTER it has found the shape valid: the geometry divides by dilF);
+// the checks, the GEMM, the output pass and the partial count all read it.
+static inline W2dPlan w2d_plan_of(const aid_conv2d_params* p) {
+    W2dPlan pl = w2d_plan(p->B, p->F, p->T, p->dilF, w2d_tf_of(p->x_wino));
+    pl.fold = w2d_fold_m(p, pl.ge);
+    return pl;
+}
+
+// validates the call and, once the shape is known to be valid, makes its plan
+static int w2d_check(const aid_conv2d_params* p, W2dPlan& pl) {
+    const int NXI = 8 * (w2d_tf_of(p->x_wino) + 2);
+    AID_REQUIRE(p->KH == 5 && p->KW == 3 && p->wp_wino && p->wino_taps == NXI, "aid_conv2d(x_wino=3|4): needs the 48- / 80-plane pack (aid_pack_conv_weight wpw2 / wpw3)");
+    AID_REQUIRE(w2d_shape_ok(p->Cin, p->Cout, p->F, p->T, p->dilF), "aid_conv2d(x_wino=3): shape not supported (aid_conv2d_wino2d_supported)");
+    pl = w2d_plan_of(p);
+    AID_REQUIRE(!p->in_scale && p->act == 0 && !p->x2.p, "aid_conv2d(x_wino=3): no in-kernel prologue, no x2");
+    if (p->fin_mode) {                                       // the last block of a sample folds the partials (aid_conv2d_fin_supported(.., 3) == 1)
+        AID_REQUIRE(p->fin_mode == 1 || p->fin_mode == 2, "aid_conv2d: fin_mode is 0, 1 or 2");
+        AID_REQUIRE(p->fin_count && p->fin_scale && (p->Cout % 8) == 0, "aid_conv2d: fin_mode needs fin_count, fin_scale and Cout % 8 == 0");
+        if (p->fin_mode == 1) AID_REQUIRE(p->stat_ws && p->fin_gamma, "aid_conv2d: fin_mode = 1 folds the stat_ws partials and needs fin_gamma");
+        else AID_REQUIRE(p->dot_ws && p->fin_stats, "aid_conv2d: fin_mode = 2 folds the dot_ws partials and needs the forward statistics in fin_stats");
+    }
+    AID_REQUIRE(!(p->stat_ws && p->dot_ws), "aid_conv2d(x_wino=3): stat_ws and dot_ws are exclusive");
+    AID_REQUIRE(!p->dot_ws || p->epi == 1, "aid_conv2d(x_wino=3): dot_ws goes with the dGELU epilogue");
+    AID_REQUIRE(p->ws && p->ws_bytes >= (int64_t)NXI * p->Cout * pl.ge.N * 4 && (((uintptr_t)p->ws) & 15) == 0, "aid_conv2d(x_wino=3|4): ws must hold 48 (80) * Cout * N floats");
+    AID_REQUIRE((p->y.sB % 4) == 0 && (p->y.sC % 4) == 0 && (p->y.sF % 4) == 0 && (((uintptr_t)p->y.p) & 15) == 0, "aid_conv2d(x_wino=3): 16-byte aligned output rows");
+    AID_REQUIRE(!p->res.p || ((p->res.sB % 4) == 0 && (p->res.sC % 4) == 0 && (p->res.sF % 4) == 0 && (((uintptr_t)p->res.p) & 15) == 0), "aid_conv2d(x_wino=3): 16-byte aligned residual rows");
+    AID_REQUIRE(!p->aux.p || ((p->aux.sB % 4) == 0 && (p->aux.sC % 4) == 0 && (p->aux.sF % 4) == 0 && (((uintptr_t)p->aux.p) & 15) == 0), "aid_conv2d(x_wino=3): 16-byte aligned aux rows");
+    const int npart = (p->Cout >> 3) * pl.nblk;          // = aid_w2d_partials()
+    AID_REQUIRE(!p->stat_ws || p->stat_n == npart, "aid_conv2d(x_wino=3): stat_n != aid_conv2d_stat_partials()");
+    AID_REQUIRE(!p->dot_ws || p->dot_n == npart, "aid_conv2d(x_wino=3): dot_n != aid_conv2d_dot_partials()");
+    return AID_OK;
+}
+static int w2d_gemm_of(const aid_conv2d_params* p, const W2dPlan& pl, hipStream_t st) {
     aid_wino2d_gemm_params gp;
     gp.U = p->wp_wino; gp.V = p->x.p; gp.M = p->ws;
-    gp.nxi = 8 * (TF + 2); gp.Cin = p->Cin; gp.Cout = p->Cout; gp.Cin_pad = p->Cin_pad; gp.Cout_pad = p->Cout_pad; gp.N = ge.N; gp.variant = 0;
-    if (w2d_fold_m(p)) {
+    gp.nxi = 8 * pl.NTP; gp.Cin = p->Cin; gp.Cout = p->Cout; gp.Cin_pad = p->Cin_pad; gp.Cout_pad = p->Cout_pad; gp.N = pl.ge.N; gp.variant = 0;
+    if (pl.fold) {
         AID_REQUIRE((gp.N % 4) == 0, "aid_conv2d(x_wino=4): N % 4 == 0");
         // The instances (profiles/r06_w2d_fold_tiles_ab.txt, per launch in the evaluation): 128-channel panels on four waves x (32 x 64), K chunks of 32 where Cin allows
         // (276 -> 264 us against chunks of 16: half the barriers; more buffers of 16 measured nothing, the loads are not what it waits for); 96-channel panels on THREE
@@ -1129,46 +1030,50 @@ static int w2d_gemm_of(const aid_conv2d_params* p, hipStream_t st) {
         // of its columns clamped and 500 on two waves x (96 x 32).  Other Cin (multiples of 16) keep the four-wave instance with chunks of 16.
         const bool p96 = (p->Cout_pad % 128) != 0;
         if (p96 && (p->Cin % W2D_FOLD96_KC) == 0)
-            return w2d_launch_gemm_fold<1, 2, 3, 1, W2D_FOLD96_KC, W2D_FOLD96_NBUF, W2D_FOLD_WPC>(&gp, TF + 2, st, "w2d_gemm_kernel<96x64,foldM,kc" W2D_STR(W2D_FOLD96_KC) ",nb" W2D_STR(W2D_FOLD96_NBUF) ">+t8");
+            return w2d_launch_gemm_fold<1, 2, 3, 1, W2D_FOLD96_KC, W2D_FOLD96_NBUF, W2D_FOLD_WPC>(&gp, pl.NTP, st, "w2d_gemm_kernel<96x64,foldM,kc" W2D_STR(W2D_FOLD96_KC) ",nb" W2D_STR(W2D_FOLD96_NBUF) ">+t8");
         if ((p->Cin % 32) == 0)
-            return w2d_launch_gemm_fold<1, 2, 4, 1, 32, 3, W2D_FOLD_WPC>(&gp, TF + 2, st, p96 ? "w2d_gemm_kernel<128x64(96),foldM,kc32,nb3>+t8" : "w2d_gemm_kernel<128x64,foldM,kc32,nb3>+t8");
-        return w2d_launch_gemm_fold<1, 2, 4, 1, 16, 3, W2D_FOLD_WPC>(&gp, TF + 2, st, p96 ? "w2d_gemm_kernel<128x64(96),foldM,kc16,nb3>+t8" : "w2d_gemm_kernel<128x64,foldM,kc16,nb3>+t8");
+            return w2d_launch_gemm_fold<1, 2, 4, 1, 32, 3, W2D_FOLD_WPC>(&gp, pl.NTP, st, p96 ? "w2d_gemm_kernel<128x64(96),foldM,kc32,nb3>+t8" : "w2d_gemm_kernel<128x64,foldM,kc32,nb3>+t8");
+        return w2d_launch_gemm_fold<1, 2, 4, 1, 16, 3, W2D_FOLD_WPC>(&gp, pl.NTP, st, p96 ? "w2d_gemm_kernel<128x64(96),foldM,kc16,nb3>+t8" : "w2d_gemm_kernel<128x64,foldM,kc16,nb3>+t8");
     }
     return aid_wino2d_gemm(&gp, st);
 }
-static int w2d_output_of(const aid_conv2d_params* p, hipStream_t st) {
-    const int TF = w2d_tf_of(p->x_wino);
-    const W2dGeo ge = w2d_geo(p->B, p->F, p->T, p->dilF, TF);
+static int w2d_output_of(const aid_conv2d_params* p, const W2dPlan& pl, hipStream_t st) {
+    const W2dGeo& ge = pl.ge;
     W2dOutDev a;
     a.p = *p; a.M = p->ws;
-    a.R = ge.R; a.J = ge.J; a.TG = ge.TG; a.NB = ge.NB; a.N = ge.N; a.nblk = w2d_nblk(ge.NB, TF, ge.TG);
+    a.R = ge.R; a.J = ge.J; a.TG = ge.TG; a.NB = ge.NB; a.N = ge.N; a.nblk = pl.nblk;
     a.fin_total = p->Cout * a.nblk;
     const dim3 grid((unsigned)((int64_t)p->B * p->Cout * a.nblk));
-    if (TF == 8 && w2d_gp(8, ge.TG) == 2) hipLaunchKernelGGL((w2d_output_kernel<8, 2, false>), grid, dim3(256), 0, st, a);
-    else if (TF == 8 && w2d_fold_m(p)) hipLaunchKernelGGL((w2d_output_kernel<8, 1, true>), grid, dim3(256), 0, st, a);
-    else if (TF == 8) hipLaunchKernelGGL((w2d_output_kernel<8, 1, false>), grid, dim3(256), 0, st, a);
+    if (pl.TF == 8 && pl.fold) hipLaunchKernelGGL((w2d_output_kernel<8, 1, true>), grid, dim3(256), 0, st, a);
+#if W2D_GP8_TWO > 0          // (experiment builds only: the two-group instance carries 240 registers)
+    else if (pl.TF == 8 && pl.gp == 2) hipLaunchKernelGGL((w2d_output_kernel<8, 2, false>), grid, dim3(256), 0, st, a);
+#endif
+    else if (pl.TF == 8) hipLaunchKernelGGL((w2d_output_kernel<8, 1, false>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((w2d_output_kernel<4, 2, false>), grid, dim3(256), 0, st, a);
     AID_CHECK_LAUNCH();
     return AID_OK;
 }
 int aid_conv53_wino2d(const aid_conv2d_params* p, hipStream_t st) {
-    int rc = w2d_check(p);
+    W2dPlan pl;
+    int rc = w2d_check(p, pl);
     if (rc != AID_OK) return rc;
-    rc = w2d_gemm_of(p, st);
+    rc = w2d_gemm_of(p, pl, st);
     if (rc != AID_OK) return rc;
-    return w2d_output_of(p, st);
+    return w2d_output_of(p, pl, st);
 }
 // The two launches of aid_conv2d(x_wino = 3) as separate calls on the same parameter block (a launch plan that wants the MFMA-bound GEMM and the
 // HBM-bound output pass as separate nodes: per-kernel timing, different streams).  _gemm then _output on one stream == aid_conv2d(p).
 extern "C" int aid_conv2d_wino2d_gemm(const aid_conv2d_params* p, void* stream) {
     AID_REQUIRE(p && p->x.p && p->y.p && (p->x_wino == 3 || p->x_wino == 4), "aid_conv2d_wino2d_gemm: x_wino = 3 | 4 parameters");
-    const int rc = w2d_check(p);
-    return rc != AID_OK ? rc : w2d_gemm_of(p, (hipStream_t)stream);
+    W2dPlan pl;
+    const int rc = w2d_check(p, pl);
+    return rc != AID_OK ? rc : w2d_gemm_of(p, pl, (hipStream_t)stream);
 }
 extern "C" int aid_conv2d_wino2d_output(const aid_conv2d_params* p, void* stream) {
     AID_REQUIRE(p && p->x.p && p->y.p && (p->x_wino == 3 || p->x_wino == 4), "aid_conv2d_wino2d_output: x_wino = 3 | 4 parameters");
-    const int rc = w2d_check(p);
+    W2dPlan pl;
+    const int rc = w2d_check(p, pl);
     if (rc != AID_OK) return rc;
     aid_note_kernel("w2d_output_kernel");
-    return w2d_output_of(p, (hipStream_t)stream);
+    return w2d_output_of(p, pl, (hipStream_t)stream);
 }
