@@ -1,4 +1,4 @@
-"""ctypes binding of libaid_hip.so (the C ABI in include/aid_kernels.h, include/aid_degrade.h, include/aid_phase.h, include/aid_autoregressive.h and include/aid_restore.h).
+"""ctypes binding of libaid_hip.so (the C ABI in include/aid_kernels.h, include/aid_degrade.h, include/aid_phase.h, include/aid_autoregressive.h, include/aid_restore.h and include/aid_declip.h).
 
 There is deliberately NO fallback: if the shared library is missing or a launcher returns an error code,
 ``AidError`` is raised.  Tensors are passed as raw device pointers + element strides; the stream is torch's
@@ -318,6 +318,21 @@ AID_RESTORE_ABI_VERSION = 1
 AID_RESTORE_JOB_FIELDS = 6             # r, s, head, tail, lo, hi (int64 each)
 RESTORE_EXPORTS = ["aid_restore_abi_version", "aid_window_gather", "aid_window_scatter"]
 
+# ---- include/aid_declip.h (declipping whole recordings: the clipped / known / absent operator and its gather; a header and export list of their own) ----
+class ClipKnownParams(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("xref", C.c_void_p), ("y", C.c_void_p), ("state", C.c_void_p), ("clip", C.c_void_p), ("out", C.c_void_p),
+                ("B", C.c_int), ("mode", C.c_int), ("L", C.c_int64), ("x_ld", C.c_int64), ("xref_ld", C.c_int64), ("y_ld", C.c_int64),
+                ("state_ld", C.c_int64), ("out_ld", C.c_int64)]
+
+
+class DeclipGatherParams(C.Structure):
+    _fields_ = [("rec", C.c_void_p), ("out", C.c_void_p), ("clip", C.c_void_p), ("y", C.c_void_p), ("k", C.c_void_p), ("c", C.c_void_p), ("jobs", C.c_void_p),
+                ("J", C.c_int), ("R", C.c_int), ("L", C.c_int64), ("N", C.c_int64), ("rec_ld", C.c_int64), ("out_ld", C.c_int64)]
+
+
+AID_DECLIP_ABI_VERSION = 1
+DECLIP_EXPORTS = ["aid_declip_abi_version", "aid_clip_known", "aid_declip_gather"]
+
 EXPORTS = ["aid_abi_version", "aid_last_error", "aid_last_kernel", "aid_group_stats", "aid_conv2d", "aid_conv2d_pack_dims", "aid_conv2d_stat_partials", "aid_pack_conv_weight", "aid_wino_gy", "aid_conv2d_wgrad_tiles", "aid_resample",
            "aid_time_attention", "aid_embed", "aid_modulation", "aid_cqt_analysis", "aid_cqt_synthesis",
            "aid_cqt_gather", "aid_axpby", "aid_score_step", "aid_add2", "aid_group_dot", "aid_norm_bwd",
@@ -416,6 +431,14 @@ def lib():
         L.aid_restore_abi_version.argtypes = []
         if L.aid_restore_abi_version() != AID_RESTORE_ABI_VERSION:
             raise AidError("include/aid_restore.h ABI version mismatch")
+        for name in DECLIP_EXPORTS:
+            if not hasattr(L, name):
+                raise AidError(f"libaid_hip.so does not export {name}")
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
+            getattr(L, name).restype = C.c_int
+        L.aid_declip_abi_version.argtypes = []
+        if L.aid_declip_abi_version() != AID_DECLIP_ABI_VERSION:
+            raise AidError("include/aid_declip.h ABI version mismatch")
         _lib = L
     return _lib
 

@@ -1,0 +1,170 @@
+"""Declipping of whole recordings, longer than one model segment, in two batched sampler passes (include/aid_declip.h).
+
+Hard clipping is pointwise, so a window cut out of a clipped recording is exactly the clipped window, and the window scheme of restore.py
+carries over unchanged: the autoregressive grid, sample ownership, the even windows as pass A, the odd ones as pass B, seeds and
+aid_window_scatter.  A window is a job when its owned range holds a clipped sample (|y| >= c of its recording) -- the plan is
+``restore.restore_plan`` over the mask |y| < c.  What differs from inpainting is the observation of a window: most samples are seen through
+the clipper, the first and last ``end`` samples of a pass-B window are KNOWN (what pass A, or the recording, left there), and the samples
+of a last window beyond the end of the recording are ABSENT.  ``ClipObserved`` is that operator, on one HIP kernel (aid_clip_known) with a
+per-sample state (0 clipped, 1 known, -1 absent) and a clip level per item; ``declip_gather`` builds the observations, states and levels
+of all windows of a pass in one launch; ``declip_passes`` is the pass code, driven with anything that has ``predict_resample``.
+GPU only; no fallback.
+"""
+from __future__ import annotations
+
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import restore
+
+
+class ClipObserved:
+    """Observation of x[B, L] with state[1|B, L] (float32 on the GPU; 0 clipped, 1 known, -1 absent) and clip[B] (levels > 0; a float32 GPU
+    tensor is used as it is and NOT inspected, anything else is checked on the host and uploaded):
+
+        apply(x)       x where known, clamp(x, -c_b, c_b) where clipped, 0 where absent
+        adjoint(g)     g where known, g * (-c_b <= x_hat <= c_b) where clipped (inclusive, as HardClip), 0 where absent, at the x_hat of the
+                       last ``apply`` on the current stream
+        project(x, y)  the point nearest to x among the signals consistent with y: y where known or |y| < c_b, max(x, c_b) where y >= c_b,
+                       min(x, -c_b) where y <= -c_b, x where absent
+
+    The operator protocol of degrade.py.  It holds per-item rows, so ``shared_mask`` is False; ``rows(lo, hi)`` is the operator of items
+    lo:hi, which is what lets network.denoise_guided run sub-batches of it on concurrent streams."""
+    shared_mask = False
+
+    def __init__(self, state: torch.Tensor, clip):
+        if not (torch.is_tensor(state) and state.is_cuda and state.dtype == torch.float32 and state.dim() == 2 and (state.stride(1) == 1 or state.shape[1] == 1)):
+            raise _lib.AidError("ClipObserved: state must be a float32 GPU tensor [1|B, L] with contiguous rows (no CPU fallback)")
+        if torch.is_tensor(clip) and clip.is_cuda:
+            if clip.dtype != torch.float32:
+                raise _lib.AidError("ClipObserved: clip levels on the GPU must be float32")
+            clip = clip.reshape(-1).contiguous()
+        else:
+            clip = torch.from_numpy(clip_levels(clip)).to(state.device)
+        if state.shape[0] not in (1, clip.numel()):
+            raise _lib.AidError(f"ClipObserved: {state.shape[0]} state rows for {clip.numel()} clip levels")
+        self.state, self.clip = state, clip
+        self.B, self.L = clip.numel(), state.shape[1]
+        self._x, self._sub = {}, {}
+
+    def rows(self, lo: int, hi: int) -> "ClipObserved":
+        """The operator restricted to items lo:hi (views, no copy; a shared state row stays shared).  Kept per range, so that the apply / adjoint
+        pair of a sub-batch meets the same object."""
+        lo, hi = int(lo), int(hi)
+        if not 0 <= lo < hi <= self.B:
+            raise _lib.AidError(f"ClipObserved.rows: [{lo}, {hi}) is no range of {self.B} items")
+        op = self._sub.get((lo, hi))
+        if op is None:
+            op = self._sub[(lo, hi)] = ClipObserved(self.state if self.state.shape[0] == 1 else self.state[lo:hi], self.clip[lo:hi])
+        return op
+
+    def _run(self, mode, x, xref=None, y=None):
+        x = x.reshape(x.shape[0], -1)
+        if not (x.is_cuda and x.dtype == torch.float32 and tuple(x.shape) == (self.B, self.L)):
+            raise _lib.AidError(f"ClipObserved: expected a float32 GPU tensor [{self.B}, {self.L}], got {tuple(x.shape)}")
+        x = x.contiguous()
+        out = torch.empty_like(x)
+        L = self.L
+        _lib.call("aid_clip_known", _lib.ClipKnownParams(x.data_ptr(), _lib.ptr(xref), _lib.ptr(y), self.state.data_ptr(), self.clip.data_ptr(), out.data_ptr(),
+                                                         self.B, mode, L, L, L, L, self.state.stride(0) if self.state.shape[0] > 1 else 0, L))
+        return out, x
+
+    def apply(self, x):
+        out, x = self._run(0, x)
+        self._x[torch.cuda.current_stream().cuda_stream] = x
+        return out
+
+    def adjoint(self, g):
+        xref = self._x.get(torch.cuda.current_stream().cuda_stream)
+        if xref is None or xref.numel() != g.numel():
+            raise _lib.AidError("ClipObserved.adjoint needs the matching apply on this stream first")
+        return self._run(1, g, xref=xref)[0]
+
+    def project(self, x, y):
+        y = y.reshape(y.shape[0], -1)
+        if not (y.is_cuda and y.dtype == torch.float32 and tuple(y.shape) == (self.B, self.L)):
+            raise _lib.AidError(f"ClipObserved.project: the observation must be a float32 GPU tensor [{self.B}, {self.L}], got {tuple(y.shape)}")
+        return self._run(2, x, y=y.contiguous())[0]
+
+    def __call__(self, x):
+        return self.apply(x)
+
+
+def clip_levels(clip_value, R: Optional[int] = None) -> np.ndarray:
+    """A float or a sequence / tensor of floats -> float32 levels (rounded to float32 as HardClip does), each finite and > 0; with ``R``, one level is
+    repeated for R recordings and any other count than 1 or R is refused."""
+    v = clip_value.detach().cpu().numpy() if torch.is_tensor(clip_value) else clip_value
+    c = np.asarray(v, dtype=np.float64).reshape(-1).astype(np.float32)
+    if c.size == 0 or not bool(np.all(np.isfinite(c) & (c > 0))):
+        raise _lib.AidError(f"every clip level must be finite and > 0, got {c.tolist()}")
+    if R is not None:
+        if c.size not in (1, R):
+            raise _lib.AidError(f"{c.size} clip levels for {R} recordings (one for all, or one each)")
+        c = np.array(np.broadcast_to(c, (R,)))
+    return c
+
+
+def declip_gather(rec: torch.Tensor, out: torch.Tensor, clip: torch.Tensor, jobs: torch.Tensor, L: int):
+    """One aid_declip_gather launch on the current stream -> (y [J, L], k [J, L], c [J]): the observations, the states and the clip level of every
+    job's window; the first ``head`` / last ``tail`` samples known from ``out``, the rest the clipped ``rec``, samples from N on absent."""
+    for t, what in ((rec, "rec"), (out, "out")):
+        restore._rows(t, what)
+    restore._table(jobs)
+    R, N = rec.shape
+    if out.shape != rec.shape or not (clip.is_cuda and clip.dtype == torch.float32 and clip.dim() == 1 and clip.numel() == R and clip.is_contiguous()):
+        raise _lib.AidError(f"declip_gather: rec {tuple(rec.shape)}, out {tuple(out.shape)} and clip {tuple(clip.shape)} do not match (clip: float32 [R] on the GPU)")
+    J = jobs.shape[0]
+    y = torch.empty((J, L), dtype=torch.float32, device=rec.device)
+    k = torch.empty((J, L), dtype=torch.float32, device=rec.device)
+    c = torch.empty((J,), dtype=torch.float32, device=rec.device)
+    if J:
+        _lib.call("aid_declip_gather", _lib.DeclipGatherParams(rec.data_ptr(), out.data_ptr(), clip.data_ptr(), y.data_ptr(), k.data_ptr(), c.data_ptr(), jobs.data_ptr(),
+                                                               J, R, int(L), N, rec.stride(0), out.stride(0)))
+    return y, k, c
+
+
+def check_declip_args(y: torch.Tensor, clip, L: int, end: int, max_batch: int, seeds) -> np.ndarray:
+    """The refusals of a declipping run, all raised before anything is launched -> the R clip levels (float32, host).  What can be judged
+    without a GPU is judged first; the device of y last."""
+    if not (torch.is_tensor(y) and y.dtype == torch.float32 and y.dim() == 2 and (y.shape[1] <= 1 or y.stride(1) == 1)):
+        raise _lib.AidError(f"y must be float32 recordings [R, N] with contiguous rows, got {tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
+    levels = clip_levels(clip, y.shape[0])
+    restore.restore_windows(y.shape[1], L, end)                       # (end in [1, L/2))
+    if max_batch < 1:
+        raise _lib.AidError(f"max_batch must be >= 1, got {max_batch}")
+    if seeds is not None and len(seeds) != y.shape[0]:
+        raise _lib.AidError(f"{len(seeds)} seeds for {y.shape[0]} recordings")
+    if not y.is_cuda:
+        raise _lib.AidError("declipping of whole recordings runs on the GPU only (no CPU fallback): y must be a float32 tensor on the GPU")
+    return levels
+
+
+def declip_plan(y: torch.Tensor, levels, L: int, end: int):
+    """restore_plan over the mask |y| < c_r (float32 comparison, on y's device): a window is a job exactly when its owned range holds a sample
+    with |y| >= c_r.  y [R, N], levels [R] -> (jobs_A, jobs_B, N_pad)."""
+    c = torch.from_numpy(np.array(levels, dtype=np.float32)).to(y.device)
+    return restore.restore_plan(y.abs() < c[:, None], L, end, y.shape[0])
+
+
+def declip_passes(sampler, y: torch.Tensor, clip, L: int, end: int, max_batch: int = 8, seeds: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """The two passes over ``sampler.predict_resample(yw [B, L], (B, L), ClipObserved(kw [B, L], cw [B])) -> [B, L]`` with B <= max_batch:
+    y [R, N] clipped recordings on the GPU (rows contiguous, any row stride), clip a level or R levels -> declipped [R, N].  Per pass: one
+    aid_declip_gather launch, the sampler calls, one aid_window_scatter launch per call (restore.run_passes).  Recordings and result stay on
+    the GPU; the plan is made on the host from |y| < c before pass A.  Seeds as restore.restore_passes."""
+    levels = check_declip_args(y, clip, L, end, max_batch, seeds)
+    R, N = y.shape
+    jobs_A, jobs_B, _ = declip_plan(y, levels, L, end)
+    out = torch.empty((R, N), dtype=torch.float32, device=y.device)
+    out.copy_(y)
+    if not (jobs_A or jobs_B):
+        return out
+    dclip = torch.from_numpy(levels).to(y.device)
+
+    def predict(win, c0, c1):
+        yw, kw, cw = (t[c0:c1] for t in win)
+        return sampler.predict_resample(yw, (c1 - c0, L), ClipObserved(kw, cw))
+    restore.run_passes(sampler, out, (jobs_A, jobs_B), L - end, max_batch, seeds, lambda table: declip_gather(y, out, dclip, table, L), predict)
+    return out

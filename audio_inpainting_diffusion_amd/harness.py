@@ -166,6 +166,32 @@ def restore_long(sampler, files: Sequence[torch.Tensor], masks: Sequence[torch.T
     return out
 
 
+def declip_long(sampler, files: Sequence[torch.Tensor], clip_values, seeds: Optional[Sequence[int]] = None, max_batch: int = 8,
+                device="cuda") -> List[torch.Tensor]:
+    """Declip every 1-D waveform of ``files`` (any lengths), clipped at +-clip_values (one float for all files, or one per file), and return the
+    full-length results on ``device``, in the order of ``files``.  Files of equal length go through ONE Sampler.predict_declipping_long call, so
+    their windows share the two batched passes; every other length is a call of its own.  ``seeds``: one RNG seed per file (file i's result then
+    depends on seeds[i] alone, not on the grouping)."""
+    levels = [float(v) for v in (clip_values.reshape(-1).tolist() if torch.is_tensor(clip_values) else
+                                 (list(clip_values) if hasattr(clip_values, "__len__") else [clip_values]))]
+    if len(levels) not in (1, len(files)):
+        raise ValueError(f"declip_long: {len(levels)} clip values for {len(files)} files")
+    if len(levels) == 1:
+        levels = levels * len(files)
+    if seeds is not None and len(seeds) != len(files):
+        raise ValueError(f"declip_long: {len(seeds)} seeds for {len(files)} files")
+    groups = {}
+    for i, x in enumerate(files):
+        groups.setdefault(x.numel(), []).append(i)
+    out: List[Optional[torch.Tensor]] = [None] * len(files)
+    for idx in groups.values():
+        y = torch.stack([files[i].reshape(-1).float() for i in idx]).to(device)
+        res = sampler.predict_declipping_long(y, [levels[i] for i in idx], max_batch=max_batch, seeds=None if seeds is None else [int(seeds[i]) for i in idx])
+        for k, i in enumerate(idx):
+            out[i] = res[k]
+    return out
+
+
 # ---- waveform pre-/post-processing of the tester --------------------------------------------------------------------------------
 def _sinc_kernel(orig: int, new: int, lowpass_filter_width: int = 6, rolloff: float = 0.99):
     """Hann-windowed sinc per output phase, [new, 2*width + orig] float64 -- torchaudio's default resampling kernel."""

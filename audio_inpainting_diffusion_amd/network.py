@@ -1550,7 +1550,9 @@ class Unet_CQT_oct_with_attention(nn.Module):
         cnoise, cin, cskip, cout = self._norm_scalars(B, x.device, (cnoise, cin, cskip, cout))
         if not (y.is_cuda and y.dtype == torch.float32 and y.is_contiguous() and y.shape[0] == B and (degradation is not None or tuple(y.shape) == (B, L))):
             raise _lib.AidError("denoise_guided: y must be a contiguous float32 GPU tensor of shape [B, L] ([B, ...] with a degradation operator)")
-        if (degradation is not None and not getattr(degradation, "shared_mask", False)) or self._n_split(B) == 1:
+        # an operator with per-item rows runs on one stream, unless it can hand out the operator of a range of items (rows(lo, hi): declip_long.ClipObserved)
+        per_item = degradation is not None and not getattr(degradation, "shared_mask", False)
+        if (per_item and not hasattr(degradation, "rows")) or self._n_split(B) == 1:
             st = self._state(B)                                      # (per-item operator masks: one stream)
             if degradation is None and self._graph_ok(B, st):
                 key = ("guided", bool(hpf), y.data_ptr(), mask.data_ptr(), tuple(mask.shape), nk)   # y / mask are read in place
@@ -1572,7 +1574,7 @@ class Unet_CQT_oct_with_attention(nn.Module):
                 sti = self._state(hi - lo, i, (B, n))
                 sti["part_slot"] = i if self.cu_partition else None
                 self._denoise_guided_one(x[lo:hi], cnoise[lo:hi], cin[lo:hi], cskip[lo:hi], cout[lo:hi], hpf, y[lo:hi],
-                                         None if m is None else (m[lo:hi] if m.shape[0] > 1 else m), degradation, sti,
+                                         None if m is None else (m[lo:hi] if m.shape[0] > 1 else m), degradation.rows(lo, hi) if per_item else degradation, sti,
                                          outs=(x_hat[lo:hi], grads[lo:hi], norm[lo:hi]), nk=nk)
         for st_ in streams:
             cur.wait_stream(st_)

@@ -15,7 +15,8 @@ it.  A window whose owned range has no gap is no job and costs nothing.  Hard co
 autoregressive mode, testing/edm_sampler.py:416).
 
 ``restore_plan`` is host code (the only part that looks at the mask on the host); ``window_gather`` / ``window_scatter`` launch the
-two HIP kernels of csrc/aid_restore.hip; ``restore_passes`` is the pass code, driven with anything that has ``predict_inpainting``.
+two HIP kernels of csrc/aid_restore.hip; ``restore_passes`` is the pass code, driven with anything that has ``predict_inpainting``;
+``run_passes`` is the loop it shares with the declipping of whole recordings (declip_long.py).
 """
 from __future__ import annotations
 
@@ -143,6 +144,24 @@ def check_restore_args(y: torch.Tensor, mask: torch.Tensor, L: int, end: int, ma
     return mask
 
 
+def run_passes(sampler, out: torch.Tensor, passes: Sequence[Sequence[Job]], step: int, max_batch: int, seeds, gather, predict) -> None:
+    """The pass loop every whole-recording restoration shares.  Per non-empty job list of ``passes``: ``win = gather(table)`` (one launch for
+    the whole pass), then per chunk [c0, c1) of at most ``max_batch`` jobs ``x = predict(win, c0, c1)`` -> [c1 - c0, L] and one
+    aid_window_scatter launch of x into ``out``.  A later pass gathers what an earlier one scattered: same stream, in order.
+    ``sampler.seeds`` is set per chunk by the seed rule (None without seeds) and put back at the end."""
+    tables = [(jobs, job_table(jobs, out.device)) for jobs in passes if jobs]
+    keep = getattr(sampler, "seeds", None)
+    try:
+        for jobs, table in tables:
+            win = gather(table)
+            for c0 in range(0, len(jobs), max_batch):
+                c1 = min(len(jobs), c0 + max_batch)
+                sampler.seeds = None if seeds is None else [int(seeds[r]) * SEED_STRIDE + s // step for r, s, *_ in jobs[c0:c1]]
+                window_scatter(predict(win, c0, c1).contiguous(), out, table[c0:c1])
+    finally:
+        sampler.seeds = keep
+
+
 def restore_passes(sampler, y: torch.Tensor, mask: torch.Tensor, L: int, end: int, max_batch: int = 8, seeds: Optional[Sequence[int]] = None) -> torch.Tensor:
     """The two passes over ``sampler.predict_inpainting(yw [B, L], mw [B, L]) -> [B, L]`` with B <= max_batch: y [R, N] recordings on the GPU
     (rows contiguous, any row stride), mask [1|R, N] -> restored [R, N].  Per pass: one gather launch, the sampler calls, one scatter launch per
@@ -156,17 +175,7 @@ def restore_passes(sampler, y: torch.Tensor, mask: torch.Tensor, L: int, end: in
     if not (jobs_A or jobs_B):
         return out
     dmask = mask.to(y.device, torch.float32).contiguous()
-    tables = [(jobs, job_table(jobs, y.device)) for jobs in (jobs_A, jobs_B) if jobs]
-    step = L - end
-    keep = getattr(sampler, "seeds", None)
-    try:
-        for jobs, table in tables:
-            yw, mw = window_gather(y, out, dmask, table, L)         # (pass B reads what pass A scattered: same stream, in order)
-            for c0 in range(0, len(jobs), max_batch):
-                c1 = min(len(jobs), c0 + max_batch)
-                sampler.seeds = None if seeds is None else [int(seeds[r]) * SEED_STRIDE + s // step for r, s, *_ in jobs[c0:c1]]
-                x = sampler.predict_inpainting(yw[c0:c1], mw[c0:c1])
-                window_scatter(x.contiguous(), out, table[c0:c1])
-    finally:
-        sampler.seeds = keep
+    run_passes(sampler, out, (jobs_A, jobs_B), L - end, max_batch, seeds,
+               lambda table: window_gather(y, out, dmask, table, L),         # (pass B reads what pass A scattered)
+               lambda win, c0, c1: sampler.predict_inpainting(win[0][c0:c1], win[1][c0:c1]))
     return out

@@ -506,6 +506,22 @@ class Sampler:
         self._check_model()
         return restore.restore_passes(self, y, mask, L, end, max_batch, seeds)
 
+    def predict_declipping_long(self, y, clip_value, max_batch=8, seeds=None):
+        """Declip whole recordings y[R, N] -- N any length, clipped at +-clip_value (a float, or R floats: one level per recording; rounded to
+        float32 as HardClip does) -> [R, N] on y.device (declip_long.py).  The window grid, the two batched passes and the seeds are those of
+        predict_inpainting_long; a window is a job when its owned range holds a sample with |y| >= c.  Each chunk of at most ``max_batch`` windows
+        is one predict_resample through declip_long.ClipObserved, which sees the recording through the clipper and takes the overlaps its
+        neighbours restored as known.  tester.data_consistency off: guidance only, as the reference's declipping; "always" / "end": the
+        projection onto the signals consistent with the clipped recording at every evaluation / once on the final state.  Windows without a
+        clipped sample cost nothing and keep the recording's samples."""
+        from . import declip_long
+        if self.rid:
+            raise _lib.AidError("predict_declipping_long returns the declipped recordings only: rid must be False")
+        L = int(self.args.exp.audio_len)
+        end = int(autoregressive_overlap(self.args) * L)
+        self._check_model()
+        return declip_long.declip_passes(self, y, clip_value, L, end, max_batch, seeds)      # (validates its arguments before anything is launched)
+
     # ---- the remaining public methods of the reference class (its testers never call them; kept so that code written against
     # ---- testing.edm_sampler_inpainting.Sampler finds every name).  They run outside the sampling loop. ------------------------------
     def apply_mask(self, x, mask=None):
