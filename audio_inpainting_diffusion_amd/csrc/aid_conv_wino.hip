@@ -10,11 +10,16 @@
 //   conv53_wino4r_kernel : F(4,3), Winograd-domain input, ROW-SHARED staging on dilation sub-lattices, 2-3 workgroups per CU (+ pair and split-K instances)
 //   conv53_wino8r_kernel : F(8,3) on the same row-shared body (wino4r_tile_body<..., WM = 8>): 64 x 512 tiles, 160 accumulators per lane -- the dominant kernel
 //   conv53_wino8r_ks_kernel : its K-group instance for launches of at most one tile per CU (small batches): eight waves on one tile, two K groups, sum through LDS
-// Which form takes a launch: wino_form_choice() / aid_conv2d_wino_form().
+//   conv53_wino4r_ks_kernel : the same for F(4,3) on the T <= 32 tile shapes
+// The four row-shared kernels are entries over wino4r_tile_body (AID_W4R_ENTRY: one family, or the 64 + 32 pair of a 96-channel layer in one grid).
+// Host side: the tile geometry of a row-shared launch is ONE WinoRPlan (aid_wino_plan.h); launch_wino_r() launches from it, and wino_form_choice() /
+// aid_conv2d_wino_form() (which form takes a launch), the K-group and split-K rules and the aid_conv2d_* host queries (fin_mode support, split-K
+// scratch, statistics and dot partial counts) read the same plan.
 #include "aid_common.h"
 #include "aid_mfma_dma.h"
 #include "aid_wino8.h"
 #include "aid_fin.h"
+#include "aid_wino_plan.h"
 #include <type_traits>
 #include <stdlib.h>
 
@@ -1185,36 +1190,37 @@ __device__ __forceinline__ void wino4r_tile_body(const ConvWinoRDev& a, const W4
     }
 }
 
-// NC1 > 0: PAIR instance for 96-channel layers -- the 64 x 256 tiles of channels [0, 64) (family 0: <TT, NC, WGM = 2>) and the 32 x 512
-// remainder tiles of channels [64, 96) (family 1: <TT, NC1, WGM = 1>) in ONE grid, family 0 first: the remainder tiles start while the
-// last 64-wide tiles drain instead of after a launch boundary (two launches: each has its own tail, and at batch 1 neither fills the chip).
+// One workgroup of a row-shared launch: a tile of the one family (NC1 == 0), or -- NC1 > 0: PAIR instance for 96-channel layers -- the 64 x 256 tiles of
+// channels [0, 64) (family 0: <TT, NC, WGM = 2>) and the 32 x 512 remainder tiles of channels [64, 96) (family 1: <TT, NC1, WGM = 1>) in ONE grid,
+// family 0 first: the remainder tiles start while the last 64-wide tiles drain instead of after a launch boundary (two launches: each has its own tail,
+// and at batch 1 neither fills the chip).  The two families share one LDS array.
 // Measured against two launches (profiles/r03_w4r_split_probe.txt, r03_w4r_ab.txt): batch 1 [96, 256, 256] 140 -> 100 us,
 // [96, 192, 512] 170 -> 145 us; batch 3 380 -> 340 us; batch 8 918 -> 905 / 627 -> 604 us; end to end +4.7 % / +1.5 % / +1.2 % / +0.6 % at batch 1 / 2 / 3 / 8.  (The two-launch path was removed after that A/B.)
 // SPK: split-K instance (ConvWinoRDev::splits == 2).
+// A macro, expanded in the four kernels, not a function: ANY function layer between a kernel and wino4r_tile_body (the array declared inside it or in the
+// kernel, the workgroup index read inside or passed) reorders independent instructions of the inlined body, and the backend then schedules every instance
+// differently -- equal instruction counts and registers, not equal code (profiles/r13_wino_r_plan.txt).
+#define AID_W4R_ENTRY(TT, NC, WGM, NB, WPC, NWV, WM, KS, NC1, SPK) do { \
+    using S0 = W4rShape<TT, NC, WGM, NB, WPC, NWV, WM, KS>; \
+    if constexpr (NC1 == 0) { \
+        __shared__ __attribute__((aligned(16))) float smem[S0::LDS]; \
+        wino4r_tile_body<TT, NC, WGM, NB, WPC, NWV, SPK, WM, KS>(a, a.g[0], smem, (int)blockIdx.x); \
+    } else { \
+        using S1 = W4rShape<TT, NC1, 1, NB, WPC, NWV, WM, KS>; \
+        __shared__ __attribute__((aligned(16))) float smem[S0::LDS > S1::LDS ? S0::LDS : S1::LDS]; \
+        const int n0 = 8 * a.g[0].per_xcd; \
+        if ((int)blockIdx.x < n0) wino4r_tile_body<TT, NC, WGM, NB, WPC, NWV, false, WM, KS>(a, a.g[0], smem, (int)blockIdx.x); \
+        else wino4r_tile_body<TT, NC1, 1, NB, WPC, NWV, false, WM, KS>(a, a.g[1], smem, (int)blockIdx.x - n0); \
+    } } while (0)
+
 template <int TT, int NC, int WGM, int NB = 3, int WPC = 2, int NWV = 4, int NC1 = 0, bool SPK = false>
-__global__ __launch_bounds__(64 * NWV, (WPC * NWV + 3) / 4) void conv53_wino4r_kernel(const ConvWinoRDev a) {
-    using S0 = W4rShape<TT, NC, WGM, NB, WPC, NWV>;
-    if constexpr (NC1 == 0) {
-        __shared__ __attribute__((aligned(16))) float smem[S0::LDS];
-        wino4r_tile_body<TT, NC, WGM, NB, WPC, NWV, SPK>(a, a.g[0], smem, (int)blockIdx.x);
-    } else {
-        using S1 = W4rShape<TT, NC1, 1, NB, WPC, NWV>;
-        __shared__ __attribute__((aligned(16))) float smem[S0::LDS > S1::LDS ? S0::LDS : S1::LDS];
-        const int n0 = 8 * a.g[0].per_xcd;
-        if ((int)blockIdx.x < n0) wino4r_tile_body<TT, NC, WGM, NB, WPC, NWV, false>(a, a.g[0], smem, (int)blockIdx.x);
-        else wino4r_tile_body<TT, NC1, 1, NB, WPC, NWV, false>(a, a.g[1], smem, (int)blockIdx.x - n0);
-    }
-}
+__global__ __launch_bounds__(64 * NWV, (WPC * NWV + 3) / 4) void conv53_wino4r_kernel(const ConvWinoRDev a) { AID_W4R_ENTRY(TT, NC, WGM, NB, WPC, NWV, 4, 1, NC1, SPK); }
 
 // K-group instance of the F(4,3) kernel (see conv53_wino8r_ks_kernel below): one eight-wave workgroup per 64 x 256 tile, two K groups, for launches of at
 // most one tile per CU -- the deepest level of the shipped networks at batch 1 (224 tiles).  Replaces the split-K instances there: the same two waves
 // per SIMD, the partial sums through LDS instead of 98 KB per tile through memory (141-159 -> see DESIGN.md 3.1e).
 template <int TT, int NC>
-__global__ __launch_bounds__(512, 2) void conv53_wino4r_ks_kernel(const ConvWinoRDev a) {
-    using S0 = W4rShape<TT, NC, 2, 3, 1, 8, 4, 2>;
-    __shared__ __attribute__((aligned(16))) float smem[S0::LDS];
-    wino4r_tile_body<TT, NC, 2, 3, 1, 8, false, 4, 2>(a, a.g[0], smem, (int)blockIdx.x);
-}
+__global__ __launch_bounds__(512, 2) void conv53_wino4r_ks_kernel(const ConvWinoRDev a) { AID_W4R_ENTRY(TT, NC, 2, 3, 1, 8, 4, 2, 0, false); }
 
 // ---- F(8,3) on the same row-shared body: 10 products per 8 outputs (0.833x the MFMAs of F(4,3), 0.417x of the direct form), Winograd-domain
 // input [B, C, F, 10, T/8] (1.25x the activation instead of 1.5x).  A tile is 64 output channels x 512 positions (64 groups: 160 accumulator
@@ -1222,19 +1228,7 @@ __global__ __launch_bounds__(512, 2) void conv53_wino4r_ks_kernel(const ConvWino
 // fp32 error 3e-6 rel-L2 per layer at Cin = 128 (F(4,3): 1.5e-6, direct: 0.8e-6; tools/wino_fm3_error.py, profiles/r04_wino_fm3_error.txt).
 // NC1 > 0: pair instance for the 96-channel layers (32 x 1024 remainder tiles), as above.
 template <int TT, int NC, int WGM, int NC1 = 0>
-__global__ __launch_bounds__(256, 2) void conv53_wino8r_kernel(const ConvWinoRDev a) {
-    using S0 = W4rShape<TT, NC, WGM, 2, 2, 4, 8>;
-    if constexpr (NC1 == 0) {
-        __shared__ __attribute__((aligned(16))) float smem[S0::LDS];
-        wino4r_tile_body<TT, NC, WGM, 2, 2, 4, false, 8>(a, a.g[0], smem, (int)blockIdx.x);
-    } else {
-        using S1 = W4rShape<TT, NC1, 1, 2, 2, 4, 8>;
-        __shared__ __attribute__((aligned(16))) float smem[S0::LDS > S1::LDS ? S0::LDS : S1::LDS];
-        const int n0 = 8 * a.g[0].per_xcd;
-        if ((int)blockIdx.x < n0) wino4r_tile_body<TT, NC, WGM, 2, 2, 4, false, 8>(a, a.g[0], smem, (int)blockIdx.x);
-        else wino4r_tile_body<TT, NC1, 1, 2, 2, 4, false, 8>(a, a.g[1], smem, (int)blockIdx.x - n0);
-    }
-}
+__global__ __launch_bounds__(256, 2) void conv53_wino8r_kernel(const ConvWinoRDev a) { AID_W4R_ENTRY(TT, NC, WGM, 2, 2, 4, 8, 1, NC1, false); }
 
 // K-group instance of the F(8,3) kernel: ONE eight-wave workgroup per CU, the same 64 x 512 (32 x 1024) tile, waves 0-3 on the even and waves 4-7 on the
 // odd pairs of input channels (four channels per staged chunk, 66-72 KB per buffer, two buffers).  The F(8,3) tile has 160 accumulators per lane, so a
@@ -1242,19 +1236,8 @@ __global__ __launch_bounds__(256, 2) void conv53_wino8r_kernel(const ConvWinoRDe
 // matrix pipe waiting on every LDS read and barrier.  Two waves per SIMD on the SAME tile need no second tile; the exchange at the end is 160 KB of
 // LDS traffic per tile (about 1 us).
 template <int TT, int NC, int WGM, int NC1 = 0>
-__global__ __launch_bounds__(512, 2) void conv53_wino8r_ks_kernel(const ConvWinoRDev a) {
-    using S0 = W4rShape<TT, NC, WGM, 2, 1, 8, 8, 2>;
-    if constexpr (NC1 == 0) {
-        __shared__ __attribute__((aligned(16))) float smem[S0::LDS];
-        wino4r_tile_body<TT, NC, WGM, 2, 1, 8, false, 8, 2>(a, a.g[0], smem, (int)blockIdx.x);
-    } else {
-        using S1 = W4rShape<TT, NC1, 1, 2, 1, 8, 8, 2>;
-        __shared__ __attribute__((aligned(16))) float smem[S0::LDS > S1::LDS ? S0::LDS : S1::LDS];
-        const int n0 = 8 * a.g[0].per_xcd;
-        if ((int)blockIdx.x < n0) wino4r_tile_body<TT, NC, WGM, 2, 1, 8, false, 8, 2>(a, a.g[0], smem, (int)blockIdx.x);
-        else wino4r_tile_body<TT, NC1, 1, 2, 1, 8, false, 8, 2>(a, a.g[1], smem, (int)blockIdx.x - n0);
-    }
-}
+__global__ __launch_bounds__(512, 2) void conv53_wino8r_ks_kernel(const ConvWinoRDev a) { AID_W4R_ENTRY(TT, NC, WGM, 2, 1, 8, 8, 2, NC1, false); }
+#undef AID_W4R_ENTRY
 
 // the device zero page of this translation unit (looked up once); nullptr with the error set when the lookup fails
 static const float* wino_zero_page() {
@@ -1306,36 +1289,16 @@ static int launch_wino4v(const aid_conv2d_params* p, hipStream_t st) {
                                                            {"conv53_wino4v_kernel", "conv53_wino4v_kernel(96)", "conv53_wino4v_kernel(64x256)"}, p, st);
 }
 
-// row-shared kernel: eligibility + launch.  Returns 1000 when the shape is better served by the 64|96 x 512 kernel.
-// Picks the fewest residue classes per tile (least staging) whose rows-per-class RA wastes at most 10 % of a tile on padding rows.
-// npos: positions per tile (256 for the 64-channel tile, 512 for the 32-channel remainder tile of 96-channel layers).
-static int wino4r_tile(const aid_conv2d_params* p, int npos, int max_nc, int* TTo, int* NCo, int* quads, int* ttiles) {
-    if (p->dilF < 1 || (p->F % p->dilF)) return 0;
-    const int TT = p->T >= 64 ? 64 : (p->T >= 32 ? 32 : 16);      // (T = 16: the deepest level of the 8-octave 44.1 kHz network at L = 184184)
-    if (p->T % TT) return 0;
-    const int nrow = p->F / p->dilF;
-    for (int NC = 1; NC * TT <= 256 && NC <= max_nc; NC *= 2) {
-        if (p->dilF % NC) break;
-        const int RA = npos / (TT * NC);
-        const int qd = (nrow + RA - 1) / RA;
-        if ((int64_t)qd * RA * 10 > (int64_t)nrow * 11) continue;     // more than 10 % of the rows of a tile would be padding
-        *TTo = TT; *NCo = NC; *quads = qd; *ttiles = p->T / TT;
-        return 1;
-    }
-    return 0;
-}
-
-struct Wino4rPlan { int TT, NC, quads, ttiles; };
-// plan[0]: the 64-channel tiles; plan[1] (96-channel layers only): the 32-channel remainder tiles.  Returns the number of launches (0: not eligible).
-static int wino4r_geometry(const aid_conv2d_params* p, Wino4rPlan plan[2]) {
-    if (p->Cout_pad % 64 == 0) return wino4r_tile(p, 256, 8, &plan[0].TT, &plan[0].NC, &plan[0].quads, &plan[0].ttiles) ? 1 : 0;
-    if (p->Cout_pad % 96) return 0;
-    if (!wino4r_tile(p, 256, 8, &plan[0].TT, &plan[0].NC, &plan[0].quads, &plan[0].ttiles)) return 0;
-    if (!wino4r_tile(p, 512, 2, &plan[1].TT, &plan[1].NC, &plan[1].quads, &plan[1].ttiles) || plan[1].TT != 64) return 0;
-    return 2;
-}
-
+// ---- row-shared kernels: plan, eligibility, launch ---------------------------------------------------------------------------------------------
+// The tile geometry of a launch is a WinoRPlan (aid_wino_plan.h); everything below reads it.
 static bool wino_v_shape_ok(int Cin, int Cout, int T);
+
+// the plan of a launch given by its logical shape (the host queries)
+static WinoRPlan wino_r_plan_of(int form, int B, int Cin, int Cout, int F, int T, int dilF) {
+    int cip, cop;
+    aid_conv2d_pack_dims(Cin, Cout, &cip, &cop);
+    return wino_r_plan(form, B, cop, F, T, dilF);
+}
 
 // (environment overrides exist only in -DAID_EXPERIMENT builds: the product library's results never depend on the environment)
 static int w4r_env(const char* name, int dflt) {
@@ -1357,154 +1320,27 @@ static int w4r_env(const char* name, int dflt) {
 // (profiles/r03_w4r_ab.txt).  AID_W4R_SPLIT overrides the threshold (0 = never split).
 // K-group instances of the F(4,3) kernel (conv53_wino4r_ks_kernel): at most one tile per CU, the T <= 32 tile shapes (the deep levels).
 // AID_W4R_KS (experiment builds): 0 never (split-K as before), 1 wherever instantiated.
-static bool wino4r_ks_wanted(const aid_conv2d_params* p, int nl, const Wino4rPlan* plan, int64_t ntiles) {
+static bool wino4r_ks_wanted(const WinoRPlan& pl, int Cin) {
     static const int force = w4r_env("AID_W4R_KS", -1);
-    if (nl != 1 || plan[0].TT > 32 || (p->Cin % 4)) return false;
+    if (pl.nl != 1 || pl.f[0].TT > 32 || (Cin % 4)) return false;
     if (force == 0 || force == 1) return force != 0;
-    return ntiles <= 256;
+    return pl.tiles <= 256;
 }
-static int wino4r_splits(const aid_conv2d_params* p, int nl, int64_t ntiles) {
+static int wino4r_splits(const WinoRPlan& pl, int B, int Cin) {
     static const int thr = w4r_env("AID_W4R_SPLIT", 230);
-    if (p->B != 1 || nl != 1 || ntiles > thr || ntiles > AID_W4R_SPLIT_MAX_TILES || (p->Cin % 4)) return 1;
+    if (B != 1 || pl.nl != 1 || pl.tiles > thr || pl.tiles > AID_W4R_SPLIT_MAX_TILES || (Cin % 4)) return 1;
     return 2;
 }
 
-// fin_mode (aid_kernels.h): argument check shared by the two row-shared launchers
-static int wino_fin_check(const aid_conv2d_params* p) {
-    if (!p->fin_mode) return AID_OK;
-    AID_REQUIRE(p->fin_mode == 1 || p->fin_mode == 2, "aid_conv2d: fin_mode is 0, 1 or 2");
-    AID_REQUIRE(p->fin_count && p->fin_scale && (p->Cout % 8) == 0, "aid_conv2d: fin_mode needs fin_count, fin_scale and Cout % 8 == 0");
-    if (p->fin_mode == 1) AID_REQUIRE(p->stat_ws && p->fin_gamma, "aid_conv2d: fin_mode = 1 folds the stat_ws partials and needs fin_gamma");
-    else AID_REQUIRE(p->dot_ws && p->fin_stats, "aid_conv2d: fin_mode = 2 folds the dot_ws partials and needs the forward statistics in fin_stats");
-    return AID_OK;
-}
-
-static int launch_wino4r(const aid_conv2d_params* p, hipStream_t st) {
-    const float* const zero = wino_zero_page();
-    if (!zero) return AID_E_LAUNCH;
-    Wino4rPlan plan[2];
-    const int nl = wino4r_geometry(p, plan);
-    if (!nl) return 1000;
-    const bool m96 = nl == 2;
-    ConvWinoRDev a;
-    a.p = *p;
-    a.zero = zero;
-    a.nchunks = p->Cin / 2;
-    a.dot_all = m96 ? 1 : 0;
-    a.splits = 1; a.part = nullptr; a.flags = nullptr;
-    W4rGeo geo[2];
-    int dot_base = 0;
-    for (int l = 0; l < nl; ++l) {
-        const Wino4rPlan& g = plan[l];
-        W4rGeo& ge = geo[l];
-        ge.quads = g.quads; ge.ttiles = g.ttiles;
-        ge.rgroups = p->dilF / g.NC;
-        ge.ny = m96 ? p->Cout_pad / 96 : p->Cout_pad / 64;
-        ge.m_base = l == 0 ? 0 : 64;
-        ge.m_stride = m96 ? 96 : 64;
-        ge.dot_base = dot_base;
-        dot_base += ge.rgroups * g.quads * g.ttiles;
-        ge.ntiles = p->B * ge.rgroups * g.quads * g.ttiles * ge.ny;
-        ge.per_xcd = (ge.ntiles + 7) / 8;
-    }
-    { const int rc = wino_fin_check(p); if (rc != AID_OK) return rc; }
-    a.fin_total = (geo[0].ntiles + (m96 ? geo[1].ntiles : 0)) / p->B;      // tiles per sample (before a split doubles the workgroups)
-    const bool kg = wino4r_ks_wanted(p, nl, plan, geo[0].ntiles);
-    if (kg) {
-        a.nchunks = p->Cin / 4;
-    } else if (wino4r_splits(p, nl, geo[0].ntiles) == 2 && p->ws && p->ws_bytes >= aid_w4r_split_bytes(geo[0].ntiles)) {
-        a.splits = 2;
-        a.flags = reinterpret_cast<unsigned*>(p->ws);
-        a.part = p->ws + AID_W4R_SPLIT_FLAG_BYTES / 4;
-        a.nchunks = p->Cin / 4;
-        geo[0].ntiles *= 2;
-        geo[0].per_xcd = (geo[0].ntiles + 7) / 8;
-    }
-    const bool short_k = p->Cin <= 128 && a.splits == 1;     // three workgroups per CU (two LDS buffers) for the short-K layers (re-measured in round 3 with
-                                                             // sub-batch streams: Cin <= 128 / 64 / never = 42.33 / 42.08 / 42.17 evaluations/s)
-#define AID_W4R(TTv, NCv, WGMv, NC1v) do { \
-        if constexpr (TTv == 64 && NCv <= 2) { if (short_k) { hipLaunchKernelGGL((conv53_wino4r_kernel<TTv, NCv, WGMv, 2, 3, 4, NC1v>), grid, dim3(256), 0, st, a); break; } } \
-        if constexpr (NC1v == 0 && WGMv == 2) { if (a.splits == 2) { hipLaunchKernelGGL((conv53_wino4r_kernel<TTv, NCv, WGMv, 3, 2, 4, 0, true>), grid, dim3(256), 0, st, a); break; } } \
-        hipLaunchKernelGGL((conv53_wino4r_kernel<TTv, NCv, WGMv, 3, 2, 4, NC1v>), grid, dim3(256), 0, st, a); } while (0)
-    if (m96) {
-        a.g[0] = geo[0]; a.g[1] = geo[1];
-        const dim3 grid((unsigned)(8 * (geo[0].per_xcd + geo[1].per_xcd)));
-        switch (plan[0].NC * 16 + plan[1].NC) {               // (both families: TT = 64, wino4r_geometry)
-            case 1 * 16 + 1: AID_W4R(64, 1, 2, 1); break;
-            case 1 * 16 + 2: AID_W4R(64, 1, 2, 2); break;
-            case 2 * 16 + 1: AID_W4R(64, 2, 2, 1); break;
-            case 2 * 16 + 2: AID_W4R(64, 2, 2, 2); break;
-            case 4 * 16 + 1: AID_W4R(64, 4, 2, 1); break;
-            case 4 * 16 + 2: AID_W4R(64, 4, 2, 2); break;
-            default: aid_set_error("aid_conv2d: row-shared pair tile shape not instantiated"); return AID_E_BADARG;
-        }
-        AID_CHECK_LAUNCH();
-    } else {
-        const Wino4rPlan& g = plan[0];
-        a.g[0] = geo[0]; a.g[1] = geo[0];
-        const dim3 grid((unsigned)(8 * geo[0].per_xcd));
-#define AID_W4R_KS(TTv, NCv) hipLaunchKernelGGL((conv53_wino4r_ks_kernel<TTv, NCv>), grid, dim3(512), 0, st, a)
-        if (kg) switch (g.TT * 16 + g.NC) {
-            case 32 * 16 + 1: AID_W4R_KS(32, 1); break;
-            case 32 * 16 + 2: AID_W4R_KS(32, 2); break;
-            case 32 * 16 + 4: AID_W4R_KS(32, 4); break;
-            case 32 * 16 + 8: AID_W4R_KS(32, 8); break;
-            case 16 * 16 + 1: AID_W4R_KS(16, 1); break;
-            case 16 * 16 + 2: AID_W4R_KS(16, 2); break;
-            case 16 * 16 + 4: AID_W4R_KS(16, 4); break;
-            case 16 * 16 + 8: AID_W4R_KS(16, 8); break;
-            default: aid_set_error("aid_conv2d: row-shared K-group tile shape not instantiated"); return AID_E_BADARG;
-        } else
-        switch (g.TT * 16 + g.NC) {
-            case 64 * 16 + 1: AID_W4R(64, 1, 2, 0); break;
-            case 64 * 16 + 2: AID_W4R(64, 2, 2, 0); break;
-            case 64 * 16 + 4: AID_W4R(64, 4, 2, 0); break;
-            case 32 * 16 + 1: AID_W4R(32, 1, 2, 0); break;
-            case 32 * 16 + 2: AID_W4R(32, 2, 2, 0); break;
-            case 32 * 16 + 4: AID_W4R(32, 4, 2, 0); break;
-            case 32 * 16 + 8: AID_W4R(32, 8, 2, 0); break;
-            case 16 * 16 + 1: AID_W4R(16, 1, 2, 0); break;
-            case 16 * 16 + 2: AID_W4R(16, 2, 2, 0); break;
-            case 16 * 16 + 4: AID_W4R(16, 4, 2, 0); break;
-            case 16 * 16 + 8: AID_W4R(16, 8, 2, 0); break;
-            default: aid_set_error("aid_conv2d: row-shared tile shape not instantiated"); return AID_E_BADARG;
-        }
-        AID_CHECK_LAUNCH();
-    }
-#undef AID_W4R
-#undef AID_W4R_KS
-    if (kg) aid_note_kernel("conv53_wino4r_ks_kernel");
-    else aid_note_kernel(m96 ? "conv53_wino4r_kernel(64+32)" : (a.splits == 2 ? "conv53_wino4r_kernel(split-K)" : (plan[0].NC == 1 ? "conv53_wino4r_kernel" : "conv53_wino4r_kernel(multi-class)")));
-    return AID_OK;
-}
-
-// ---- F(8,3) row-shared tiles: geometry, eligibility, launch ---------------------------------------------------------------------------------------
-// ng: groups per tile (64 for the 64-channel tile = 512 positions, 128 for the 32-channel remainder tile of 96-channel layers).  Instantiated:
-// 64 groups -- TT = 64: NC 1, 2 (RA = 8, 4); TT = 32: NC 1, 2, 4 (RA = 16, 8, 4); 128 groups -- TT = 64: NC 1, 2, 4 (RA = 16, 8, 4).  More classes per tile would not
-// leave room for two workgroups per CU (NC (RA + 4) staged rows x 10 planes).
-static int wino8r_tile(const aid_conv2d_params* p, int ng, Wino4rPlan* o) {
-    if (p->dilF < 1 || (p->F % p->dilF) || (p->T % 32)) return 0;
-    const int TT = (p->T % 64 == 0) ? 64 : 32;
-    if (ng == 128 && TT != 64) return 0;
-    const int GPR = TT / 8;
-    const int nrow = p->F / p->dilF;
-    const int max_nc = (ng == 64 && TT == 64) ? 2 : 4;
-    for (int NC = 1; NC <= max_nc; NC *= 2) {
-        if (p->dilF % NC) break;
-        const int RA = ng / (GPR * NC);
-        const int qd = (nrow + RA - 1) / RA;
-        if ((int64_t)qd * RA * 100 > (int64_t)nrow * 115) continue;     // (up to 15 % padding rows: 7, 14, 28 rows per class -> 8, 16, 32; the form choice weighs them)
-        o->TT = TT; o->NC = NC; o->quads = qd; o->ttiles = p->T / TT;
-        return 1;
-    }
-    return 0;
-}
-static int wino8r_geometry(const aid_conv2d_params* p, Wino4rPlan plan[2]) {
-    if (p->Cout_pad % 64 == 0) return wino8r_tile(p, 64, &plan[0]) ? 1 : 0;
-    if (p->Cout_pad % 96) return 0;
-    if (!wino8r_tile(p, 64, &plan[0]) || plan[0].TT != 64) return 0;
-    if (!wino8r_tile(p, 128, &plan[1])) return 0;
-    return 2;
+// K-group instances (conv53_wino8r_ks_kernel): a launch none of whose CUs would hold two tiles.  Per-layer A/B against the plain F(8,3) tiles and
+// F(4,3) (profiles/r04_ks_probe.txt): -12 ... -18 % on the <= 256-tile launches (batch 1: levels 0, 3, 4, 5; batch 2: level 6), within +-2 % of the
+// plain tiles elsewhere (where they are not used: the hardware's dynamic dispatch of two independent workgroups per CU is the safer schedule).
+// AID_W8R_KS (experiment builds): 0 never, 1 always, 2 also the launches of 2 r + 1 half-rounds (512 < tiles <= 768).
+static bool wino8r_ks_wanted(const WinoRPlan& pl) {
+    static const int force = w4r_env("AID_W8R_KS", -1);
+    if (force == 0 || force == 1) return force != 0;
+    if (force == 2 && pl.tiles > 512 && pl.tiles <= 768) return true;
+    return pl.tiles <= 256;
 }
 
 // Which Winograd form the row-shared kernels want for a 5x3 layer of this LAUNCH shape: 8 (F(8,3)), 4 (F(4,3)) or 0 (no Winograd-domain input).
@@ -1514,120 +1350,126 @@ static int wino8r_geometry(const aid_conv2d_params* p, Wino4rPlan plan[2]) {
 // (x 1.2 for a single tile per CU -- x 1.03 for F(8,3), whose K-group instances put eight waves on that tile); the cheaper form takes the launch, ties go to F(4,3) (its smaller tiles leave the shorter tail).  Against the
 // per-layer A/B of both kernels at batch 1, 2, 3, 4 and 8 (profiles/r04_streamk_probe.txt) this picks the faster kernel on all but a handful of
 // shapes, where it is within 5 %.  A function of the launch shape, B included: equal launches (the same sub-batch size) take equal kernels.
-static int wino_form_choice(const aid_conv2d_params* p) {
-    if (!wino_v_shape_ok(p->Cin, p->Cout, p->T)) return 0;
-    Wino4rPlan p4[2], p8[2];
-    const int n4 = wino4r_geometry(p, p4);
-    const int n8 = (p->T % 32 == 0) ? wino8r_geometry(p, p8) : 0;
-    if (!n8) return (n4 || p->T >= 32) ? 4 : 0;
-    if (!n4) return 8;
-    auto cost = [&](const Wino4rPlan* pl, int nl, int per_tile) {
-        int64_t tiles = 0;
-        for (int l = 0; l < nl; ++l)
-            tiles += (int64_t)p->B * (p->dilF / pl[l].NC) * pl[l].quads * pl[l].ttiles * (nl == 2 ? p->Cout_pad / 96 : p->Cout_pad / 64);
-        const int64_t per_cu = (tiles + 255) / 256;
-        // (launches of one tile per CU take the K-group instances where there is one: two waves per SIMD on the one tile, 1.03 instead of 1.2)
-        const bool kgroups = per_tile == 5 || (nl == 1 && pl[0].TT <= 32);     // (wino8r_ks_wanted / wino4r_ks_wanted)
+static int wino_form_choice(int B, int Cin, int Cout, int F, int T, int dilF) {
+    if (!wino_v_shape_ok(Cin, Cout, T)) return 0;
+    const WinoRPlan p4 = wino_r_plan_of(4, B, Cin, Cout, F, T, dilF), p8 = wino_r_plan_of(8, B, Cin, Cout, F, T, dilF);
+    if (!p8.nl) return (p4.nl || T >= 32) ? 4 : 0;
+    if (!p4.nl) return 8;
+    auto cost = [](const WinoRPlan& pl) {
+        const int per_tile = pl.form == 8 ? 5 : 3;
+        const int64_t per_cu = (pl.tiles + 255) / 256;
+        // (launches of one tile per CU take the K-group instances where there is one: two waves per SIMD on the one tile, 1.03 instead of 1.2;
+        //  the rule of wino8r_ks_wanted / wino4r_ks_wanted without the overrides of experiment builds)
+        const bool kgroups = pl.form == 8 || (pl.nl == 1 && pl.f[0].TT <= 32);
         return per_cu * per_tile * (per_cu == 1 ? (kgroups ? 103 : 120) : 100);
     };
-    return cost(p8, n8, 5) < cost(p4, n4, 3) ? 8 : 4;
+    return cost(p8) < cost(p4) ? 8 : 4;
 }
 
-// K-group instances (conv53_wino8r_ks_kernel): a launch none of whose CUs would hold two tiles.  Per-layer A/B against the plain F(8,3) tiles and
-// F(4,3) (profiles/r04_ks_probe.txt): -12 ... -18 % on the <= 256-tile launches (batch 1: levels 0, 3, 4, 5; batch 2: level 6), within +-2 % of the
-// plain tiles elsewhere (where they are not used: the hardware's dynamic dispatch of two independent workgroups per CU is the safer schedule).
-// AID_W8R_KS (experiment builds): 0 never, 1 always, 2 also the launches of 2 r + 1 half-rounds (512 < tiles <= 768).
-static bool wino8r_ks_wanted(int64_t ntiles) {
-    static const int force = w4r_env("AID_W8R_KS", -1);
-    if (force == 0 || force == 1) return force != 0;
-    if (force == 2 && ntiles > 512 && ntiles <= 768) return true;
-    return ntiles <= 256;
+// fin_mode (aid_kernels.h): argument check of the row-shared launcher
+static int wino_fin_check(const aid_conv2d_params* p) {
+    if (!p->fin_mode) return AID_OK;
+    AID_REQUIRE(p->fin_mode == 1 || p->fin_mode == 2, "aid_conv2d: fin_mode is 0, 1 or 2");
+    AID_REQUIRE(p->fin_count && p->fin_scale && (p->Cout % 8) == 0, "aid_conv2d: fin_mode needs fin_count, fin_scale and Cout % 8 == 0");
+    if (p->fin_mode == 1) AID_REQUIRE(p->stat_ws && p->fin_gamma, "aid_conv2d: fin_mode = 1 folds the stat_ws partials and needs fin_gamma");
+    else AID_REQUIRE(p->dot_ws && p->fin_stats, "aid_conv2d: fin_mode = 2 folds the dot_ws partials and needs the forward statistics in fin_stats");
+    return AID_OK;
 }
 
-
-static int launch_wino8r(const aid_conv2d_params* p, hipStream_t st) {
+// The launcher of the row-shared kernels, form = 4 (F(4,3)) or 8 (F(8,3)).  F(4,3) returns 1000 when the shape is better served by the 64|96 x 512 kernel.
+// A plan of more than 2^30 tiles is refused whatever the form: W4rGeo counts tiles, and a split launch twice as many, in 32 bits (no shipped shape comes near).
+static int launch_wino_r(int form, const aid_conv2d_params* p, hipStream_t st) {
     const float* const zero = wino_zero_page();
     if (!zero) return AID_E_LAUNCH;
-    Wino4rPlan plan[2];
-    const int nl = wino8r_geometry(p, plan);
-    AID_REQUIRE(nl, "aid_conv2d: x_wino = 2 (F(8,3)) needs a shape aid_conv2d_wino8_supported() answers 1 for");
-    const bool m96 = nl == 2;
+    const WinoRPlan pl = wino_r_plan(form, p->B, p->Cout_pad, p->F, p->T, p->dilF);
+    if (!pl.nl && form == 4) return 1000;
+    AID_REQUIRE(pl.nl, "aid_conv2d: x_wino = 2 (F(8,3)) needs a shape aid_conv2d_wino8_supported() answers 1 for");
+    AID_REQUIRE(2 * pl.tiles <= INT32_MAX, "aid_conv2d: the row-shared kernels count the tiles of a launch (twice, when split) in 32 bits");
+    { const int rc = wino_fin_check(p); if (rc != AID_OK) return rc; }
+    const bool pair = pl.nl == 2;
+    const bool kg = form == 8 ? wino8r_ks_wanted(pl) : wino4r_ks_wanted(pl, p->Cin);
     ConvWinoRDev a;
     a.p = *p;
     a.zero = zero;
-    a.nchunks = p->Cin / 2;
-    a.dot_all = m96 ? 1 : 0;
+    a.dot_all = pair ? 1 : 0;
     a.splits = 1; a.part = nullptr; a.flags = nullptr;
-    W4rGeo geo[2];
-    int dot_base = 0;
-    for (int l = 0; l < nl; ++l) {
-        const Wino4rPlan& g = plan[l];
-        W4rGeo& ge = geo[l];
-        ge.quads = g.quads; ge.ttiles = g.ttiles;
-        ge.rgroups = p->dilF / g.NC;
-        ge.ny = m96 ? p->Cout_pad / 96 : p->Cout_pad / 64;
-        ge.m_base = l == 0 ? 0 : 64;
-        ge.m_stride = m96 ? 96 : 64;
-        ge.dot_base = dot_base;
-        dot_base += ge.rgroups * g.quads * g.ttiles;
-        ge.ntiles = p->B * ge.rgroups * g.quads * g.ttiles * ge.ny;
+    if (form == 4 && !kg && wino4r_splits(pl, p->B, p->Cin) == 2 && p->ws && p->ws_bytes >= aid_w4r_split_bytes(pl.tiles)) {
+        a.splits = 2;
+        a.flags = reinterpret_cast<unsigned*>(p->ws);
+        a.part = p->ws + AID_W4R_SPLIT_FLAG_BYTES / 4;
+    }
+    a.nchunks = (kg || a.splits == 2) ? p->Cin / 4 : p->Cin / 2;
+    a.fin_total = (int)(pl.tiles / p->B);                  // tiles per sample (before a split doubles the workgroups)
+    for (int l = 0; l < 2; ++l) {                           // (one family: g[1] repeats g[0])
+        const WinoRFamily& f = pl.f[pair ? l : 0];
+        W4rGeo& ge = a.g[l];
+        ge.quads = f.quads; ge.ttiles = f.ttiles; ge.rgroups = f.rgroups; ge.ny = f.ny;
+        ge.m_base = f.m_base; ge.m_stride = f.m_stride; ge.dot_base = f.dot_base;
+        ge.ntiles = (int)f.ntiles * a.splits;
         ge.per_xcd = (ge.ntiles + 7) / 8;
     }
-    const int64_t ntl = (int64_t)geo[0].ntiles + (m96 ? geo[1].ntiles : 0);
-    { const int rc = wino_fin_check(p); if (rc != AID_OK) return rc; }
-    a.fin_total = (int)(ntl / p->B);                       // tiles per sample
-    const bool kg = wino8r_ks_wanted(ntl);
-    if (kg) a.nchunks = p->Cin / 4;
-#define AID_W8R(TTv, NCv, WGMv, NC1v) do { \
-        if (kg) hipLaunchKernelGGL((conv53_wino8r_ks_kernel<TTv, NCv, WGMv, NC1v>), grid, dim3(512), 0, st, a); \
-        else hipLaunchKernelGGL((conv53_wino8r_kernel<TTv, NCv, WGMv, NC1v>), grid, dim3(256), 0, st, a); } while (0)
-    if (m96) {
-        a.g[0] = geo[0]; a.g[1] = geo[1];
-        const dim3 grid((unsigned)(8 * (geo[0].per_xcd + geo[1].per_xcd)));
-        switch (plan[0].NC * 16 + plan[1].NC) {               // (both families: TT = 64)
-            case 1 * 16 + 1: AID_W8R(64, 1, 2, 1); break;
-            case 1 * 16 + 2: AID_W8R(64, 1, 2, 2); break;
-            case 1 * 16 + 4: AID_W8R(64, 1, 2, 4); break;
-            case 2 * 16 + 1: AID_W8R(64, 2, 2, 1); break;
-            case 2 * 16 + 2: AID_W8R(64, 2, 2, 2); break;
-            case 2 * 16 + 4: AID_W8R(64, 2, 2, 4); break;
-            default: aid_set_error("aid_conv2d: F(8,3) pair tile shape not instantiated"); return AID_E_BADARG;
+    const dim3 grid((unsigned)(8 * (a.g[0].per_xcd + (pair ? a.g[1].per_xcd : 0))));
+    // The instances: (TT, NC) of family 0 and NC1 of the remainder family (0: one family).  Both families of a pair have TT = 64 (aid_wino_plan.h).
+    const int shape = (pl.f[0].TT * 16 + pl.f[0].NC) * 16 + (pair ? pl.f[1].NC : 0);
+#define AID_WR_CASE(TTv, NCv, NC1v) case (TTv * 16 + NCv) * 16 + NC1v
+    if (form == 4) {
+        const bool short_k = p->Cin <= 128 && a.splits == 1;     // three workgroups per CU (two LDS buffers) for the short-K layers (re-measured in round 3 with
+                                                                 // sub-batch streams: Cin <= 128 / 64 / never = 42.33 / 42.08 / 42.17 evaluations/s)
+#define AID_W4R(TTv, NCv, WGMv, NC1v) AID_WR_CASE(TTv, NCv, NC1v): do { \
+        if constexpr (TTv <= 32 && NC1v == 0) { if (kg) { hipLaunchKernelGGL((conv53_wino4r_ks_kernel<TTv, NCv>), grid, dim3(512), 0, st, a); break; } } \
+        if constexpr (TTv == 64 && NCv <= 2) { if (short_k) { hipLaunchKernelGGL((conv53_wino4r_kernel<TTv, NCv, WGMv, 2, 3, 4, NC1v>), grid, dim3(256), 0, st, a); break; } } \
+        if constexpr (NC1v == 0 && WGMv == 2) { if (a.splits == 2) { hipLaunchKernelGGL((conv53_wino4r_kernel<TTv, NCv, WGMv, 3, 2, 4, 0, true>), grid, dim3(256), 0, st, a); break; } } \
+        hipLaunchKernelGGL((conv53_wino4r_kernel<TTv, NCv, WGMv, 3, 2, 4, NC1v>), grid, dim3(256), 0, st, a); } while (0); break
+        switch (shape) {
+            AID_W4R(64, 1, 2, 1); AID_W4R(64, 1, 2, 2);
+            AID_W4R(64, 2, 2, 1); AID_W4R(64, 2, 2, 2);
+            AID_W4R(64, 4, 2, 1); AID_W4R(64, 4, 2, 2);
+            AID_W4R(64, 1, 2, 0); AID_W4R(64, 2, 2, 0); AID_W4R(64, 4, 2, 0);
+            AID_W4R(32, 1, 2, 0); AID_W4R(32, 2, 2, 0); AID_W4R(32, 4, 2, 0); AID_W4R(32, 8, 2, 0);      // (TT <= 32: and the K-group instance)
+            AID_W4R(16, 1, 2, 0); AID_W4R(16, 2, 2, 0); AID_W4R(16, 4, 2, 0); AID_W4R(16, 8, 2, 0);
+            default:
+                aid_set_error(pair ? "aid_conv2d: row-shared pair tile shape not instantiated"
+                                   : (kg ? "aid_conv2d: row-shared K-group tile shape not instantiated" : "aid_conv2d: row-shared tile shape not instantiated"));
+                return AID_E_BADARG;
         }
-        AID_CHECK_LAUNCH();
+#undef AID_W4R
     } else {
-        const Wino4rPlan& g = plan[0];
-        a.g[0] = geo[0]; a.g[1] = geo[0];
-        const dim3 grid((unsigned)(8 * geo[0].per_xcd));
-        switch (g.TT * 16 + g.NC) {
-            case 64 * 16 + 1: AID_W8R(64, 1, 2, 0); break;
-            case 64 * 16 + 2: AID_W8R(64, 2, 2, 0); break;
-            case 32 * 16 + 1: AID_W8R(32, 1, 2, 0); break;
-            case 32 * 16 + 2: AID_W8R(32, 2, 2, 0); break;
-            case 32 * 16 + 4: AID_W8R(32, 4, 2, 0); break;
-            default: aid_set_error("aid_conv2d: F(8,3) tile shape not instantiated"); return AID_E_BADARG;
+#define AID_W8R(TTv, NCv, WGMv, NC1v) AID_WR_CASE(TTv, NCv, NC1v): \
+        if (kg) hipLaunchKernelGGL((conv53_wino8r_ks_kernel<TTv, NCv, WGMv, NC1v>), grid, dim3(512), 0, st, a); \
+        else hipLaunchKernelGGL((conv53_wino8r_kernel<TTv, NCv, WGMv, NC1v>), grid, dim3(256), 0, st, a); \
+        break
+        switch (shape) {
+            AID_W8R(64, 1, 2, 1); AID_W8R(64, 1, 2, 2); AID_W8R(64, 1, 2, 4);
+            AID_W8R(64, 2, 2, 1); AID_W8R(64, 2, 2, 2); AID_W8R(64, 2, 2, 4);
+            AID_W8R(64, 1, 2, 0); AID_W8R(64, 2, 2, 0);
+            AID_W8R(32, 1, 2, 0); AID_W8R(32, 2, 2, 0); AID_W8R(32, 4, 2, 0);
+            default: aid_set_error(pair ? "aid_conv2d: F(8,3) pair tile shape not instantiated" : "aid_conv2d: F(8,3) tile shape not instantiated"); return AID_E_BADARG;
         }
-        AID_CHECK_LAUNCH();
-    }
 #undef AID_W8R
-    if (kg) aid_note_kernel(m96 ? "conv53_wino8r_ks_kernel(64+32)" : "conv53_wino8r_ks_kernel");
-    else aid_note_kernel(m96 ? "conv53_wino8r_kernel(64+32)" : (plan[0].NC == 1 ? "conv53_wino8r_kernel" : "conv53_wino8r_kernel(multi-class)"));
+    }
+#undef AID_WR_CASE
+    AID_CHECK_LAUNCH();
+    const char* name;
+    if (form == 4) {
+        if (kg) name = "conv53_wino4r_ks_kernel";
+        else if (pair) name = "conv53_wino4r_kernel(64+32)";
+        else if (a.splits == 2) name = "conv53_wino4r_kernel(split-K)";
+        else name = pl.f[0].NC == 1 ? "conv53_wino4r_kernel" : "conv53_wino4r_kernel(multi-class)";
+    } else {
+        if (kg) name = pair ? "conv53_wino8r_ks_kernel(64+32)" : "conv53_wino8r_ks_kernel";
+        else if (pair) name = "conv53_wino8r_kernel(64+32)";
+        else name = pl.f[0].NC == 1 ? "conv53_wino8r_kernel" : "conv53_wino8r_kernel(multi-class)";
+    }
+    aid_note_kernel(name);
     return AID_OK;
 }
 
 extern "C" int aid_conv2d_wino8_supported(int Cin, int Cout, int F, int T, int dilF) {
-    if (!wino_v_shape_ok(Cin, Cout, T) || (T % 32)) return 0;
-    aid_conv2d_params q = {};
-    q.B = 1; q.Cin = Cin; q.Cout = Cout; q.F = F; q.T = T; q.dilF = dilF; q.KH = 5; q.KW = 3;
-    aid_conv2d_pack_dims(Cin, Cout, &q.Cin_pad, &q.Cout_pad);
-    Wino4rPlan plan[2];
-    return wino8r_geometry(&q, plan) ? 1 : 0;
+    return (wino_v_shape_ok(Cin, Cout, T) && (T % 32) == 0 && wino_r_plan_of(8, 1, Cin, Cout, F, T, dilF).nl) ? 1 : 0;
 }
 
 extern "C" int aid_conv2d_wino_form(int B, int Cin, int Cout, int F, int T, int dilF) {
-    aid_conv2d_params q = {};
-    q.B = B; q.Cin = Cin; q.Cout = Cout; q.F = F; q.T = T; q.dilF = dilF; q.KH = 5; q.KW = 3;
-    aid_conv2d_pack_dims(Cin, Cout, &q.Cin_pad, &q.Cout_pad);
-    const int f = wino_form_choice(&q);
+    const int f = wino_form_choice(B, Cin, Cout, F, T, dilF);
     if (f == 4 && !aid_conv2d_wino_input_ok(B, Cin, Cout, F, T, dilF)) return 0;
     return f;
 }
@@ -1637,25 +1479,15 @@ extern "C" int aid_conv2d_fin_supported(int B, int Cin, int Cout, int F, int T, 
     if (B < 1 || (Cout % 8) || !wino_v_shape_ok(Cin, Cout, T)) return 0;
     if (x_wino == 2) return aid_conv2d_wino8_supported(Cin, Cout, F, T, dilF);
     if (x_wino != 1) return 0;
-    aid_conv2d_params q = {};
-    q.B = B; q.Cin = Cin; q.Cout = Cout; q.F = F; q.T = T; q.dilF = dilF; q.KH = 5; q.KW = 3;
-    aid_conv2d_pack_dims(Cin, Cout, &q.Cin_pad, &q.Cout_pad);
-    Wino4rPlan plan[2];
-    return wino4r_geometry(&q, plan) ? 1 : 0;
+    return wino_r_plan_of(4, B, Cin, Cout, F, T, dilF).nl ? 1 : 0;
 }
 
 // scratch of the split-K instances (aid_kernels.h: ws): 0 when a launch of this shape is not split
 extern "C" int64_t aid_conv2d_wino_split_ws_bytes(int B, int Cin, int Cout, int F, int T, int dilF) {
     if (!wino_v_shape_ok(Cin, Cout, T)) return 0;
-    aid_conv2d_params q = {};
-    q.B = B; q.Cin = Cin; q.Cout = Cout; q.F = F; q.T = T; q.dilF = dilF; q.KH = 5; q.KW = 3;
-    aid_conv2d_pack_dims(Cin, Cout, &q.Cin_pad, &q.Cout_pad);
-    Wino4rPlan plan[2];
-    const int nl = wino4r_geometry(&q, plan);
-    if (nl != 1) return 0;
-    const int64_t ntiles = (int64_t)B * (dilF / plan[0].NC) * plan[0].quads * plan[0].ttiles * (q.Cout_pad / 64);
-    if (wino4r_ks_wanted(&q, nl, plan, ntiles)) return 0;       // (the K-group instance takes the launch: no scratch)
-    return wino4r_splits(&q, nl, ntiles) == 2 ? aid_w4r_split_bytes(ntiles) : 0;
+    const WinoRPlan pl = wino_r_plan_of(4, B, Cin, Cout, F, T, dilF);
+    if (pl.nl != 1 || wino4r_ks_wanted(pl, Cin)) return 0;      // (the K-group instance takes the launch: no scratch)
+    return wino4r_splits(pl, B, Cin) == 2 ? aid_w4r_split_bytes(pl.tiles) : 0;
 }
 
 // Output positions per tile of the 64-wide F(4,3) kernels: 512, or 256 when a launch would otherwise put fewer than ~0.75
@@ -1680,12 +1512,7 @@ extern "C" int aid_conv2d_wino_input_supported(int Cin, int Cout, int T) { retur
 extern "C" int aid_conv2d_wino_input_ok(int B, int Cin, int Cout, int F, int T, int dilF) {
     if (!wino_v_shape_ok(Cin, Cout, T)) return 0;
     if (T >= 32) return 1;
-    int cip, cop;
-    aid_conv2d_pack_dims(Cin, Cout, &cip, &cop);
-    aid_conv2d_params q{};
-    q.B = B; q.Cin = Cin; q.Cout = Cout; q.F = F; q.T = T; q.dilF = dilF; q.Cout_pad = cop;
-    Wino4rPlan plan[2];
-    return wino4r_geometry(&q, plan) == 1 ? 1 : 0;
+    return wino_r_plan_of(4, B, Cin, Cout, F, T, dilF).nl == 1 ? 1 : 0;
 }
 
 // partials per (sample, group) of the forward (sum, sum of squares) option: the row-shared kernel only
@@ -1699,13 +1526,7 @@ extern "C" int aid_conv2d_stat_partials(int B, int Cin, int Cout, int F, int T, 
     const int mblk = (cop % 64 == 0) ? 64 : ((cop % 96 == 0) ? 96 : 0);
     const int cpg = Cout / 8;
     if (!mblk || (cpg % 4) || (mblk % cpg)) return 0;
-    aid_conv2d_params q{};
-    q.B = B; q.Cin = Cin; q.Cout = Cout; q.F = F; q.T = T; q.dilF = dilF; q.Cout_pad = cop;
-    Wino4rPlan plan[2];
-    const int nl = x_wino == 2 ? wino8r_geometry(&q, plan) : wino4r_geometry(&q, plan);
-    int n = 0;
-    for (int l = 0; l < nl; ++l) n += (dilF / plan[l].NC) * plan[l].quads * plan[l].ttiles;
-    return n;
+    return wino_r_plan(x_wino == 2 ? 8 : 4, B, cop, F, T, dilF).slots;
 }
 
 // tiles per sample of the F(4,3) kernels (64|96 x 512 tiles) when the per-tile <y, aux> partials are well defined
@@ -1718,13 +1539,8 @@ extern "C" int aid_conv2d_dot_partials(int B, int Cin, int Cout, int F, int T, i
     const int cpg = Cout / 8;
     if (!mblk || (cpg % 4) || (mblk % cpg)) return 0;
     if (x_wino && wino_v_shape_ok(Cin, Cout, T)) {           // the row-shared kernel takes the launch when its geometry fits
-        aid_conv2d_params q{};
-        q.B = B; q.Cin = Cin; q.Cout = Cout; q.F = F; q.T = T; q.dilF = dilF; q.Cout_pad = cop;
-        Wino4rPlan plan[2];
-        const int nl = x_wino == 2 ? wino8r_geometry(&q, plan) : wino4r_geometry(&q, plan);
-        int n = 0;
-        for (int l = 0; l < nl; ++l) n += (dilF / plan[l].NC) * plan[l].quads * plan[l].ttiles;
-        if (nl || x_wino == 2) return n;
+        const WinoRPlan pl = wino_r_plan(x_wino == 2 ? 8 : 4, B, cop, F, T, dilF);
+        if (pl.nl || x_wino == 2) return pl.slots;
     }
     const int nblk = wino_tile_n(B, cop, F, T);
     int TT = aid_pow2ceil(T);
@@ -1745,7 +1561,7 @@ static int conv53_wino_v(const aid_conv2d_params* p, hipStream_t st) {
         AID_REQUIRE(wino_v_shape_ok(p->Cin, p->Cout, p->T) && (p->T % 32) == 0, "aid_conv2d: shape not supported with x_wino = 2 (see aid_conv2d_wino_form)");
         AID_REQUIRE(p->x.sF >= 10 * (p->T / 8) && (int64_t)4 * p->x.sC < (1LL << 31), "aid_conv2d: x_wino = 2 rows are [10][T/8]");
         AID_REQUIRE(al4(p->x) && al4(p->y) && (!p->res.p || al4(p->res)) && (!p->aux.p || al4(p->aux)), "aid_conv2d: x_wino views must be 16-byte aligned");
-        return launch_wino8r(p, st);
+        return launch_wino_r(8, p, st);
     }
     AID_REQUIRE(p->wp_wino && p->wino_taps == 30 && p->KH == 5 && p->KW == 3 && !p->in_scale && p->act == 0,
                 "aid_conv2d: x_wino needs the 30-tap Winograd pack of a 5x3 layer and no in-kernel prologue");
@@ -1753,7 +1569,7 @@ static int conv53_wino_v(const aid_conv2d_params* p, hipStream_t st) {
     AID_REQUIRE(p->x.sF >= 6 * (p->T / 4) && (int64_t)4 * p->x.sC < (1LL << 31), "aid_conv2d: x_wino rows are [6][T/4]");
     AID_REQUIRE(al4(p->x) && al4(p->y) && (!p->res.p || al4(p->res)) && (!p->aux.p || al4(p->aux)), "aid_conv2d: x_wino views must be 16-byte aligned");
     int rc;
-    rc = launch_wino4r(p, st);                              // row-shared tiles, two workgroups per CU (when the geometry fits)
+    rc = launch_wino_r(4, p, st);                             // row-shared tiles, two workgroups per CU (when the geometry fits)
     if (rc != 1000) return rc;
     AID_REQUIRE(!p->fin_mode, "aid_conv2d: fin_mode needs the row-shared kernel (aid_conv2d_fin_supported)");
     if (p->Cout_pad % 64 == 0 && wino_tile_n(p->B, p->Cout_pad, p->F, p->T) == 256)

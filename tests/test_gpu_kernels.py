@@ -208,7 +208,31 @@ WINO_V_CASES = [
     (1, 128, 128, 160, 128, 32, 0, True),    # 160 tiles, <64, 4>
     (1, 256, 256, 448, 32, 64, 1, False),    # <32, 8>
     (1, 96, 64, 36, 128, 1, 1, True),        # 24 chunks per half
+    # the instances no case above selects (which <TT, NC, NC1> and which arm a shape takes: csrc/aid_wino_plan.h), at their smallest shapes
+    (1, 8, 96, 8, 64, 2, 1, True),           # pair <64, 1> + remainder over two classes <64, 2> (4 rows per class), short-K instance
+    (1, 8, 64, 8, 32, 1, 0, True),           # K-group <32, 1>: one tile
+    # Cin > 128: the three-buffer instances of the shapes whose short-K (two-buffer) instances the cases above run
+    (1, 192, 96, 8, 64, 1, 1, True),         # pair <64, 1> + <64, 1>
+    (1, 192, 96, 8, 64, 2, 0, True),         # pair <64, 1> + <64, 2>
+    (2, 192, 64, 12, 64, 2, 1, False),       # <64, 2>: 6 rows per class, batch 2 (not split)
+    # more than 256 tiles of the T <= 32 tile shapes: the plain four-wave instances (the small cases above run the K-group instances)
+    (2, 8, 64, 1032, 32, 1, 1, True),        # <32, 1>, 258 tiles
+    (2, 8, 64, 1040, 32, 52, 0, False),      # <32, 2>: 20 rows per class, 260 tiles
+    (2, 8, 64, 1040, 32, 104, 1, True),      # <32, 4>: 10 rows per class
+    (2, 8, 64, 1080, 32, 120, 0, True),      # <32, 8>: 9 rows per class, 270 tiles
+    (2, 8, 64, 2064, 16, 1, 1, False),       # <16, 1>, 258 tiles
+    (2, 8, 64, 2080, 16, 52, 0, True),       # <16, 2>: 40 rows per class, 260 tiles
+    (2, 8, 64, 2080, 16, 104, 1, True),      # <16, 4>: 20 rows per class
+    (2, 8, 64, 2080, 16, 208, 0, False),     # <16, 8>: 10 rows per class
 ]
+# the noted name of the cases that exist for one instance each
+WINO_V_NOTED = {(1, 8, 96, 8, 64, 2): "conv53_wino4r_kernel(64+32)", (1, 8, 64, 8, 32, 1): "conv53_wino4r_ks_kernel",
+                (1, 192, 96, 8, 64, 1): "conv53_wino4r_kernel(64+32)", (1, 192, 96, 8, 64, 2): "conv53_wino4r_kernel(64+32)",
+                (2, 192, 64, 12, 64, 2): "conv53_wino4r_kernel(multi-class)",
+                (2, 8, 64, 1032, 32, 1): "conv53_wino4r_kernel", (2, 8, 64, 1040, 32, 52): "conv53_wino4r_kernel(multi-class)",
+                (2, 8, 64, 1040, 32, 104): "conv53_wino4r_kernel(multi-class)", (2, 8, 64, 1080, 32, 120): "conv53_wino4r_kernel(multi-class)",
+                (2, 8, 64, 2064, 16, 1): "conv53_wino4r_kernel", (2, 8, 64, 2080, 16, 52): "conv53_wino4r_kernel(multi-class)",
+                (2, 8, 64, 2080, 16, 104): "conv53_wino4r_kernel(multi-class)", (2, 8, 64, 2080, 16, 208): "conv53_wino4r_kernel(multi-class)"}
 
 
 @pytest.mark.parametrize("case", WINO_V_CASES)
@@ -259,6 +283,7 @@ def test_conv2d_winograd_domain_input(L, case):
     kern = L.lib().aid_last_kernel().decode()
     # (launches of at most 256 tiles on the T <= 32 tile shapes take the K-group instance -- eight waves per tile, the K halves summed through LDS -- and need no scratch)
     assert ("wino4r_ks" in kern) == (Cout % 64 == 0 and T <= 32 and tiles <= 256 and "wino4r" in kern), (kern, tiles)
+    assert kern == WINO_V_NOTED.get(case[:6], kern)
     assert (need > 0) == (B == 1 and Cout % 64 == 0 and tiles <= 230 and "wino4r" in kern and "wino4r_ks" not in kern), (need, kern)
     if need:
         ws = torch.zeros(need // 4 + 8, device=DEV)
@@ -301,10 +326,11 @@ WINO8_CASES = [
     (4, 96, 96, 128, 256, 2, 1, True),       # pair <64, 1> + <64, 1>, 384 tiles
     (30, 64, 96, 48, 64, 2, 0, False),       # pair <64, 1> + <64, 2>, 270 tiles
     (44, 96, 96, 16, 128, 4, 1, True),       # pair <64, 2> + <64, 4>, 264 tiles
+    (2, 8, 64, 1040, 64, 52, 1, True),       # <64, 2>, 260 tiles: 20 rows per class (no other case runs the plain instance of this shape)
 ]
 # launches of at most 256 tiles (one per CU) take the K-group instances: one eight-wave workgroup per tile, two K groups (conv53_wino8r_ks_kernel)
 WINO8_PLAIN = {(4, 64, 64, 96, 1024), (5, 128, 128, 64, 512), (5, 128, 128, 448, 32), (5, 64, 128, 448, 32), (9, 64, 128, 256, 32), (4, 96, 96, 128, 256),
-               (30, 64, 96, 48, 64), (44, 96, 96, 16, 128)}
+               (30, 64, 96, 48, 64), (44, 96, 96, 16, 128), (2, 8, 64, 1040, 64)}
 
 
 @pytest.mark.parametrize("case", WINO8_CASES)
@@ -353,6 +379,7 @@ def test_conv2d_winograd8_domain_input(L, case):
     torch.cuda.synchronize()
     kern = L.lib().aid_last_kernel().decode()
     assert "wino8r" in kern and ("wino8r_ks" in kern) == ((B, Cin, Cout, Fd, T) not in WINO8_PLAIN), kern
+    assert case[:6] != (2, 8, 64, 1040, 64, 52) or kern == "conv53_wino8r_kernel(multi-class)"
     err = rel_l2(y.cpu(), ref)
     assert err < 1e-5, err
     # (3) the pack kernel writes the same F(8,3) packs as the torch helper

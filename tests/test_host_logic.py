@@ -491,6 +491,79 @@ def test_winograd_form_choice_is_a_function_of_the_launch_shape():
     assert L.aid_conv2d_fin_supported(4, 128, 128, 256, 256, 2, 0) == 0 and L.aid_conv2d_fin_supported(4, 2, 64, 64, 1024, 1, 1) == 0
 
 
+def _wino_r_host_grid():
+    import json
+    with open(os.path.join(GOLDEN, "wino_r_host_grid.json")) as f:
+        return json.load(f)
+
+
+def test_row_shared_winograd_host_queries_answer_as_recorded():
+    """The seven host queries of the row-shared Winograd kernels (form, F(8,3) support, Winograd-input support, fin_mode support, split-K scratch,
+    statistics and dot partials) over the recorded grid of launch shapes -- the seven levels at every dilation and batch 1, 2, 3, 4, 8, T = 16 ... 96,
+    F not a multiple of the dilation, few-channel and 96 / 192-channel layers, the shapes the kernels decline: every answer equals the one recorded
+    from the library of the commit the fixture names (tools/wino_r_host_grid.py), before the queries read one tile plan (csrc/aid_wino_plan.h)."""
+    from audio_inpainting_diffusion_amd import _lib
+    L = _lib.lib()
+    grid = _wino_r_host_grid()
+    assert len(grid["commit"]) == 40 and len(grid["rows"]) == 1320
+    for rec in grid["rows"]:
+        s = rec[:6]
+        got = s + [L.aid_conv2d_wino_form(*s), L.aid_conv2d_wino8_supported(*s[1:]), L.aid_conv2d_wino_input_ok(*s), L.aid_conv2d_wino_split_ws_bytes(*s),
+                   [L.aid_conv2d_fin_supported(*s, x) for x in (0, 1, 2)], [L.aid_conv2d_stat_partials(*s, x) for x in (0, 1, 2)],
+                   [L.aid_conv2d_dot_partials(*s, x) for x in (0, 1, 2)]]
+        assert got == rec, (dict(zip(grid["columns"], rec)), got)
+
+
+def test_tile_plan_header_runs_clean_under_sanitizers_and_counts_what_the_library_counts(tmp_path):
+    """csrc/aid_wino_plan.h is plain host C++: a stand-alone program built with -fsanitize=address,undefined walks the recorded grid and extreme shapes
+    (B = 4096, F = 2^20, dilation 2^10, T = 2^16) for both forms and exits clean; the plan's partial slots per sample are aid_conv2d_stat_partials of the
+    library, and its tile count is B * (dilF / NC) * quads * ttiles * Cout tiles summed over the families, in unbounded integers."""
+    import shutil
+    import subprocess
+    from audio_inpainting_diffusion_amd import _lib
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++")
+    L = _lib.lib()
+    rows = [tuple(r[:6]) for r in _wino_r_host_grid()["rows"]]
+    extreme = [(4096, 64, c, 1 << 20, 1 << 16, d) for c in (64, 96, 256) for d in (1, 1 << 10)] + [(4096, 64, 64, (1 << 20) + 1, 1 << 16, 1 << 10), (1, 64, 96, 7, 16, 1)]
+    shapes = [(B, _lib.pack_dims(ci, co)[1], F, T, d) for B, ci, co, F, T, d in rows + extreme]
+    src = tmp_path / "plan.cpp"
+    src.write_text('#include <stdio.h>\n#include "aid_wino_plan.h"\nstatic const int S[][5] = {\n' + "".join("    {%d, %d, %d, %d, %d},\n" % s for s in shapes) + '''};
+int main() {
+    for (const auto& s : S)
+        for (int form = 4; form <= 8; form += 4) {
+            const WinoRPlan p = wino_r_plan(form, s[0], s[1], s[2], s[3], s[4]);
+            printf("%d", p.nl);
+            for (int l = 0; l < 2; ++l) printf(" %d %d %d %d %lld", p.f[l].TT, p.f[l].NC, p.f[l].quads, p.f[l].ttiles, (long long)p.f[l].ntiles);
+            printf(" %d %lld\\n", p.slots, (long long)p.tiles);
+        }
+    return 0;
+}
+''')
+    exe = tmp_path / "plan"
+    subprocess.check_call([gxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I" + os.path.join(ROOT, "audio_inpainting_diffusion_amd", "csrc"), str(src), "-o", str(exe)])
+    run = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert run.returncode == 0 and not run.stderr, run.stderr[-2000:]
+    out = [[int(v) for v in line.split()] for line in run.stdout.splitlines()]
+    assert len(out) == 2 * len(shapes)
+    checked = 0
+    for i, (B, cop, F, T, d) in enumerate(shapes):
+        for j, form in enumerate((4, 8)):
+            nl, fam, slots, tiles = out[2 * i + j][0], [out[2 * i + j][1:6], out[2 * i + j][6:11]], out[2 * i + j][11], out[2 * i + j][12]
+            ny = cop // (96 if nl == 2 else 64)
+            per_family = [B * (d // NC) * quads * ttiles * ny for TT, NC, quads, ttiles, _ in fam[:nl]]
+            assert [f[4] for f in fam[:nl]] == per_family and tiles == sum(per_family), (form, B, cop, F, T, d, out[2 * i + j])
+            assert fam[nl:] == [[0] * 5] * (2 - nl) and (nl > 0 or slots == 0)
+            assert slots == sum((d // NC) * quads * ttiles for TT, NC, quads, ttiles, _ in fam[:nl]) < 2 ** 31
+            if i < len(rows) and rows[i][1] == 64 and rows[i][2] in (64, 96, 128, 256):
+                assert slots == L.aid_conv2d_stat_partials(*rows[i], 1 if form == 4 else 2), (form, rows[i], slots)
+                checked += 1
+    assert checked >= 100
+    assert out[2 * len(rows)][0] == 1 and out[2 * len(rows)][12] == 4096 * (2 ** 20 // 4) * 1024 > 2 ** 31      # F(4,3), 64 channels, dilation 1: TT = 64, RA = 4
+
+
 def test_two_dimensional_winograd_choice_is_a_function_of_the_launch_shape():
     """aid_conv2d_wino2d_supported / _wanted / _positions (pure host functions): K = 256 levels always (padding up to 4/3), K = 128 levels with T <= 256 up to
     1.2 padding (longer rows only for launches of at most two samples), nothing below 128 channels; positions = B * ceil(F / (4 dil)) * dil * T / 4."""
