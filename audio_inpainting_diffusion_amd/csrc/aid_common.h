@@ -30,6 +30,9 @@ void aid_note_kernel(const char* name);   // aid_capi.hip: records which device 
 static inline int aid_ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 static inline int aid_pow2ceil(int v) { return 1 << aid_ilog2(v); }
 static inline int aid_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+// q-float vector accesses along T of the view are aligned: every stride a multiple of q floats (aid_view_strides), the base of 4 q bytes
+static inline bool aid_view_strides(const aid_view& v, int q) { return (v.sB % q) == 0 && (v.sC % q) == 0 && (v.sF % q) == 0; }
+static inline bool aid_view_aligned(const aid_view& v, int q) { return aid_view_strides(v, q) && (((uintptr_t)v.p) & (4 * q - 1)) == 0; }
 
 __device__ __forceinline__ float aid_gelu(float x) {
     return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));

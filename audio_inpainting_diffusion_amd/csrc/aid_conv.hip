@@ -21,6 +21,7 @@
 //   F.conv2d is limited only by summation order.
 #include "aid_common.h"
 #include "aid_mfma_dma.h"
+#include "aid_conv1x1_plan.h"
 #include <stdlib.h>
 
 struct ConvDev {
@@ -385,16 +386,14 @@ int aid_conv_splitk_reduce(const aid_conv2d_params* p, const float* ws, int spli
     return AID_OK;
 }
 
-// ------------------------------------------------------------------------------------------------------
-static int pick_mblk(int Cout) {
-    if (Cout <= 32) return 32;
-    if (Cout <= 64) return 64;
-    if (Cout <= 96 || (Cout % 96 == 0 && Cout % 128 != 0)) return 96;   // 96, 192, 288: no padded rows
-    return 128;
+// The split-K scratch rule: S partial planes fit the scratch that is offered, and the reduction's float4 accesses of y and res are aligned.
+bool aid_conv_splitk_scratch_ok(const aid_conv2d_params* p, int S) {
+    return p->ws && c11_splitk_fits(S, p->B, p->Cout, p->F, p->T, p->ws_bytes) && aid_view_aligned(p->y, 4) && (!p->res.p || aid_view_aligned(p->res, 4));
 }
 
+// ------------------------------------------------------------------------------------------------------
 extern "C" void aid_conv2d_pack_dims(int Cin, int Cout, int* Cin_pad, int* Cout_pad) {
-    const int mb = pick_mblk(Cout);
+    const int mb = c11_pick_mblk(Cout);
     *Cin_pad = ((Cin + 31) / 32) * 32;
     *Cout_pad = ((Cout + mb - 1) / mb) * mb;
 }
@@ -431,49 +430,45 @@ static int launch_cfg(const aid_conv2d_params* p, hipStream_t st, int splits = 1
     hipLaunchKernelGGL(kern, grid, dim3(64 * WGM * WGN), lds, st, a);
     AID_CHECK_LAUNCH();
     aid_note_kernel(a.splits > 1 ? "conv_mfma_kernel+splitk" : (KH == 5 ? "conv_mfma_kernel(5x3)" : "conv_mfma_kernel(1x1)"));
-    if (a.splits > 1) {
-        const int64_t total = (int64_t)p->B * p->Cout * ((int64_t)p->F * p->T / 4);
-        hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, *p, (const float*)p->ws, a.splits);
-        AID_CHECK_LAUNCH();
-    }
+    if (a.splits > 1) return aid_conv_splitk_reduce(p, (const float*)p->ws, a.splits, st);
     return AID_OK;
 }
 
-template <int KH, int KW, int KC>
-static int launch_m(const aid_conv2d_params* p, hipStream_t st) {
-    int mb = pick_mblk(p->Cout);
+// the register-staged kernel on a 5x3 layer
+static int launch_m53(const aid_conv2d_params* p, hipStream_t st) {
+    int mb = c11_pick_mblk(p->Cout);
     if (mb == 128) {
-        // grid-starved GEMMs (qk projections: N = B*T columns only)
+        // single pass: trade tile height for more workgroups
         const int64_t npos = (int64_t)p->B * p->F * p->T;
         const int64_t ntiles = (npos + 255) / 256;
-        const int64_t wg64 = ntiles * (p->Cout_pad / 64);
-        if (KH == 1 && p->ws && p->epi == 0 && wg64 < 384 && p->Cin >= 16 * KC && p->Cout_pad % 64 == 0 && (p->T % 4) == 0) {
-            // split K over several workgroups per 64 x 256 tile (deterministic two-pass reduction through ws)
-            int S = (int)((768 + wg64 - 1) / wg64);
-            if (S > 8) S = 8;
-            const int64_t need = (int64_t)S * p->B * p->Cout * p->F * p->T * 4;
-            auto al4 = [](const aid_view& v) { return (v.sB % 4) == 0 && (v.sC % 4) == 0 && (v.sF % 4) == 0 && (((uintptr_t)v.p) & 15) == 0; };
-            if (S > 1 && need <= p->ws_bytes && al4(p->y) && (!p->res.p || al4(p->res)))
-                return launch_cfg<KH, KW, 1, 2, 2, 4, KC>(p, st, S);
-        }
-        // single pass: trade tile height for more workgroups
         if (ntiles * (p->Cout_pad / 128) < 192) mb = (ntiles * (p->Cout_pad / 64) < 192) ? 32 : 64;
     }
-    if (KH == 1) {                      // more waves per CU for the short-K (memory-bound) channel projections
-        switch (mb) {
-            case 32: return launch_cfg<KH, KW, 1, 2, 1, 4, KC>(p, st);
-            case 64: return launch_cfg<KH, KW, 1, 2, 2, 4, KC>(p, st);     // 64x256, 8 waves, 2 workgroups / CU
-            case 96: return launch_cfg<KH, KW, 1, 2, 3, 4, KC>(p, st);     // 96x256, 12 waves
-            default: return launch_cfg<KH, KW, 1, 2, 4, 4, KC>(p, st);     // 128x256, 16 waves
-        }
-    }
     switch (mb) {
-        case 32: return launch_cfg<KH, KW, 1, 2, 1, 4, KC>(p, st);
+        case 32: return launch_cfg<5, 3, 1, 2, 1, 4, 4>(p, st);
         case 64:
-            if (p->T >= 64) return launch_cfg<KH, KW, 1, 2, 2, 8, KC>(p, st);     // 16 waves, 64x512
-            return launch_cfg<KH, KW, 2, 2, 1, 4, KC>(p, st);
-        case 96: return launch_cfg<KH, KW, 1, 2, 3, 4, KC>(p, st);     // 12 waves, 96x256
-        default: return launch_cfg<KH, KW, 1, 2, 4, 4, KC>(p, st);     // 16 waves (4 per SIMD), 128x256
+            if (p->T >= 64) return launch_cfg<5, 3, 1, 2, 2, 8, 4>(p, st);     // 16 waves, 64x512
+            return launch_cfg<5, 3, 2, 2, 1, 4, 4>(p, st);
+        case 96: return launch_cfg<5, 3, 1, 2, 3, 4, 4>(p, st);     // 12 waves, 96x256
+        default: return launch_cfg<5, 3, 1, 2, 4, 4, 4>(p, st);     // 16 waves (4 per SIMD), 128x256
+    }
+}
+
+// ... and on a 1x1 layer no other kernel took: the tile of c11_tiled_plan, K split through the scratch when the plan says so and y / res allow it
+template <int KC>
+static int launch_m11(const aid_conv2d_params* p, hipStream_t st) {
+    C11Shape s = c11_shape_of(*p);
+    C11Plan pl = c11_tiled_plan(s);
+    if (pl.S > 1 && !aid_conv_splitk_scratch_ok(p, pl.S)) {
+        s.ws = false;
+        pl = c11_tiled_plan(s);
+    }
+    AID_REQUIRE(pl.ok, "aid_conv2d: too many rows or tiles for the tiled 1x1 kernel");
+    if (pl.S > 1) return launch_cfg<1, 1, 1, 2, 2, 4, KC>(p, st, pl.S);
+    switch (pl.WGM) {
+        case 1: return launch_cfg<1, 1, 1, 2, 1, 4, KC>(p, st);
+        case 2: return launch_cfg<1, 1, 1, 2, 2, 4, KC>(p, st);     // 64x256, 8 waves, 2 workgroups / CU
+        case 3: return launch_cfg<1, 1, 1, 2, 3, 4, KC>(p, st);     // 96x256, 12 waves
+        default: return launch_cfg<1, 1, 1, 2, 4, 4, KC>(p, st);    // 128x256, 16 waves
     }
 }
 
@@ -485,12 +480,49 @@ int aid_conv1x1_dma_try(const aid_conv2d_params* p, hipStream_t st);     // aid_
 int aid_conv_small_try(const aid_conv2d_params* p, hipStream_t st);      // aid_conv_small.hip
 int aid_conv1x1_rs_try(const aid_conv2d_params* p, hipStream_t st);      // aid_conv1x1_rs.hip
 
+// The one 1x1 dispatch, in the order of c11_plan: the register-streamed kernel (K <= 256, HBM-bound, weights resident in LDS), the direct-to-LDS kernel
+// (2-3 workgroups per CU: K % 16 == 0, Cout tile 64/96/128; the qk GEMMs), the streaming kernel (remaining short-K / narrow projections), the tiled
+// kernel.  `only_first_two`: the refusal of an option (x2, dot_ws) that only the first two take.
+static int conv1x1_dispatch(const aid_conv2d_params* p, hipStream_t st, const char* only_first_two) {
+    int r = aid_conv1x1_rs_try(p, st);
+    if (r == 0) r = aid_conv1x1_dma_try(p, st);
+    if (r == 0 && only_first_two) {
+        aid_set_error(only_first_two);
+        return AID_E_BADARG;
+    }
+    if (r == 0) r = aid_conv1x1_stream_try(p, st);
+    if (r != 0) return r < 0 ? r : AID_OK;
+    return p->Cin <= 8 ? launch_m11<8>(p, st) : launch_m11<16>(p, st);
+}
+
+static C11Shape c11_query_shape(int B, int Cin, int Cout, int F, int T) {
+    C11Shape s = {};
+    int cip;
+    aid_conv2d_pack_dims(Cin, Cout, &cip, &s.Cout_pad);
+    s.B = B; s.Cin = Cin; s.Cout = Cout; s.F = F; s.T = T;
+    return s;
+}
+
+// partials per (sample, group) of the <y, aux> option (epi = 1 on a 1x1 layer): the slots of the kernel that serves the shape; 0 = not available
+extern "C" int aid_conv2d_dot_partials_1x1(int B, int Cin, int Cout, int F, int T) {
+    C11Shape s = c11_query_shape(B, Cin, Cout, F, T);
+    s.epi = 1; s.dot = true;
+    return c11_plan(s).slots;
+}
+
+// shapes on which the two-tensor K axis (x2 / Cin1) is available: what the direct-to-LDS tiles take (the register-streamed kernel's own shapes are not promised)
+extern "C" int aid_conv2d_x2_supported(int Cin, int Cin1, int Cout, int F, int T) {
+    C11Shape s = c11_query_shape(1, Cin, Cout, F, T);
+    s.x2 = true; s.Cin1 = Cin1;
+    return c11_dma_plan(s).family ? 1 : 0;
+}
+
 extern "C" int aid_conv2d(const aid_conv2d_params* p, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     AID_REQUIRE(p && p->x.p && p->y.p && p->wp, "aid_conv2d: null pointer");
     AID_REQUIRE(p->B > 0 && p->Cin > 0 && p->Cout > 0 && p->F > 0 && p->T > 0, "aid_conv2d: empty shape");
     AID_REQUIRE((p->T % 4) == 0, "aid_conv2d: T must be a multiple of 4");
-    AID_REQUIRE(p->x_wino == 3 || p->x_wino == 4 || ((p->x.sB % 4) == 0 && (p->x.sC % 4) == 0 && (p->x.sF % 4) == 0), "aid_conv2d: input view strides % 4 == 0");
+    AID_REQUIRE(p->x_wino == 3 || p->x_wino == 4 || aid_view_strides(p->x, 4), "aid_conv2d: input view strides % 4 == 0");
     AID_REQUIRE((((uintptr_t)p->x.p) & 15) == 0, "aid_conv2d: input view must be 16-byte aligned");
     int cip, cop;
     aid_conv2d_pack_dims(p->Cin, p->Cout, &cip, &cop);
@@ -503,10 +535,7 @@ extern "C" int aid_conv2d(const aid_conv2d_params* p, void* stream) {
     if (p->x2.p) {
         AID_REQUIRE(p->KH == 1 && p->KW == 1 && !p->in_scale && p->act == 0 && p->Cin1 > 0 && p->Cin1 < p->Cin && (p->Cin1 % 16) == 0 && ((p->Cin - p->Cin1) % 16) == 0,
                     "aid_conv2d: x2 is an option of plain 1x1 convolutions with both K segments multiples of 16");
-        int r = aid_conv1x1_rs_try(p, st);
-        if (r == 0) r = aid_conv1x1_dma_try(p, st);
-        if (r == 0) aid_set_error("aid_conv2d: x2 given but the layer is not eligible for the 1x1 kernels that take it");
-        return r == 1 ? AID_OK : (r < 0 ? r : AID_E_BADARG);
+        return conv1x1_dispatch(p, st, "aid_conv2d: x2 given but the layer is not eligible for the 1x1 kernels that take it");
     }
     if (p->stat_ws) {
         AID_REQUIRE(!p->dot_ws && p->epi == 0 && p->x_wino, "aid_conv2d: stat_ws is an option of the forward epilogue on Winograd-domain input");
@@ -514,10 +543,7 @@ extern "C" int aid_conv2d(const aid_conv2d_params* p, void* stream) {
     }
     if (p->dot_ws && p->KH == 1 && p->KW == 1) {                     // <y, aux> partials from the direct-to-LDS 1x1 kernel's dGELU epilogue
         AID_REQUIRE(p->epi == 1 && !p->res.p, "aid_conv2d: dot_ws on a 1x1 layer is an option of the dGELU epilogue without residual");
-        int r = aid_conv1x1_rs_try(p, st);
-        if (r == 0) r = aid_conv1x1_dma_try(p, st);
-        if (r == 0) aid_set_error("aid_conv2d: dot_ws given but the 1x1 layer is not eligible (aid_conv2d_dot_partials_1x1)");
-        return r == 1 ? AID_OK : (r < 0 ? r : AID_E_BADARG);
+        return conv1x1_dispatch(p, st, "aid_conv2d: dot_ws given but the 1x1 layer is not eligible (aid_conv2d_dot_partials_1x1)");
     }
     if (p->dot_ws) {
         AID_REQUIRE(p->KH == 5 && p->KW == 3 && p->wp_wino && p->wino_taps == (p->x_wino == 2 ? 50 : 30) && p->epi == 1 && !p->res.p,
@@ -544,20 +570,9 @@ extern "C" int aid_conv2d(const aid_conv2d_params* p, void* stream) {
             const int r = aid_conv53_dma_try(p, st);     // direct form, direct-to-LDS staging (layers without a Winograd pack)
             if (r != 0) return r < 0 ? r : AID_OK;
         }
-        return launch_m<5, 3, 4>(p, st);                 // register-staged kernel: in-kernel prologue, Cin = 2, odd shapes
+        return launch_m53(p, st);                 // register-staged kernel: in-kernel prologue, Cin = 2, odd shapes
     }
-    if (p->KH == 1 && p->KW == 1) {
-        {
-            int r = aid_conv1x1_rs_try(p, st);               // K <= 256, HBM-bound: register-streamed kernel (weights resident in LDS)
-            if (r != 0) return r < 0 ? r : AID_OK;
-            r = aid_conv1x1_dma_try(p, st);                  // direct-to-LDS kernel, 2-3 workgroups per CU (K % 16 == 0, Cout tile 64/96/128)
-            if (r != 0) return r < 0 ? r : AID_OK;
-            r = aid_conv1x1_stream_try(p, st);               // remaining short-K / narrow projections: streaming kernel
-            if (r != 0) return r < 0 ? r : AID_OK;
-        }
-        if (p->Cin <= 8) return launch_m<1, 1, 8>(p, st);
-        return launch_m<1, 1, 16>(p, st);
-    }
+    if (p->KH == 1 && p->KW == 1) return conv1x1_dispatch(p, st, nullptr);
     aid_set_error("aid_conv2d: unsupported kernel size (5x3 and 1x1 only)");
     return AID_E_BADARG;
 }

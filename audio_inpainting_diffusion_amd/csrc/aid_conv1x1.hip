@@ -16,7 +16,7 @@
 // Epilogue identical to conv_mfma_kernel: y = alpha*(res_scale*res + acc*out_scale[b,co]) or the dGELU form.
 #include "aid_common.h"
 #include "aid_mfma_dma.h"
-#include <stdlib.h>
+#include "aid_conv1x1_plan.h"
 
 struct C1Dev {
     aid_conv2d_params p;
@@ -143,49 +143,27 @@ __global__ __launch_bounds__(256, MINW) void conv1x1_stream_kernel(const C1Dev a
 }
 
 template <int MT, int NT, int PF, int MINW>
-static int launch_c1(const aid_conv2d_params* p, hipStream_t st) {
+static int launch_c1(const aid_conv2d_params* p, hipStream_t st, const C11Plan& pl) {
     C1Dev a;
     a.p = *p;
-    a.npos = (int64_t)p->B * p->F * p->T;
-    a.mchunks = p->Cout_pad / (32 * MT);
-    const int64_t pblocks = (a.npos + 4 * 32 * NT - 1) / (4 * 32 * NT);
-    hipLaunchKernelGGL((conv1x1_stream_kernel<MT, NT, PF, MINW>), dim3((unsigned)(pblocks * a.mchunks)), dim3(256), 0, st, a);
+    a.npos = pl.npos;
+    a.mchunks = pl.mchunks;
+    hipLaunchKernelGGL((conv1x1_stream_kernel<MT, NT, PF, MINW>), dim3((unsigned)(pl.pblocks * a.mchunks)), dim3(256), 0, st, a);
     AID_CHECK_LAUNCH();
     aid_note_kernel("conv1x1_stream_kernel");
     return AID_OK;
 }
 
-static bool view_ok(const aid_view& v, int al) {
-    return (v.sB % al) == 0 && (v.sC % al) == 0 && (v.sF % al) == 0 && (((uintptr_t)v.p) & (4 * al - 1)) == 0;
-}
-
 // returns 1 if the streaming kernel took the launch, 0 if not eligible, <0 on error
 int aid_conv1x1_stream_try(const aid_conv2d_params* p, hipStream_t st) {
-    if (!(p->KH == 1 && p->KW == 1) || p->act != 0) return 0;
-    if (p->Cin < 16 || (p->Cin & 1) || p->Cout < 32) return 0;
-    const int64_t ft = (int64_t)p->F * p->T;
-    if (p->F == 1 || (int64_t)p->B * ft < 2048) return 0;            // few positions (qk GEMMs, F = 1): the tiled kernel's job
-    // measured (profiles/r01_conv1x1_probe.txt): ahead of the register-staged tiled kernel for the short-K / write-dominated
-    // projections (Cin <= 96: 8-35 %), behind it (10-18 %) once K >= 256 makes the layer MFMA-bound; the direct-to-LDS kernel
-    // (aid_conv1x1_dma.hip, tried first) is 17-20 % ahead of this one wherever it is eligible, so this kernel serves the shapes
-    // that one refuses (K % 16 != 0, Cout tiles of 32).  128 positions per wave (float4 traffic) when the geometry allows, else 64.
-    if (!(p->Cin <= 96 || p->Cout_pad <= 32)) return 0;
-    int nt = 4;
-    if ((ft % 128) || (p->T % 4)) nt = 2;
-    if ((ft % (32 * nt)) || (p->T % nt)) return 0;                  // a wave's positions stay inside one sample b, vectors inside one row
-    if (!view_ok(p->x, nt) || !view_ok(p->y, nt)) return 0;
-    if (p->res.p && !view_ok(p->res, nt)) return 0;
-    if (p->aux.p && !view_ok(p->aux, nt)) return 0;
-    const int mt32 = p->Cout_pad / 32;
+    if (!(p->KH == 1 && p->KW == 1)) return 0;
+    const C11Plan pl = c11_stream_plan(c11_shape_of(*p));
+    if (!pl.family) return 0;
+    if (!aid_view_aligned(p->x, pl.nt) || !aid_view_aligned(p->y, pl.nt) || (p->res.p && !aid_view_aligned(p->res, pl.nt)) || (p->aux.p && !aid_view_aligned(p->aux, pl.nt))) return 0;
     int rc;
-    if (nt == 4) {
-        if (mt32 % 2 == 0) rc = launch_c1<2, 4, 4, 2>(p, st);
-        else               rc = launch_c1<1, 4, 4, 2>(p, st);
-    } else {
-        if (mt32 % 4 == 0)      rc = launch_c1<4, 2, 4, 2>(p, st);   // 128-wide slices, 2 waves / SIMD
-        else if (mt32 % 3 == 0) rc = launch_c1<3, 2, 4, 2>(p, st);   // 96-wide (Cout 96, 192), 3 waves / SIMD
-        else if (mt32 % 2 == 0) rc = launch_c1<2, 2, 4, 2>(p, st);
-        else                    rc = launch_c1<1, 2, 4, 2>(p, st);
-    }
+    if (pl.nt == 4)      rc = pl.MT == 2 ? launch_c1<2, 4, 4, 2>(p, st, pl) : launch_c1<1, 4, 4, 2>(p, st, pl);
+    else if (pl.MT == 4) rc = launch_c1<4, 2, 4, 2>(p, st, pl);   // 128-wide slices, 2 waves / SIMD
+    else if (pl.MT == 3) rc = launch_c1<3, 2, 4, 2>(p, st, pl);   // 96-wide (Cout 96, 192), 3 waves / SIMD
+    else                 rc = pl.MT == 2 ? launch_c1<2, 2, 4, 2>(p, st, pl) : launch_c1<1, 2, 4, 2>(p, st, pl);
     return rc == AID_OK ? 1 : rc;
 }

@@ -13,10 +13,11 @@
 // Per-(b,ci) prologue scale (in_scale) is applied to the A fragment (a tile never straddles two samples: host-checked).
 #include "aid_common.h"
 #include "aid_mfma_dma.h"
+#include "aid_conv1x1_plan.h"
 #include <type_traits>
-#include <stdlib.h>
 
 int aid_conv_splitk_reduce(const aid_conv2d_params* p, const float* ws, int splits, hipStream_t st);      // aid_conv.hip
+bool aid_conv_splitk_scratch_ok(const aid_conv2d_params* p, int S);
 
 struct C11Dev {
     aid_conv2d_params p;
@@ -295,9 +296,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv11_dma_kernel(const 
 }
 
 template <int MT, int WGM, int WGN, int RMAX, int KC, int MINW>
-static int launch_c11(const aid_conv2d_params* p, hipStream_t st, int splits = 1, int kps = 0) {      // splits > 1: the partition of gemm_k_partition
-    constexpr int M_BLK = 32 * MT * WGM;
-    constexpr int N_BLK = 64 * WGN;
+static int launch_c11(const aid_conv2d_params* p, hipStream_t st, const C11Plan& pl) {
     static const float* zero = nullptr;
     if (!zero) {
         void* z = nullptr;
@@ -307,20 +306,16 @@ static int launch_c11(const aid_conv2d_params* p, hipStream_t st, int splits = 1
     C11Dev a;
     a.p = *p;
     a.zero = zero;
-    int TT = aid_pow2ceil(p->T);
-    if (TT > N_BLK) TT = N_BLK;
-    a.tt_log2 = aid_ilog2(TT);
-    const int ROWS = N_BLK / TT;
-    if (ROWS > RMAX) return 1000;
-    a.rows_log2 = aid_ilog2(ROWS);
-    a.tiles_t = aid_cdiv(p->T, TT);
-    a.nrows = p->B * p->F;
-    a.nchunks = aid_cdiv(p->Cin, KC);
-    a.nch1 = p->x2.p ? p->Cin1 / KC : a.nchunks;
-    a.nx = aid_cdiv(a.nrows, ROWS) * a.tiles_t;
-    a.ny = p->Cout_pad / M_BLK;
-    a.per_xcd = (a.nx * a.ny + 7) / 8;
-    a.cps = splits > 1 ? kps / KC : a.nchunks;
+    a.tt_log2 = aid_ilog2(pl.TT);
+    a.rows_log2 = aid_ilog2(pl.ROWS);
+    a.tiles_t = pl.tiles_t;
+    a.nrows = pl.nrows;
+    a.nchunks = pl.nchunks;
+    a.nch1 = pl.nch1;
+    a.nx = pl.nx;
+    a.ny = pl.ny;
+    a.per_xcd = (int)(((int64_t)a.nx * a.ny + 7) / 8);
+    a.cps = pl.kps / KC;
     a.splits = aid_cdiv(a.nchunks, a.cps);
     a.ws = (float*)p->ws;
     hipLaunchKernelGGL((conv11_dma_kernel<MT, WGM, WGN, RMAX, KC, MINW>), dim3((unsigned)(8 * a.per_xcd), (unsigned)a.splits), dim3(64 * WGM * WGN), 0, st, a);
@@ -389,105 +384,34 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(const aid_conv2d_param
     }
 }
 
-// partials per (sample, group) of the <y, aux> option on this kernel (epi = 1 on a 1x1 layer): position tiles per sample; 0 = not available
-int aid_conv1x1_rs_dot_partials(int Cin, int Cout, int cop, int F, int T);   // aid_conv1x1_rs.hip
-int aid_conv1x1_rs_shape_ok(int Cin, int Cout, int cop, int F, int T);
-int aid_conv1x1_rs_enabled(void);
-
-extern "C" int aid_conv2d_dot_partials_1x1(int B, int Cin, int Cout, int F, int T) {
-    int cip, cop;
-    aid_conv2d_pack_dims(Cin, Cout, &cip, &cop);
-    if (aid_conv1x1_rs_enabled()) {                                   // the register-streamed kernel takes the shapes it serves
-        const int n = aid_conv1x1_rs_dot_partials(Cin, Cout, cop, F, T);
-        if (n) return n;
-        if (aid_conv1x1_rs_shape_ok(Cin, Cout, cop, F, T)) return 0;
-    }
-    if (F <= 1 || Cin < 32 || (Cin % 16) || Cout < 32 || (Cout % 8) || (T % 4) || aid_pow2ceil(T) < 8) return 0;
-    const int mblk = (cop % 128 == 0) ? 128 : ((cop % 64 == 0) ? 64 : ((cop % 96 == 0) ? 96 : 0));
-    const int cpg = Cout / 8;
-    if (!mblk || (cpg % 4) || (mblk % cpg)) return 0;
-    int TT = aid_pow2ceil(T); if (TT > 256) TT = 256;
-    const int ROWS = 256 / TT;
-    if (ROWS > 16 || (F % ROWS)) return 0;
-    return (F / ROWS) * aid_cdiv(T, TT);
-}
-
-// K partition of the qk GEMMs: a function of K ALONE -- the skinny kernel (N <= 128) and the tiled kernel (any N) then add the same k-pairs in
-// the same order into the same number of partial planes, so a segment's result does not depend on the batch it is evaluated in.
-static void gemm_k_partition(int Cin, int* S, int* kps) {
-    int s = 8;
-    if (s > Cin / 64) s = Cin / 64;
-    if (s < 1) s = 1;
-    int cps = aid_cdiv(aid_cdiv(Cin, 16), s);          // 16-channel chunks per range, even (two LDS buffers alternate from the first chunk)
-    cps += cps & 1;
-    *kps = cps * 16;
-    *S = aid_cdiv(Cin, *kps);
-}
-
-// shapes on which the two-tensor K axis (x2 / Cin1) is available: what aid_conv1x1_dma_try accepts below, minus the pointer alignment checks
-extern "C" int aid_conv2d_x2_supported(int Cin, int Cin1, int Cout, int F, int T) {
-    int cip, cop;
-    aid_conv2d_pack_dims(Cin, Cout, &cip, &cop);
-    if (F <= 1 || Cin < 32 || (Cin % 16) || Cout < 32 || Cin1 <= 0 || Cin1 >= Cin || (Cin1 % 16)) return 0;
-    if ((T % 4) || aid_pow2ceil(T) < 8) return 0;
-    int TT = aid_pow2ceil(T); if (TT > 256) TT = 256;
-    if (256 / TT > 16) return 0;
-    return (cop % 128 == 0 || cop % 64 == 0 || cop % 96 == 0) ? 1 : 0;
-}
-
 // returns 1 if this kernel took the launch, 0 if not eligible, <0 on error
 int aid_conv1x1_dma_try(const aid_conv2d_params* p, hipStream_t st) {
-    if (!(p->KH == 1 && p->KW == 1) || p->act != 0) return 0;
-    if (p->Cin < 32 || (p->Cin % 16) || p->Cout < 32) return 0;      // (K is walked in whole 16-channel chunks: no ragged tail)
-    const bool gemm = p->F == 1;                                     // the qk projections: a plain GEMM with N = B*T columns
-    if (gemm && (p->epi != 0 || p->in_scale || p->x2.p || (p->Cout_pad % 128) || p->Cin < 256)) return 0;
-    if ((p->T % 4) || aid_pow2ceil(p->T) < 8) return 0;
-    auto al = [](const aid_view& v, int q) { return (v.sB % q) == 0 && (v.sC % q) == 0 && (v.sF % q) == 0 && (((uintptr_t)v.p) & (4 * q - 1)) == 0; };
-    if (!al(p->x, 4) || !al(p->y, 2) || (p->res.p && !al(p->res, 2)) || (p->aux.p && !al(p->aux, 2))) return 0;
+    if (!(p->KH == 1 && p->KW == 1)) return 0;
+    C11Shape s = c11_shape_of(*p);
+    C11Plan pl = c11_dma_plan(s);
+    if (!pl.family) return 0;
+    if (!aid_view_aligned(p->x, 4) || !aid_view_aligned(p->y, 2) || (p->res.p && !aid_view_aligned(p->res, 2)) || (p->aux.p && !aid_view_aligned(p->aux, 2))) return 0;
     if ((int64_t)4 * 16 * p->x.sC >= (1LL << 31)) return 0;
-    if (p->x2.p && (!al(p->x2, 4) || (int64_t)4 * 16 * p->x2.sC >= (1LL << 31) || (p->Cin1 % 16) || p->in_scale)) return 0;
-    // a tile (256 positions) must stay inside one sample when a per-(b,ci) scale is applied to the weights
-    int TT = aid_pow2ceil(p->T); if (TT > 256) TT = 256;
-    const int ROWS = 256 / TT;
-    if (ROWS > 16) return 0;
-    if (p->in_scale && (p->F % ROWS)) return 0;
-    if (p->dot_ws && (p->epi != 1 || p->dot_n != aid_conv2d_dot_partials_1x1(p->B, p->Cin, p->Cout, p->F, p->T) || p->dot_n <= 0 || p->x2.p)) return 0;
+    if (p->x2.p && (!aid_view_aligned(p->x2, 4) || (int64_t)4 * 16 * p->x2.sC >= (1LL << 31))) return 0;
+    if (p->dot_ws && p->dot_n != pl.slots) return 0;
+    if (pl.S > 1 && !aid_conv_splitk_scratch_ok(p, pl.S)) {      // y or res not aligned for the reduction: the plan without scratch (a single pass)
+        s.ws = false;
+        pl = c11_dma_plan(s);
+    }
     int rc;
-    if (gemm && p->B * p->T <= 128 && (p->T % 4) == 0 && (p->Cin % 2) == 0 && p->ws) {
-        // skinny GEMM: a wave per 32 rows and K range; enough K ranges for ~2000 waves, as the scratch allows (16 at most)
-        const int nt = aid_cdiv(p->B * p->T, 32);
-        const int rowtiles = p->Cout_pad / 32;
-        int S, kps;
-        gemm_k_partition(p->Cin, &S, &kps);
-        auto al4 = [](const aid_view& v) { return (v.sB % 4) == 0 && (v.sC % 4) == 0 && (v.sF % 4) == 0 && (((uintptr_t)v.p) & 15) == 0; };
-        if ((int64_t)S * p->B * p->Cout * p->T * 4 <= p->ws_bytes && al4(p->y) && (!p->res.p || al4(p->res))) {
-            const dim3 grid((unsigned)aid_cdiv(rowtiles, 4), (unsigned)S);
-            switch (nt) {
-                case 1: hipLaunchKernelGGL(gemm_skinny_kernel<1>, grid, dim3(256), 0, st, *p, (float*)p->ws, kps); break;
-                case 2: hipLaunchKernelGGL(gemm_skinny_kernel<2>, grid, dim3(256), 0, st, *p, (float*)p->ws, kps); break;
-                case 3: hipLaunchKernelGGL(gemm_skinny_kernel<3>, grid, dim3(256), 0, st, *p, (float*)p->ws, kps); break;
-                default: hipLaunchKernelGGL(gemm_skinny_kernel<4>, grid, dim3(256), 0, st, *p, (float*)p->ws, kps); break;
-            }
-            AID_CHECK_LAUNCH();
-            aid_note_kernel("gemm_skinny_kernel+splitk");
-            rc = aid_conv_splitk_reduce(p, (const float*)p->ws, S, st);
-            return rc == AID_OK ? 1 : rc;
+    if (pl.family == C11_SKINNY) {
+        const dim3 grid((unsigned)pl.gx, (unsigned)pl.S);
+        switch (pl.nt) {
+            case 1: hipLaunchKernelGGL(gemm_skinny_kernel<1>, grid, dim3(256), 0, st, *p, (float*)p->ws, pl.kps); break;
+            case 2: hipLaunchKernelGGL(gemm_skinny_kernel<2>, grid, dim3(256), 0, st, *p, (float*)p->ws, pl.kps); break;
+            case 3: hipLaunchKernelGGL(gemm_skinny_kernel<3>, grid, dim3(256), 0, st, *p, (float*)p->ws, pl.kps); break;
+            default: hipLaunchKernelGGL(gemm_skinny_kernel<4>, grid, dim3(256), 0, st, *p, (float*)p->ws, pl.kps); break;
         }
-    }
-    if (gemm) {
-        // grid-starved: split K over several workgroups per tile when the scratch is there (deterministic fixed-order reduction)
-        int S, kps;
-        gemm_k_partition(p->Cin, &S, &kps);
-        auto al4 = [](const aid_view& v) { return (v.sB % 4) == 0 && (v.sC % 4) == 0 && (v.sF % 4) == 0 && (((uintptr_t)v.p) & 15) == 0; };
-        if (S > 1 && !(p->ws && (int64_t)S * p->B * p->Cout * p->F * p->T * 4 <= p->ws_bytes && al4(p->y) && (!p->res.p || al4(p->res)))) S = 1;
-        rc = launch_c11<2, 2, 4, 16, 16, 4>(p, st, S, kps);
-        if (rc == 1000) return 0;
-        return rc == AID_OK ? 1 : rc;
-    }
-    if (p->Cout_pad % 128 == 0)      rc = launch_c11<2, 2, 4, 16, 16, 4>(p, st);      // 128 x 256, 8 waves, 2 workgroups / CU
-    else if (p->Cout_pad % 64 == 0)  rc = launch_c11<1, 2, 4, 16, 16, 4>(p, st);      //  64 x 256
-    else if (p->Cout_pad % 96 == 0)  rc = launch_c11<3, 1, 4, 16, 16, 2>(p, st);      //  96 x 256, 4 waves
-    else return 0;
-    if (rc == 1000) return 0;
+        AID_CHECK_LAUNCH();
+        aid_note_kernel("gemm_skinny_kernel+splitk");
+        rc = aid_conv_splitk_reduce(p, (const float*)p->ws, pl.S, st);
+    } else if (pl.MT == 2) rc = launch_c11<2, 2, 4, 16, 16, 4>(p, st, pl);      // 128 x 256, 8 waves, 2 workgroups / CU
+    else if (pl.MT == 1) rc = launch_c11<1, 2, 4, 16, 16, 4>(p, st, pl);        //  64 x 256
+    else                 rc = launch_c11<3, 1, 4, 16, 16, 2>(p, st, pl);        //  96 x 256, 4 waves
     return rc == AID_OK ? 1 : rc;
 }

@@ -17,8 +17,7 @@
 // The k-pairs are accumulated in increasing order into one accumulator per output, as in the other 1x1 kernels.
 #include "aid_common.h"
 #include "aid_mfma_dma.h"
-#include <stdint.h>
-#include <stdlib.h>
+#include "aid_conv1x1_plan.h"
 
 struct C11RDev {
     aid_conv2d_params p;
@@ -27,19 +26,6 @@ struct C11RDev {
     int tps;                   // 64-position tiles per sample (F*T / 64)
     int ntiles;                // B * tps
 };
-
-// returns the number of <y, aux> partial slots per (sample, group) = tiles per sample, or 0 when the shape is not served
-// Which layers (a function of the per-sample shape only, so that a segment's result does not depend on its batch): measured per shape at batch 8 AND
-// batch 1 against the tile kernels (profiles/r03_trace_b8.txt / _b1.txt before and after): 96 output channels (MT = 3) win for every K <= 256
-// (batch 8: -12 ... -32 %); 64 output channels (MT = 2) win at K = 64 and lose at K = 128 / 192 (more waves would be needed to cover the longer K
-// loop's exposed first block); 128-channel slices (MT = 4: 128 accumulators + the epilogue's gather registers, 64-128 KB of weights per workgroup)
-// lose on the small pyramid levels by 2x (32 ... 128 tiles per sample: one wave per tile, most SIMDs idle) and are not instantiated.
-static int c11rs_shape(int Cin, int Cout, int cop, int F, int T) {
-    if (F <= 1 || Cin < 32 || (Cin % 32) || Cin > 256 || Cout < 32) return 0;
-    if (!(cop == 96 || (cop == 64 && Cin <= 64)) || Cout != cop) return 0;
-    if ((T % 2) || (((int64_t)F * T) % 64)) return 0;
-    return (int)(((int64_t)F * T) / 64);
-}
 
 // EPI: the dGELU(aux) epilogue (epi = 1); RES: a residual is added.  Cout == Cout_pad (host-checked): no row predicates in the epilogue.
 template <int MT, int KMAX, bool ACT, bool SCALE, bool EPI, bool RES>
@@ -202,21 +188,16 @@ __global__ __launch_bounds__(512, 1) void conv11_rs_kernel(const C11RDev a) {
 }
 
 template <int MT, int KMAX>
-static int launch_c11rs(const aid_conv2d_params* p, hipStream_t st) {
+static int launch_c11rs(const aid_conv2d_params* p, hipStream_t st, const C11Plan& pl) {
     C11RDev a;
     a.p = *p;
     a.nsteps = p->Cin / 2;
-    a.nsteps1 = p->x2.p ? p->Cin1 / 2 : a.nsteps;
-    a.tps = (int)(((int64_t)p->F * p->T) / 64);
-    a.ntiles = p->B * a.tps;
-    int gx = aid_cdiv(a.ntiles, 8);
-    const int ny = p->Cout_pad / (32 * MT);
-    const int cap = ny > 1 ? 256 / ny + (256 % ny ? 1 : 0) : 256;      // one workgroup per CU over all Cout slices
-    if (gx > cap) gx = cap;
-    const dim3 grid((unsigned)gx, (unsigned)ny);
+    a.nsteps1 = pl.nsteps1;
+    a.tps = pl.tps;
+    a.ntiles = pl.ntiles;
+    const dim3 grid((unsigned)pl.gx, (unsigned)pl.ny);
 #define AID_C11RS(ACTv, SCv, EPIv, RESv) hipLaunchKernelGGL((conv11_rs_kernel<MT, KMAX, ACTv, SCv, EPIv, RESv>), grid, dim3(512), 0, st, a)
-    const int key = (p->act ? 8 : 0) | (p->in_scale ? 4 : 0) | (p->epi == 1 ? 2 : 0) | (p->res.p ? 1 : 0);
-    switch (key) {                                       // (the combinations the network emits; anything else goes to the tile kernels)
+    switch (pl.key) {                                    // <ACT, SCALE, EPI, RES>
         case 12: AID_C11RS(true, true, false, false); break;
         case 13: AID_C11RS(true, true, false, true); break;
         case 0:  AID_C11RS(false, false, false, false); break;
@@ -226,7 +207,7 @@ static int launch_c11rs(const aid_conv2d_params* p, hipStream_t st) {
         case 4:  AID_C11RS(false, true, false, false); break;
         case 5:  AID_C11RS(false, true, false, true); break;
         case 6:  AID_C11RS(false, true, true, false); break;
-        default: return 1000;
+        default: aid_set_error("aid_conv2d: no conv11_rs_kernel instance for these options"); return AID_E_BADARG;      // (c11_rs_plan admits the nine above)
     }
 #undef AID_C11RS
     AID_CHECK_LAUNCH();
@@ -234,43 +215,19 @@ static int launch_c11rs(const aid_conv2d_params* p, hipStream_t st) {
     return AID_OK;
 }
 
-// <y, aux> partial slots per (sample, group) when this kernel serves the shape (0: it does not)
-int aid_conv1x1_rs_dot_partials(int Cin, int Cout, int cop, int F, int T) {
-    const int n = c11rs_shape(Cin, Cout, cop, F, T);
-    if (!n || (Cout % 8)) return 0;
-    const int cpg = Cout / 8;
-    const int mblk = (cop % 128 == 0) ? 128 : cop;
-    if ((cpg % 4) || (mblk % cpg)) return 0;
-    return n;
-}
-
-int aid_conv1x1_rs_shape_ok(int Cin, int Cout, int cop, int F, int T) { return c11rs_shape(Cin, Cout, cop, F, T) ? 1 : 0; }
-
-int aid_conv1x1_rs_enabled(void) {
-#ifdef AID_EXPERIMENT
-    static const int enabled = getenv("AID_C11_RS") ? atoi(getenv("AID_C11_RS")) : 1;
-#else
-    constexpr int enabled = 1;
-#endif
-    return enabled;
-}
-
 // returns 1 if this kernel took the launch, 0 if not eligible, <0 on error
 int aid_conv1x1_rs_try(const aid_conv2d_params* p, hipStream_t st) {
-    if (!aid_conv1x1_rs_enabled()) return 0;
-    if (!(p->KH == 1 && p->KW == 1) || p->ws || (p->act && !p->in_scale) || p->Cout != p->Cout_pad) return 0;
-    if (!c11rs_shape(p->Cin, p->Cout, p->Cout_pad, p->F, p->T)) return 0;
-    auto al = [](const aid_view& v, int q) { return (v.sB % q) == 0 && (v.sC % q) == 0 && (v.sF % q) == 0 && (((uintptr_t)v.p) & (4 * q - 1)) == 0; };
-    if (!al(p->x, 2) || !al(p->y, 2) || (p->res.p && !al(p->res, 2)) || (p->aux.p && !al(p->aux, 2))) return 0;
-    if (p->x2.p && (!al(p->x2, 2) || (p->Cin1 % 2) || p->Cin1 <= 0 || p->Cin1 >= p->Cin || p->in_scale || p->act)) return 0;
-    if ((((uintptr_t)p->wp) & 15) || (p->Cout_pad % 4)) return 0;
+    if (!(p->KH == 1 && p->KW == 1)) return 0;
+    const C11Plan pl = c11_rs_plan(c11_shape_of(*p));
+    if (pl.family != C11_RS) return 0;
+    if (!aid_view_aligned(p->x, 2) || !aid_view_aligned(p->y, 2) || (p->res.p && !aid_view_aligned(p->res, 2)) || (p->aux.p && !aid_view_aligned(p->aux, 2))) return 0;
+    if (p->x2.p && !aid_view_aligned(p->x2, 2)) return 0;
+    if (((uintptr_t)p->wp) & 15) return 0;
     auto fits = [&](const aid_view& v, int C) { return v.sC >= 0 && v.sF >= 0 && (int64_t)4 * ((int64_t)C * v.sC + (int64_t)p->F * v.sF + p->T) < (1LL << 32); };   // 32-bit byte offsets within a sample
     if (!fits(p->x, p->Cin) || !fits(p->y, p->Cout_pad) || (p->res.p && !fits(p->res, p->Cout_pad)) || (p->aux.p && !fits(p->aux, p->Cout_pad)) || (p->x2.p && !fits(p->x2, p->Cin))) return 0;
-    if (p->dot_ws && (p->epi != 1 || p->dot_n <= 0 || p->dot_n != aid_conv1x1_rs_dot_partials(p->Cin, p->Cout, p->Cout_pad, p->F, p->T))) return 0;
+    if (p->dot_ws && p->dot_n != pl.slots) return 0;
     int rc;
-    const bool k128 = p->Cin <= 128;
-    if (p->Cout_pad == 96) rc = k128 ? launch_c11rs<3, 128>(p, st) : launch_c11rs<3, 256>(p, st);
-    else                   rc = launch_c11rs<2, 128>(p, st);
-    if (rc == 1000) return 0;
+    if (pl.MT == 3) rc = pl.KMAX == 128 ? launch_c11rs<3, 128>(p, st, pl) : launch_c11rs<3, 256>(p, st, pl);
+    else            rc = launch_c11rs<2, 128>(p, st, pl);
     return rc == AID_OK ? 1 : rc;
 }

@@ -304,7 +304,7 @@ int aid_conv53_dma_try(const aid_conv2d_params* p, hipStream_t st) {
     if ((p->Cin % 4) != 0 || p->Cout < 64 || (p->T % 4) != 0) return 0;
     const int TT = aid_pow2ceil(p->T);
     if (TT < 8) return 0;                                  // ROWS <= 32 (halo area)
-    if ((p->x.sB % 4) || (p->x.sC % 4) || (p->x.sF % 4) || (((uintptr_t)p->x.p) & 15)) return 0;
+    if (!aid_view_aligned(p->x, 4)) return 0;
     if ((int64_t)4 * p->x.sC >= (1LL << 31)) return 0;
     int rc;
     // (round-1 experiments with 4/16-wave tiles, KC = 2 and 3-4 workgroups per CU are recorded in DESIGN.md section 3.1)

@@ -277,13 +277,12 @@ static int launch_cs(K kern, const aid_conv2d_params* p, hipStream_t st, bool sp
 int aid_conv_small_try(const aid_conv2d_params* p, hipStream_t st) {
     if (p->act != 0 || p->epi != 0 || (p->T % 4)) return 0;
     {   // C -> 2, 5x3, dilation 1 (any C >= 8): sliding-row kernel
-        auto al4 = [](const aid_view& v) { return (v.sB % 4) == 0 && (v.sC % 4) == 0 && (v.sF % 4) == 0 && (((uintptr_t)v.p) & 15) == 0; };
         int lpr = aid_pow2ceil(p->T / 4); if (lpr > 64) lpr = 64;
         const int64_t wgs1 = (int64_t)aid_cdiv(p->F / 4, 64 / lpr) * aid_cdiv(p->T / 4, lpr);      // workgroups PER SAMPLE: the choice must not depend on the
         // batch (item b of a batch has to come out bit-identical however the batch is cut).  Deep levels: a dozen workgroups per sample walking 64
         // channels per wave lose to the MFMA kernel (244 vs 150 us at B = 1, C = 256; level at B = 8)
         if (p->KH == 5 && p->KW == 3 && p->dilF == 1 && p->Cout <= 2 && p->Cin >= 8 && !p->in_scale && (p->F % 4) == 0 && !(p->Cin > 128 && wgs1 < 16) &&
-            al4(p->x) && al4(p->y) && (!p->res.p || al4(p->res))) {
+            aid_view_aligned(p->x, 4) && aid_view_aligned(p->y, 4) && (!p->res.p || aid_view_aligned(p->res, 4))) {
             const int rc = launch_cout2_rows(p, st);
             return rc == AID_OK ? 1 : rc;
         }
@@ -293,8 +292,7 @@ int aid_conv_small_try(const aid_conv2d_params* p, hipStream_t st) {
     if (p->Cin > 96 || (p->Cout > 96 && p->Cin > 8)) return 0;      // (few input channels: any Cout -- the walk over Cout is sliced over blockIdx.y)
     const bool k11 = p->KH == 1 && p->KW == 1, k53 = p->KH == 5 && p->KW == 3;
     if (!k11 && !k53) return 0;
-    auto al4 = [](const aid_view& v) { return (v.sB % 4) == 0 && (v.sC % 4) == 0 && (v.sF % 4) == 0 && (((uintptr_t)v.p) & 15) == 0; };
-    if (!al4(p->x) || !al4(p->y) || (p->res.p && !al4(p->res))) return 0;
+    if (!aid_view_aligned(p->x, 4) || !aid_view_aligned(p->y, 4) || (p->res.p && !aid_view_aligned(p->res, 4))) return 0;
     int rc;
     if (p->Cout <= 8 && p->Cin >= 8) {
         if (k11)            rc = p->Cout <= 2 ? launch_cs(conv_small_cout_kernel<1, 1, 2>, p, st) : launch_cs(conv_small_cout_kernel<1, 1, 8>, p, st);

@@ -1552,7 +1552,6 @@ extern "C" int aid_conv2d_dot_partials(int B, int Cin, int Cout, int F, int T, i
 
 // x_wino = 1: the caller already wrote the Winograd-domain input; there is no other kernel that can read it
 static int conv53_wino_v(const aid_conv2d_params* p, hipStream_t st) {
-    auto al4 = [](const aid_view& v) { return (v.sB % 4) == 0 && (v.sC % 4) == 0 && (v.sF % 4) == 0 && (((uintptr_t)v.p) & 15) == 0; };
     AID_REQUIRE((int64_t)p->Cin * p->x.sC * 4 < (1LL << 32) && (int64_t)p->wino_taps * p->Cin_pad * p->Cout_pad * 4 < (1LL << 32),
                 "aid_conv2d: x_wino kernels address one sample and the weight pack with 32-bit byte offsets");
     if (p->x_wino == 2) {                                   // F(8,3): [B, Cin, F, 10, T/8] input, 50-tap pack
@@ -1560,14 +1559,14 @@ static int conv53_wino_v(const aid_conv2d_params* p, hipStream_t st) {
                     "aid_conv2d: x_wino = 2 needs the 50-tap F(8,3) pack of a 5x3 layer and no in-kernel prologue");
         AID_REQUIRE(wino_v_shape_ok(p->Cin, p->Cout, p->T) && (p->T % 32) == 0, "aid_conv2d: shape not supported with x_wino = 2 (see aid_conv2d_wino_form)");
         AID_REQUIRE(p->x.sF >= 10 * (p->T / 8) && (int64_t)4 * p->x.sC < (1LL << 31), "aid_conv2d: x_wino = 2 rows are [10][T/8]");
-        AID_REQUIRE(al4(p->x) && al4(p->y) && (!p->res.p || al4(p->res)) && (!p->aux.p || al4(p->aux)), "aid_conv2d: x_wino views must be 16-byte aligned");
+        AID_REQUIRE(aid_view_aligned(p->x, 4) && aid_view_aligned(p->y, 4) && (!p->res.p || aid_view_aligned(p->res, 4)) && (!p->aux.p || aid_view_aligned(p->aux, 4)), "aid_conv2d: x_wino views must be 16-byte aligned");
         return launch_wino_r(8, p, st);
     }
     AID_REQUIRE(p->wp_wino && p->wino_taps == 30 && p->KH == 5 && p->KW == 3 && !p->in_scale && p->act == 0,
                 "aid_conv2d: x_wino needs the 30-tap Winograd pack of a 5x3 layer and no in-kernel prologue");
     AID_REQUIRE(wino_v_shape_ok(p->Cin, p->Cout, p->T), "aid_conv2d: shape not supported with x_wino (see aid_conv2d_wino_input_supported)");
     AID_REQUIRE(p->x.sF >= 6 * (p->T / 4) && (int64_t)4 * p->x.sC < (1LL << 31), "aid_conv2d: x_wino rows are [6][T/4]");
-    AID_REQUIRE(al4(p->x) && al4(p->y) && (!p->res.p || al4(p->res)) && (!p->aux.p || al4(p->aux)), "aid_conv2d: x_wino views must be 16-byte aligned");
+    AID_REQUIRE(aid_view_aligned(p->x, 4) && aid_view_aligned(p->y, 4) && (!p->res.p || aid_view_aligned(p->res, 4)) && (!p->aux.p || aid_view_aligned(p->aux, 4)), "aid_conv2d: x_wino views must be 16-byte aligned");
     int rc;
     rc = launch_wino_r(4, p, st);                             // row-shared tiles, two workgroups per CU (when the geometry fits)
     if (rc != 1000) return rc;
@@ -1588,15 +1587,15 @@ int aid_conv53_wino_try(const aid_conv2d_params* p, hipStream_t st) {
     if (!p->wp_wino || !(p->KH == 5 && p->KW == 3) || p->in_scale || p->act != 0) return 0;
     if ((p->Cin % 4) != 0 || p->Cout < 64 || (p->T % 4) != 0) return 0;
     if (aid_pow2ceil(p->T) < 8) return 0;
-    if ((p->x.sB % 4) || (p->x.sC % 4) || (p->x.sF % 4) || (((uintptr_t)p->x.p) & 15)) return 0;
-    if ((p->y.sB % 2) || (p->y.sC % 2) || (p->y.sF % 2) || (((uintptr_t)p->y.p) & 7)) return 0;
-    if (p->res.p && ((p->res.sB % 2) || (p->res.sC % 2) || (p->res.sF % 2) || (((uintptr_t)p->res.p) & 7))) return 0;
-    if (p->aux.p && ((p->aux.sB % 2) || (p->aux.sC % 2) || (p->aux.sF % 2) || (((uintptr_t)p->aux.p) & 7))) return 0;
+    if (!aid_view_aligned(p->x, 4)) return 0;
+    if (!aid_view_aligned(p->y, 2)) return 0;
+    if (p->res.p && !aid_view_aligned(p->res, 2)) return 0;
+    if (p->aux.p && !aid_view_aligned(p->aux, 2)) return 0;
     if ((int64_t)4 * p->x.sC >= (1LL << 31)) return 0;
     if (p->wino_taps != 30) return 0;                      // the 30-tap F(4,3) pack is the only Winograd pack
-    if ((p->y.sB % 4) || (p->y.sC % 4) || (p->y.sF % 4) || (((uintptr_t)p->y.p) & 15)) return 0;
-    if (p->res.p && ((p->res.sB % 4) || (p->res.sC % 4) || (p->res.sF % 4) || (((uintptr_t)p->res.p) & 15))) return 0;
-    if (p->aux.p && ((p->aux.sB % 4) || (p->aux.sC % 4) || (p->aux.sF % 4) || (((uintptr_t)p->aux.p) & 15))) return 0;
+    if (!aid_view_aligned(p->y, 4)) return 0;
+    if (p->res.p && !aid_view_aligned(p->res, 4)) return 0;
+    if (p->aux.p && !aid_view_aligned(p->aux, 4)) return 0;
     int rc;
     if (p->Cout_pad % 64 == 0 && wino_tile_n(p->B, p->Cout_pad, p->F, p->T) == 256)
                                     rc = launch_wino4<1, 1, 2, 2, 16, 2, 2>(p, st);   // 64 x 256, 4 waves: small grids

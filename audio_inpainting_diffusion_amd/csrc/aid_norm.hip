@@ -88,9 +88,7 @@ extern "C" int aid_group_stats(const aid_group_stats_params* p, void* stream) {
     AID_REQUIRE(p && p->x.p && p->gamma && p->scale && p->ws, "aid_group_stats: null pointer");
     AID_REQUIRE(p->groups > 0 && p->groups <= 64 && p->C % p->groups == 0, "aid_group_stats: C must be divisible by groups (<= 64)");
     AID_REQUIRE(p->ws_n >= 0, "aid_group_stats: bad ws_n");
-    AID_REQUIRE((p->T % 4) == 0 && (p->x.sB % 4) == 0 && (p->x.sC % 4) == 0 && (p->x.sF % 4) == 0 &&
-                    (((uintptr_t)p->x.p) & 15) == 0,
-                "aid_group_stats: view must be float4-addressable");
+    AID_REQUIRE((p->T % 4) == 0 && aid_view_aligned(p->x, 4), "aid_group_stats: view must be float4-addressable");
     StatsDev a;
     a.p = *p;
     a.cg = p->C / p->groups;
@@ -392,7 +390,7 @@ extern "C" int aid_norm_bwd(const aid_norm_bwd_params* p, void* stream) {
         return aid_w2d_input_nb(p, a.coef, (hipStream_t)stream);
     if (p->wout.p && p->wform == 2) {
         AID_REQUIRE((p->T % 16) == 0 && !p->accumulate, "aid_norm_bwd: wout needs T % 16 == 0 and accumulate = 0 (neighbour samples are recomputed)");
-        AID_REQUIRE(p->wout.sF >= 10 * (p->T / 8) && (p->wout.sB % 4) == 0 && (p->wout.sC % 4) == 0 && (p->wout.sF % 4) == 0 && (((uintptr_t)p->wout.p) & 15) == 0,
+        AID_REQUIRE(p->wout.sF >= 10 * (p->T / 8) && aid_view_aligned(p->wout, 4),
                     "aid_norm_bwd: wout rows (wform = 2) are [10][T/8], 16-byte aligned");
         AID_REQUIRE((p->T % 8) == 0, "aid_norm_bwd: wform = 2 needs T % 8 == 0");
         hipLaunchKernelGGL(norm_bwd_wino8_kernel, dim3((unsigned)(aid_cdiv(a.nrows, rpb) * a.tiles)), dim3(256), 0, (hipStream_t)stream, a);   // (thread <-> float4, as the F(4,3) form)
@@ -402,7 +400,7 @@ extern "C" int aid_norm_bwd(const aid_norm_bwd_params* p, void* stream) {
     if (p->wout.p) {
         AID_REQUIRE(p->wform == 0 || p->wform == 1, "aid_norm_bwd: wform is 1 (F(4,3)) or 2 (F(8,3))");
         AID_REQUIRE((p->T % 16) == 0 && !p->accumulate, "aid_norm_bwd: wout needs T % 16 == 0 and accumulate = 0 (neighbour samples are recomputed)");
-        AID_REQUIRE(p->wout.sF >= 6 * (p->T / 4) && (p->wout.sB % 4) == 0 && (p->wout.sC % 4) == 0 && (p->wout.sF % 4) == 0 && (((uintptr_t)p->wout.p) & 15) == 0,
+        AID_REQUIRE(p->wout.sF >= 6 * (p->T / 4) && aid_view_aligned(p->wout, 4),
                     "aid_norm_bwd: wout rows are [6][T/4], 16-byte aligned");
         hipLaunchKernelGGL(norm_bwd_wino_kernel, dim3((unsigned)(aid_cdiv(a.nrows, rpb) * a.tiles)), dim3(256), 0, (hipStream_t)stream, a);
         AID_CHECK_LAUNCH();
@@ -558,9 +556,9 @@ extern "C" int aid_scale_act(const aid_scale_act_params* p, void* stream) {
     a.p = *p;
     if (p->wino == 2) {
         AID_REQUIRE((p->T % 16) == 0, "aid_scale_act: the Winograd-domain output needs T % 16 == 0");
-        AID_REQUIRE((p->y.sB % 2) == 0 && (p->y.sC % 2) == 0 && (p->y.sF % 2) == 0 && (((uintptr_t)p->y.p) & 7) == 0 && p->y.sF >= 10 * (p->T / 8),
+        AID_REQUIRE(aid_view_aligned(p->y, 2) && p->y.sF >= 10 * (p->T / 8),
                     "aid_scale_act: F(8,3) Winograd-domain output rows are [10][T/8], 8-byte aligned");
-        AID_REQUIRE(p->T < 32 || p->T > 64 || ((p->y.sB % 4) == 0 && (p->y.sC % 4) == 0 && (p->y.sF % 4) == 0 && (((uintptr_t)p->y.p) & 15) == 0 && (p->T % 32) == 0),
+        AID_REQUIRE(p->T < 32 || p->T > 64 || (aid_view_aligned(p->y, 4) && (p->T % 32) == 0),
                     "aid_scale_act: F(8,3) output with T = 32 / 64 needs 16-byte aligned rows (staged float4 stores)");
         int lpr = aid_pow2ceil(p->T / 16);
         if (lpr > 256) lpr = 256;
@@ -575,7 +573,7 @@ extern "C" int aid_scale_act(const aid_scale_act_params* p, void* stream) {
     if (p->wino) {
         AID_REQUIRE(p->wino == 1, "aid_scale_act: wino is 0, 1 (F(4,3)), 2 (F(8,3)) or 3 (F(4,5) x F(4,3))");
         AID_REQUIRE((p->T % 16) == 0, "aid_scale_act: the Winograd-domain output needs T % 16 == 0");
-        AID_REQUIRE((p->y.sB % 4) == 0 && (p->y.sC % 4) == 0 && (p->y.sF % 4) == 0 && (((uintptr_t)p->y.p) & 15) == 0 && p->y.sF >= 6 * (p->T / 4),
+        AID_REQUIRE(aid_view_aligned(p->y, 4) && p->y.sF >= 6 * (p->T / 4),
                     "aid_scale_act: Winograd-domain output rows are [6][T/4], 16-byte aligned");
         int lpr = aid_pow2ceil(p->T / 16);
         if (lpr > 256) lpr = 256;

@@ -200,9 +200,9 @@ extern "C" int aid_resample(const aid_resample_params* p, void* stream) {
     if (!p->adjoint) { mode = p->up ? 1 : 0; a.Tout = p->up ? 2 * p->T : p->T / 2; }
     else             { mode = p->up ? 3 : 2; a.Tout = p->up ? p->T / 2 : 2 * p->T; }   // T = length of the incoming gradient
     AID_REQUIRE(a.Tout >= 4 && (a.Tout % 4) == 0, "aid_resample: output length must be a multiple of 4");
-    AID_REQUIRE((p->y.sB % 4) == 0 && (p->y.sC % 4) == 0 && (p->y.sF % 4) == 0 && (((uintptr_t)p->y.p) & 15) == 0,
+    AID_REQUIRE(aid_view_aligned(p->y, 4),
                 "aid_resample: output view must be float4-addressable");
-    a.xvec = ((p->x.sB % 4) == 0 && (p->x.sC % 4) == 0 && (p->x.sF % 4) == 0 && (((uintptr_t)p->x.p) & 15) == 0) ? 1 : 0;
+    a.xvec = aid_view_aligned(p->x, 4) ? 1 : 0;
     const int min_in = (mode == 0) ? 4 : (mode == 1 ? 3 : 0);
     AID_REQUIRE(p->T >= min_in, "aid_resample: input too short for reflect padding");
     int lpr = aid_pow2ceil(a.Tout / 4);

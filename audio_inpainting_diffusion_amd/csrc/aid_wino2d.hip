@@ -663,7 +663,7 @@ __global__ __launch_bounds__(256) void w2d_input_kernel(const W2dInDev a) {
 static int w2d_input_launch(W2dInDev& a, int TF, bool nb, hipStream_t st) {
     AID_REQUIRE(a.dil >= 1 && (a.F % a.dil) == 0 && (a.T % 16) == 0 && a.T <= 2048, "2-D Winograd input pass: F % dilF == 0, T % 16 == 0, T <= 2048");
     AID_REQUIRE(TF == 4 || (a.T % 32) == 0, "2-D Winograd input pass with F(8,3) along T: T % 32 == 0");
-    AID_REQUIRE((a.x.sB % 4) == 0 && (a.x.sC % 4) == 0 && (a.x.sF % 4) == 0 && (((uintptr_t)a.x.p) & 15) == 0, "2-D Winograd input pass: 16-byte aligned input rows");
+    AID_REQUIRE(aid_view_aligned(a.x, 4), "2-D Winograd input pass: 16-byte aligned input rows");
     const W2dGeo ge = w2d_geo(a.B, a.F, a.T, a.dil, TF);
     AID_REQUIRE(ge.N < (1LL << 31), "2-D Winograd input pass: too many positions");
     a.R = ge.R; a.J = ge.J; a.TG = ge.TG; a.NB = ge.NB; a.N = ge.N;
@@ -716,9 +716,9 @@ int aid_w2d_input(const aid_scale_act_params* p, hipStream_t st) {
 // dgrad conv of the layer below in one pass -- reads gd, x, gy once (1.125 x with the halo rows), writes out (= dL/dx) and V
 int aid_w2d_input_nb(const aid_norm_bwd_params* p, const float* coef, hipStream_t st) {
     AID_REQUIRE(!p->accumulate && p->wdil >= 1, "aid_norm_bwd(wform=3|4): accumulate = 0 and wdil = the dilation of the layer that reads V");
-    AID_REQUIRE((p->gd.sB % 4) == 0 && (p->gd.sC % 4) == 0 && (p->gd.sF % 4) == 0 && (((uintptr_t)p->gd.p) & 15) == 0 &&
-                (p->out.sB % 4) == 0 && (p->out.sC % 4) == 0 && (p->out.sF % 4) == 0 && (((uintptr_t)p->out.p) & 15) == 0 &&
-                (!p->gy.p || ((p->gy.sB % 4) == 0 && (p->gy.sC % 4) == 0 && (p->gy.sF % 4) == 0 && (((uintptr_t)p->gy.p) & 15) == 0)),
+    AID_REQUIRE(aid_view_aligned(p->gd, 4) &&
+                aid_view_aligned(p->out, 4) &&
+                (!p->gy.p || aid_view_aligned(p->gy, 4)),
                 "aid_norm_bwd(wform=3|4): 16-byte aligned rows");
     W2dInDev a = {};
     a.x = p->x; a.scale = p->wscale; a.scale_ld = p->wscale_ld; a.V = p->wout.p; a.mul = 1.f;
@@ -1010,9 +1010,9 @@ static int w2d_check(const aid_conv2d_params* p, W2dPlan& pl) {
     AID_REQUIRE(!(p->stat_ws && p->dot_ws), "aid_conv2d(x_wino=3): stat_ws and dot_ws are exclusive");
     AID_REQUIRE(!p->dot_ws || p->epi == 1, "aid_conv2d(x_wino=3): dot_ws goes with the dGELU epilogue");
     AID_REQUIRE(p->ws && p->ws_bytes >= (int64_t)NXI * p->Cout * pl.ge.N * 4 && (((uintptr_t)p->ws) & 15) == 0, "aid_conv2d(x_wino=3|4): ws must hold 48 (80) * Cout * N floats");
-    AID_REQUIRE((p->y.sB % 4) == 0 && (p->y.sC % 4) == 0 && (p->y.sF % 4) == 0 && (((uintptr_t)p->y.p) & 15) == 0, "aid_conv2d(x_wino=3): 16-byte aligned output rows");
-    AID_REQUIRE(!p->res.p || ((p->res.sB % 4) == 0 && (p->res.sC % 4) == 0 && (p->res.sF % 4) == 0 && (((uintptr_t)p->res.p) & 15) == 0), "aid_conv2d(x_wino=3): 16-byte aligned residual rows");
-    AID_REQUIRE(!p->aux.p || ((p->aux.sB % 4) == 0 && (p->aux.sC % 4) == 0 && (p->aux.sF % 4) == 0 && (((uintptr_t)p->aux.p) & 15) == 0), "aid_conv2d(x_wino=3): 16-byte aligned aux rows");
+    AID_REQUIRE(aid_view_aligned(p->y, 4), "aid_conv2d(x_wino=3): 16-byte aligned output rows");
+    AID_REQUIRE(!p->res.p || aid_view_aligned(p->res, 4), "aid_conv2d(x_wino=3): 16-byte aligned residual rows");
+    AID_REQUIRE(!p->aux.p || aid_view_aligned(p->aux, 4), "aid_conv2d(x_wino=3): 16-byte aligned aux rows");
     const int npart = (p->Cout >> 3) * pl.nblk;          // = aid_w2d_partials()
     AID_REQUIRE(!p->stat_ws || p->stat_n == npart, "aid_conv2d(x_wino=3): stat_n != aid_conv2d_stat_partials()");
     AID_REQUIRE(!p->dot_ws || p->dot_n == npart, "aid_conv2d(x_wino=3): dot_n != aid_conv2d_dot_partials()");

@@ -85,8 +85,8 @@ CONV_CASES = [
     (2, 24, 8, 12, 8, 1, 1, 1, True, False),         # attention proj_in (scale prologue, no GELU)
     (2, 8, 24, 12, 8, 1, 1, 1, False, True),         # attention proj_out
     (2, 96, 192, 1, 8, 1, 1, 1, False, False),       # qk GEMM, F = 1
-    (1, 320, 640, 1, 128, 1, 1, 1, False, False),    # qk GEMM, larger K (split-K through the scratch buffer)
-    (2, 1024, 512, 1, 64, 1, 1, 1, False, True),     # qk-sized GEMM with gate + residual epilogue after the split-K reduction
+    (1, 320, 640, 1, 128, 1, 1, 1, False, False),    # qk GEMM, larger K: N = 128 columns -> skinny GEMM (K split 5 ways through the scratch buffer)
+    (2, 1024, 512, 1, 64, 1, 1, 1, False, True),     # qk-sized GEMM (N = 128: skinny) with gate + residual epilogue after the split-K reduction
     (1, 2560, 5120, 1, 128, 1, 1, 1, False, False),  # the reference's batch: N = 128 columns -> skinny GEMM (4 column tiles per wave, K split 8 ways)
     (1, 512, 1024, 1, 32, 1, 1, 1, False, True),     # N = 32: one column tile per wave, epilogue through the reduction
     (3, 256, 640, 1, 36, 1, 1, 1, False, True),      # N = 108: ragged last column tile (columns >= B*T masked), T not a power of two
@@ -103,18 +103,18 @@ CONV_CASES = [
     (2, 96, 8, 6, 16, 1, 1, 1, True, False),         # attention proj_in
     (2, 8, 64, 6, 16, 1, 1, 1, False, True),         # attention proj_out
     (3, 2, 40, 5, 12, 1, 1, 1, False, False),        # ragged rows, Cout not a multiple of anything
-    # 1x1 with enough positions -> streaming kernel (aid_conv1x1.hip)
-    (2, 64, 192, 16, 64, 1, 1, 1, True, True),       # two 96-wide Cout slices, per-(b,ci) prologue scale
-    (2, 96, 64, 8, 32, 1, 1, 1, False, True),        # 64-wide slice, a wave spans two rows
-    (1, 128, 128, 4, 512, 1, 1, 1, False, False),    # 128-wide slice
-    (2, 192, 96, 12, 16, 1, 1, 1, True, True),       # a wave spans four rows
-    (3, 64, 40, 16, 64, 1, 1, 1, False, True),       # Cout padded to 64: masked rows
-    (2, 512, 256, 8, 32, 1, 1, 1, False, True),      # K = 512, two 128-wide slices
-    (4, 64, 64, 18, 32, 1, 1, 1, True, True),        # F*T = 9 * 64: the 64-positions-per-wave variant
-    # 1x1 with K >= 128 -> direct-to-LDS kernel (aid_conv1x1_dma.hip)
-    (2, 128, 96, 16, 64, 1, 1, 1, True, True),       # 96-wide tile (4 waves), prologue scale on the weight fragment
-    (1, 256, 192, 8, 128, 1, 1, 1, True, True),      # three 64-wide Cout tiles, two rows per tile
-    (2, 144, 128, 8, 256, 1, 1, 1, False, True),     # K = 9 chunks (odd chunk count), 128-wide tile
+    # 1x1 with enough positions (which kernel serves each: tests/golden/conv1x1_dispatch.json pins the choice on its own cases; noted here as recorded)
+    (2, 64, 192, 16, 64, 1, 1, 1, True, True),       # direct-to-LDS kernel, three 64-wide Cout tiles, per-(b,ci) prologue scale
+    (2, 96, 64, 8, 32, 1, 1, 1, False, True),        # direct-to-LDS kernel (K = 96 > 64), 64-wide tile, TT = 32: 8 rows per tile
+    (1, 128, 128, 4, 512, 1, 1, 1, False, False),    # direct-to-LDS kernel, 128-wide tile
+    (2, 192, 96, 12, 16, 1, 1, 1, True, True),       # register-streamed kernel (K = 192, 96 channels), a 64-position tile spans four rows
+    (3, 64, 40, 16, 64, 1, 1, 1, False, True),       # direct-to-LDS kernel, Cout padded to 64: masked rows
+    (2, 512, 256, 8, 32, 1, 1, 1, False, True),      # direct-to-LDS kernel, K = 512, two 128-wide tiles
+    (4, 64, 64, 18, 32, 1, 1, 1, True, True),        # register-streamed kernel (K = 64, 64 channels), F*T = 9 * 64 positions per sample
+    # 1x1 with K >= 128
+    (2, 128, 96, 16, 64, 1, 1, 1, True, True),       # register-streamed kernel (96 channels, K = 128), prologue scale
+    (1, 256, 192, 8, 128, 1, 1, 1, True, True),      # direct-to-LDS kernel: three 64-wide Cout tiles, two rows per tile, prologue scale on the weight fragment
+    (2, 144, 128, 8, 256, 1, 1, 1, False, True),     # direct-to-LDS kernel: K = 9 chunks (odd chunk count), 128-wide tile
     # no prologue -> direct-to-LDS (global_load_lds) kernel
     (1, 64, 64, 24, 1024, 5, 3, 2, False, True),     # 64 x 512 tile, two t-tiles per row
     (2, 96, 96, 20, 256, 5, 3, 8, False, True),      # 96 x 256 tile (weight rows padded to 128 in LDS)
@@ -1051,3 +1051,101 @@ def test_qk_gemm_is_bit_identical_across_batch_sizes(L):
         outs[B] = (y, L.lib().aid_last_kernel().decode())
     assert outs[1][1].startswith("gemm_skinny") and outs[2][1].startswith("gemm_skinny") and outs[8][1].startswith("conv11_dma")
     assert torch.equal(outs[1][0], outs[8][0][:1]) and torch.equal(outs[2][0], outs[8][0][:2])
+
+
+def _c11_dispatch_cases():
+    import json
+    import os
+    from conftest import GOLDEN
+    with open(os.path.join(GOLDEN, "conv1x1_dispatch.json")) as f:
+        return json.load(f)["cases"]
+
+
+def _c11_launch(L, case):
+    """One 1x1 launch through aid_conv2d with the options of `case` = (B, Cin, Cout, F, T, act, in_scale, epi, res + out_scale, dot partials, Cin1 (x2),
+    scratch offered): returns (noted kernel name, y on the host in fp64, fp64 reference, sentinel intact)."""
+    B, Cin, Cout, Fd, T, act, isc_on, epi, res_on, dot_on, cin1, ws_on = case
+    g = torch.Generator().manual_seed(23)
+    rn = lambda *s: torch.randn(*s, generator=g)
+    x = rn(B, Cin, Fd, T)
+    w = rn(Cout, Cin, 1, 1) / math.sqrt(Cin)
+    isc = (1.0 + 0.5 * rn(B, Cin)) if isc_on else None
+    osc = (1.0 + 0.3 * rn(B, Cout)) if (res_on or epi) else None
+    res = rn(B, Cout, Fd, T) if res_on else None
+    aux, asc = (rn(B, Cout, Fd, T), 1.0 + 0.3 * rn(B, Cout)) if epi else (None, None)
+    alpha, res_scale = 0.7, 1.5
+    h = x.double()
+    if isc is not None:
+        h = h * isc.double()[:, :, None, None]
+    if act:
+        h = F.gelu(h)
+    ref = F.conv2d(h, w.double())
+    if osc is not None:
+        ref = ref * osc.double()[:, :, None, None]
+    if epi:
+        u = aux.double() * asc.double()[:, :, None, None]
+        ref = ref * (0.5 * (1 + torch.erf(u / math.sqrt(2))) + u * torch.exp(-0.5 * u * u) / math.sqrt(2 * math.pi))
+    if res is not None:
+        ref = ref + res_scale * res.double()
+    ref = alpha * ref
+    dv = lambda t: None if t is None else t.to(DEV)
+    xd, iscd, oscd, resd, auxd, ascd = dv(x), dv(isc), dv(osc), dv(res), dv(aux), dv(asc)
+    wp = L.pack_conv_weight(w.to(DEV))
+    ybig = torch.full((B, Cout + 4, Fd, T), 7.0, device=DEV)             # y is a channel slice of a larger buffer: 16-byte aligned, strided
+    p = L.Conv2dParams()
+    if cin1:
+        x1d, x2d = xd[:, :cin1].contiguous(), xd[:, cin1:].contiguous()
+        p.x, p.x2, p.Cin1 = L.view4(x1d), L.view4(x2d), cin1
+    else:
+        p.x = L.view4(xd)
+    p.y, p.res, p.aux = L.view4(ybig[:, 2:2 + Cout]), L.view4(resd), L.view4(auxd)
+    p.wp = wp.data_ptr()
+    p.in_scale, p.in_scale_ld = L.ptr(iscd), (0 if iscd is None else iscd.stride(0))
+    p.out_scale, p.out_scale_ld = L.ptr(oscd), (0 if oscd is None else oscd.stride(0))
+    p.aux_scale, p.aux_scale_ld = L.ptr(ascd), (0 if ascd is None else ascd.stride(0))
+    p.B, p.Cin, p.Cout, p.F, p.T = B, Cin, Cout, Fd, T
+    p.Cin_pad, p.Cout_pad = wp.shape[1], wp.shape[2]
+    p.KH, p.KW, p.dilF, p.act, p.epi = 1, 1, 1, act, epi
+    p.alpha, p.res_scale = alpha, res_scale
+    if ws_on:
+        ws = torch.empty(8 * B * Cout * Fd * T, device=DEV)              # eight partial planes: the most a K split asks for
+        p.ws, p.ws_bytes = ws.data_ptr(), ws.numel() * 4
+    if dot_on:
+        P = int(L.lib().aid_conv2d_dot_partials_1x1(B, Cin, Cout, Fd, T))
+        assert P > 0
+        dws = torch.full((B * 8 * P + 4,), float("nan"), device=DEV, dtype=torch.float64)
+        p.dot_ws, p.dot_n = dws.data_ptr(), P
+    L.call("aid_conv2d", p)
+    name = L.lib().aid_last_kernel().decode()
+    torch.cuda.synchronize()
+    yc = ybig[:, 2:2 + Cout].cpu().double()
+    intact = float(ybig[:, :2].min()) == 7.0 and float(ybig[:, :2].max()) == 7.0 and float(ybig[:, 2 + Cout:].min()) == 7.0 and float(ybig[:, 2 + Cout:].max()) == 7.0
+    if dot_on:
+        assert bool(torch.isnan(dws[B * 8 * P:]).all())
+        got = dws[:B * 8 * P].cpu().reshape(B, 8, P).sum(-1)
+        want = (yc * aux.double()).reshape(B, 8, Cout // 8, Fd, T).sum((2, 3, 4))
+        assert float((got - want).abs().max()) < 1e-5 * float((yc.abs() * aux.double().abs()).reshape(B, 8, -1).sum(-1).max())
+    return name, yc, ref, intact
+
+
+@pytest.mark.parametrize("rec", _c11_dispatch_cases(), ids=lambda r: "-".join(str(v) for v in r[:12]))
+def test_conv1x1_dispatch_is_as_recorded(L, rec):
+    """Which kernel serves a 1x1 launch is pinned: every case of tests/golden/conv1x1_dispatch.json (recorded once on an MI355X from the library of the
+    commit the file names, tools/conv1x1_dispatch_record.py; together the cases reach every selectable instance of the register-streamed, direct-to-LDS,
+    skinny-GEMM, streaming and tiled 1x1 kernels, profiles/r14_conv1x1_plan.txt) notes the recorded kernel name and matches the fp64 definition
+      y = alpha * (res_scale * res + out_scale * dGELU(aux * aux_scale) * (W act(x * in_scale)))
+    to 1e-5 rel-L2 (fp32 GEMM-shaped kernels, K <= 768: the budget of test_conv2d), writing nothing outside its channel slice."""
+    name, yc, ref, intact = _c11_launch(L, tuple(rec[:12]))
+    e = rel_l2(yc, ref)
+    print(f"{rec[:12]}: {name}, rel-L2 {e:.2e}")
+    assert name == rec[12], (rec, name)
+    assert e < 1e-5, e
+    assert intact, "wrote outside its channel slice"
+
+
+def test_conv1x1_dot_partials_are_refused_when_the_kernel_that_counts_them_declines(L):
+    """aid_conv2d_dot_partials_1x1 answers the register-streamed kernel's slots (F T / 64 = 8) for a 64-channel K = 64 layer; with scratch offered that kernel
+    declines, and the direct-to-LDS kernel, which would write F / ROWS * tiles = 2 slots per group, must not run on a buffer counted for another kernel:
+    the launch is refused loudly and y is untouched."""
+    with pytest.raises(L.AidError, match="dot_ws given but the 1x1 layer is not eligible"):
+        _c11_launch(L, (2, 64, 64, 8, 64, 0, 0, 1, 0, 1, 0, 1))

@@ -564,6 +564,139 @@ int main() {
     assert out[2 * len(rows)][0] == 1 and out[2 * len(rows)][12] == 4096 * (2 ** 20 // 4) * 1024 > 2 ** 31      # F(4,3), 64 channels, dilation 1: TT = 64, RA = 4
 
 
+def _conv1x1_host_grid():
+    import json
+    with open(os.path.join(GOLDEN, "conv1x1_host_grid.json")) as f:
+        return json.load(f)
+
+
+def _cin1s(cin):
+    return (16, 64, cin // 2, cin - 16, cin, 24)
+
+
+def test_conv1x1_host_queries_answer_as_recorded():
+    """aid_conv2d_pack_dims, aid_conv2d_dot_partials_1x1 and aid_conv2d_x2_supported over the recorded grid -- the network's own 1x1 layers (channels C, 2C, 8, 2
+    at each level's F), Cin in 16 ... 512 x Cout in 32 ... 288 x F in 1 ... 2048, each at T = 8 ... 2048, x2 with six Cin1 per shape: every answer equals the one
+    recorded from the library of the commit the fixture names (tools/conv1x1_host_grid.py), before the queries read one plan (csrc/aid_conv1x1_plan.h)."""
+    from audio_inpainting_diffusion_amd import _lib
+    L = _lib.lib()
+    grid = _conv1x1_host_grid()
+    B, TS = grid["B"], grid["TS"]
+    assert len(grid["commit"]) == 40 and len(grid["rows"]) == 1144 and len(TS) == 12
+    for rec in grid["rows"]:
+        cin, cout, F = rec[:3]
+        got = [cin, cout, F, *_lib.pack_dims(cin, cout), [L.aid_conv2d_dot_partials_1x1(B, cin, cout, F, T) for T in TS],
+               [sum(L.aid_conv2d_x2_supported(cin, c1, cout, F, T) << i for i, c1 in enumerate(_cin1s(cin))) for T in TS]]
+        assert got == rec, (dict(zip(grid["columns"], rec)), got)
+
+
+def test_conv1x1_plan_header_runs_clean_under_sanitizers_and_answers_what_the_library_answers(tmp_path):
+    """csrc/aid_conv1x1_plan.h is plain host C++: a stand-alone program built with -fsanitize=address,undefined walks the recorded grid and extreme shapes
+    (B = 4096, F = 2^20, T = 2^16, Cin = 2^20; every option set; scratch of 0, 2^20 and 2^62 bytes) through the whole chain and exits clean; its partial
+    slots and x2 verdicts are the library's aid_conv2d_dot_partials_1x1 / aid_conv2d_x2_supported, and the counts it plans with fit the kernels' ints."""
+    import shutil
+    import subprocess
+    from audio_inpainting_diffusion_amd import _lib
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++")
+    L = _lib.lib()
+    grid = _conv1x1_host_grid()
+    shapes = [(grid["B"], r[0], r[1], r[2], T) for r in grid["rows"] for T in grid["TS"] if T in (8, 16, 48, 256, 2048)]
+    n_grid = len(shapes)
+    shapes += [(B, ci, co, F, T) for B in (1, 4096, 2 ** 31 - 1) for ci in (64, 256, 1 << 20) for co in (64, 96, 128, 1 << 20) for F in (1, 9, 1 << 20, 2 ** 31 - 1)
+               for T in (8, 1 << 16, 2 ** 31 - 1)]
+    src = tmp_path / "plan.cpp"
+    src.write_text('#include <stdio.h>\n#include "aid_conv1x1_plan.h"\nstatic const int S[][6] = {\n' +
+                   "".join("    {%d, %d, %d, %d, %d, %d},\n" % (s + (_lib.pack_dims(s[1], s[2])[1],)) for s in shapes) + '''};
+int main() {
+    for (const auto& v : S) {
+        C11Shape s = {};
+        s.B = v[0]; s.Cin = v[1]; s.Cout = v[2]; s.F = v[3]; s.T = v[4]; s.Cout_pad = v[5];
+        C11Shape q = s;
+        q.epi = 1; q.dot = true;
+        printf("%d", c11_plan(q).slots);
+        const int c1[6] = {16, 64, s.Cin / 2, s.Cin - 16, s.Cin, 24};
+        for (int i = 0; i < 6; ++i) {
+            C11Shape x = s;
+            x.B = 1; x.x2 = true; x.Cin1 = c1[i];
+            printf(" %d", c11_dma_plan(x).family ? 1 : 0);
+        }
+        long long worst = 0;                                   // the largest count any option set plans with
+        for (int o = 0; o < 128; ++o)
+            for (int w = 0; w < 3; ++w) {
+                C11Shape t = s;
+                t.act = o & 1; t.in_scale = o & 2; t.epi = (o >> 2) & 1; t.res = o & 8; t.x2 = o & 16; t.dot = o & 32; t.ws = w > 0;
+                t.Cin1 = (o & 64) ? 16 : s.Cin / 2;
+                t.ws_bytes = w == 1 ? (1LL << 20) : (w == 2 ? (1LL << 62) : 0);
+                const C11Plan pl = c11_plan(t);
+                if (!pl.ok) continue;
+                const long long c[] = {pl.nrows, pl.nx, (long long)pl.nx * pl.ny + 7, pl.ntiles, pl.ntiles ? pl.ntiles + 2048LL : 0, pl.pblocks * pl.mchunks, pl.slots, pl.S, pl.gx};
+                for (long long k : c) worst = k > worst ? k : worst;
+                if (pl.family == C11_STREAM && pl.npos != (long long)t.B * t.F * t.T) return 2;
+                if (pl.S > 1 && !c11_splitk_fits(pl.S, t.B, t.Cout, t.F, t.T, t.ws_bytes)) return 3;
+            }
+        printf(" %lld\\n", worst);
+    }
+    return 0;
+}
+''')
+    exe = tmp_path / "plan"
+    subprocess.check_call([gxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I" + os.path.join(ROOT, "audio_inpainting_diffusion_amd", "csrc"), str(src), "-o", str(exe)])
+    run = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert run.returncode == 0 and not run.stderr, (run.returncode, run.stderr[-2000:])
+    out = [[int(v) for v in line.split()] for line in run.stdout.splitlines()]
+    assert len(out) == len(shapes)
+    nonzero = 0
+    for (B, cin, cout, F, T), o in zip(shapes, out):
+        assert o[0] == L.aid_conv2d_dot_partials_1x1(B, cin, cout, F, T), (B, cin, cout, F, T, o)
+        assert o[1:7] == [L.aid_conv2d_x2_supported(cin, c1, cout, F, T) for c1 in _cin1s(cin)], (B, cin, cout, F, T, o)
+        assert 0 <= o[7] <= 2 ** 31 - 1, (B, cin, cout, F, T, o)
+        nonzero += o[0] > 0
+    assert nonzero >= 1000 and any(o[0] > 0 for o in out[n_grid:]) and any(o[0] == 0 for o in out[n_grid:])
+
+
+def test_conv1x1_plan_names_the_kernel_that_the_dispatch_recording_names(tmp_path):
+    """c11_plan (the chain rs, dma, stream, tiled on scalars, which the host queries read) and aid_conv2d's dispatch (the same chain through the *_try
+    functions) state the order twice: for every case of tests/golden/conv1x1_dispatch.json the family and K split of c11_plan, from a stand-alone program
+    over the header, name the kernel that the recording (aid_last_kernel after aid_conv2d on an MI355X) names."""
+    import json
+    import shutil
+    import subprocess
+    from audio_inpainting_diffusion_amd import _lib
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++")
+    with open(os.path.join(GOLDEN, "conv1x1_dispatch.json")) as f:
+        cases = json.load(f)["cases"]
+    assert len(cases) >= 61
+    src = tmp_path / "family.cpp"
+    src.write_text('#include <stdio.h>\n#include "aid_conv1x1_plan.h"\nstatic const int S[][13] = {\n' +
+                   "".join("    {%s},\n" % ", ".join(str(v) for v in c[:12] + [_lib.pack_dims(c[1], c[2])[1]]) for c in cases) + '''};
+int main() {
+    for (const auto& v : S) {
+        C11Shape s = {};
+        s.B = v[0]; s.Cin = v[1]; s.Cout = v[2]; s.F = v[3]; s.T = v[4]; s.act = v[5]; s.in_scale = v[6]; s.epi = v[7]; s.res = v[8]; s.dot = v[9];
+        s.Cin1 = v[10]; s.x2 = v[10] > 0; s.ws = v[11]; s.ws_bytes = v[11] ? 4LL * 8 * v[0] * v[2] * v[3] * v[4] : 0; s.Cout_pad = v[12];
+        const C11Plan pl = c11_plan(s);
+        printf("%d %d %d\\n", pl.ok ? pl.family : -1, pl.S, pl.slots);
+    }
+    return 0;
+}
+''')
+    exe = tmp_path / "family"
+    subprocess.check_call([gxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "audio_inpainting_diffusion_amd", "csrc"), str(src), "-o", str(exe)])
+    out = [[int(v) for v in line.split()] for line in subprocess.check_output([str(exe)], text=True).splitlines()]
+    names = {1: "conv11_rs_kernel", 2: "conv11_dma_kernel", 3: "gemm_skinny_kernel+splitk", 4: "conv11_dma_kernel+splitk", 5: "conv1x1_stream_kernel"}
+    assert len(out) == len(cases)
+    for c, (family, S, slots) in zip(cases, out):
+        want = names[family] if family else ("conv_mfma_kernel+splitk" if S > 1 else "conv_mfma_kernel(1x1)")
+        assert want == c[12], (c, family, S)
+        assert (slots > 0) == bool(c[9]) and (not c[9] or slots == _lib.lib().aid_conv2d_dot_partials_1x1(*c[:5])), (c, slots)
+    assert {c[12] for c in cases} == set(names.values()) | {"conv_mfma_kernel+splitk", "conv_mfma_kernel(1x1)"}
+
+
 def test_two_dimensional_winograd_choice_is_a_function_of_the_launch_shape():
     """aid_conv2d_wino2d_supported / _wanted / _positions (pure host functions): K = 256 levels always (padding up to 4/3), K = 128 levels with T <= 256 up to
     1.2 padding (longer rows only for launches of at most two samples), nothing below 128 channels; positions = B * ceil(F / (4 dil)) * dil * T / 4."""
