@@ -1,4 +1,4 @@
-"""ctypes binding of libaid_hip.so (the C ABI in include/aid_kernels.h, include/aid_degrade.h, include/aid_phase.h, include/aid_autoregressive.h, include/aid_restore.h and include/aid_declip.h).
+"""ctypes binding of libaid_hip.so (the C ABI in include/aid_kernels.h, include/aid_degrade.h, include/aid_phase.h, include/aid_autoregressive.h, include/aid_restore.h, include/aid_declip.h and include/aid_resample_op.h).
 
 There is deliberately NO fallback: if the shared library is missing or a launcher returns an error code,
 ``AidError`` is raised.  Tensors are passed as raw device pointers + element strides; the stream is torch's
@@ -333,6 +333,16 @@ class DeclipGatherParams(C.Structure):
 AID_DECLIP_ABI_VERSION = 1
 DECLIP_EXPORTS = ["aid_declip_abi_version", "aid_clip_known", "aid_declip_gather"]
 
+# ---- include/aid_resample_op.h (the resampling degradation of bandwidth extension: the adjoint of aid_resample_poly; a header and export list of their own) ----
+class ResamplePolyAdjParams(C.Structure):
+    _fields_ = [("g", C.c_void_p), ("gx", C.c_void_p), ("kT", C.c_void_p), ("j_lo", C.c_void_p), ("j_hi", C.c_void_p),
+                ("g_ld", C.c_int64), ("gx_ld", C.c_int64), ("L", C.c_int64), ("Lout", C.c_int64),
+                ("B", C.c_int), ("orig_freq", C.c_int), ("new_freq", C.c_int), ("width", C.c_int), ("K", C.c_int)]
+
+
+AID_RESAMPLE_OP_ABI_VERSION = 1
+RESAMPLE_OP_EXPORTS = ["aid_resample_op_abi_version", "aid_resample_poly_adj"]
+
 EXPORTS = ["aid_abi_version", "aid_last_error", "aid_last_kernel", "aid_group_stats", "aid_conv2d", "aid_conv2d_pack_dims", "aid_conv2d_stat_partials", "aid_pack_conv_weight", "aid_wino_gy", "aid_conv2d_wgrad_tiles", "aid_resample",
            "aid_time_attention", "aid_embed", "aid_modulation", "aid_cqt_analysis", "aid_cqt_synthesis",
            "aid_cqt_gather", "aid_axpby", "aid_score_step", "aid_add2", "aid_group_dot", "aid_norm_bwd",
@@ -439,6 +449,14 @@ def lib():
         L.aid_declip_abi_version.argtypes = []
         if L.aid_declip_abi_version() != AID_DECLIP_ABI_VERSION:
             raise AidError("include/aid_declip.h ABI version mismatch")
+        for name in RESAMPLE_OP_EXPORTS:
+            if not hasattr(L, name):
+                raise AidError(f"libaid_hip.so does not export {name}")
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
+            getattr(L, name).restype = C.c_int
+        L.aid_resample_op_abi_version.argtypes = []
+        if L.aid_resample_op_abi_version() != AID_RESAMPLE_OP_ABI_VERSION:
+            raise AidError("include/aid_resample_op.h ABI version mismatch")
         _lib = L
     return _lib
 

@@ -9,13 +9,17 @@ defined, :47-54), ``shared_mask`` and ``__call__ = apply`` -- running on HIP ker
     or a strided correlation with symmetric integer padding;
   * ``Decimate(factor, L)``: x[..., 0:-1:factor] (:259-260);
   * ``IIRFilter(b, a, L, clamp=False)`` / ``IIRFilter.biquad(...)``: lfilter (:253-258), recursion in fp64;
-  * ``HardClip(clip_value)``: clip(x, -c, c) (:366-368).
+  * ``HardClip(clip_value)``: clip(x, -c, c) (:366-368);
+  * ``SincResample(orig_freq, new_freq, L)`` / ``SincResample.from_factor(factor, L)``: torchaudio.functional.resample with its default
+    Hann-windowed sinc kernel (:262-264), [B, L] -> [B, ceil(new*L/orig)] (aid_resample_poly and, include/aid_resample_op.h, its adjoint).
 
 None holds per-item data, so sub-batches on concurrent streams may share one (``shared_mask`` is True); per-call state
 (the clip's x_hat, the IIR scratch) is keyed by the current stream.  Tables are built once on the host in float64 and
 kept on the device.  GPU only; no fallback.
 """
 from __future__ import annotations
+
+import math
 
 import numpy as np
 import torch
@@ -254,3 +258,122 @@ class HardClip(_Operator):
         if xref is None or xref.numel() != g.numel():
             raise _lib.AidError("HardClip.adjoint needs the matching apply on this stream first")
         return self._run(g, 1, xref=xref)
+
+
+# ---- the resampling degradation: torchaudio's default resampler and its adjoint -------------------------------------------------------
+def sinc_kernel(orig: int, new: int, lowpass_filter_width: int = 6, rolloff: float = 0.99):
+    """Hann-windowed sinc per output phase, [new, 2*width + orig] float64 -- torchaudio's default resampling kernel."""
+    base = min(orig, new) * rolloff
+    width = math.ceil(lowpass_filter_width * orig / base)
+    idx = np.arange(-width, width + orig, dtype=np.float64)[None, :] / orig
+    t = np.arange(0, -new, -1, dtype=np.float64)[:, None] / new + idx
+    t = np.clip(t * base, -lowpass_filter_width, lowpass_filter_width)
+    window = np.cos(t * math.pi / lowpass_filter_width / 2) ** 2
+    t = t * math.pi
+    k = np.where(t == 0, 1.0, np.sin(t) / np.where(t == 0, 1.0, t)) * window * (base / orig)
+    return k, width
+
+
+def resample_host_tables(orig: int, new: int):
+    """(k [new, K] float32 -- the table aid_resample_poly takes --, width, kT [K, new] float32 = k transposed, j_lo [K], j_hi [K] int32):
+    [j_lo[t], j_hi[t]) is the tight range of phases outside which tap t of the float32 table is exactly 0.0f (the clamped Hann window;
+    an all-zero tap gets the empty range [0, 0)), so the adjoint may skip every other term without changing its sum."""
+    k64, width = sinc_kernel(orig, new)
+    k = np.ascontiguousarray(k64, dtype=np.float32)
+    kT = np.ascontiguousarray(k.T)
+    nz = kT != 0
+    any_nz = nz.any(axis=1)
+    j_lo = np.where(any_nz, nz.argmax(axis=1), 0).astype(np.int32)
+    j_hi = np.where(any_nz, new - nz[:, ::-1].argmax(axis=1), 0).astype(np.int32)
+    return k, width, kT, j_lo, j_hi
+
+
+_RESAMPLE_TABLES = {}
+
+
+def resample_tables(orig: int, new: int, device):
+    """The device copies of resample_host_tables, built once per (ratio, device) and shared by harness.resample and SincResample:
+    (k, width, kT, j_lo, j_hi).  The upload is waited for, so that any stream may read the tables afterwards."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (orig, new, device)
+    tab = _RESAMPLE_TABLES.get(key)
+    if tab is None:
+        k, width, kT, j_lo, j_hi = resample_host_tables(orig, new)
+        tab = (torch.from_numpy(k).to(device), width) + tuple(torch.from_numpy(a).to(device) for a in (kT, j_lo, j_hi))
+        if device.type == "cuda":
+            torch.cuda.current_stream(device).synchronize()
+        _RESAMPLE_TABLES[key] = tab
+    return tab
+
+
+def resample_poly(x, orig: int, new: int):
+    """x [B, L] contiguous float32 on the GPU -> [B, ceil(new*L/orig)] (aid_resample_poly), orig / new already divided by their gcd"""
+    k, width = resample_tables(orig, new, x.device)[:2]
+    B, L = x.shape
+    Lout = (new * L + orig - 1) // orig
+    y = torch.empty(B, Lout, device=x.device, dtype=torch.float32)
+    p = _lib.ResamplePolyParams(x.data_ptr(), y.data_ptr(), k.data_ptr(), x.stride(0), y.stride(0), L, Lout, B, orig, new, width, k.shape[1])
+    _lib.call("aid_resample_poly", p)
+    return y
+
+
+def bwe_resample_ratio(factor):
+    """(orig, new) of the reference's "resample" degradation for a bandwidth-extension factor: orig_freq = int(100 * factor), new_freq = 100
+    (edm_sampler.py:262-264, truncation included: 1.15 -> 114:100), divided by their gcd."""
+    try:
+        f = float(factor)
+    except (TypeError, ValueError):
+        raise _lib.AidError(f"resample: the factor must be a number, got {factor!r}") from None
+    if not 0 < f <= 16:
+        raise _lib.AidError(f"resample: the factor must lie in (0, 16], got {factor!r}")
+    o = int(100 * f)
+    if o < 1:
+        raise _lib.AidError(f"resample: int(100 * factor) = {o} for factor {factor!r}: no input rate")
+    g = math.gcd(o, 100)
+    return o // g, 100 // g
+
+
+class SincResample(_Operator):
+    """torchaudio.functional.resample(x, orig_freq, new_freq) with its default kernel (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99):
+    y[b, i*new + j] = sum_t k[j][t] * x[b, i*orig + t - width], [B, L] -> [B, L_out = ceil(new*L/orig)] -- the reference's "resample"
+    degradation of bandwidth extension (edm_sampler.py:262-264).  ``apply`` is harness.resample's launch on harness.resample's table;
+    ``adjoint`` is the exact transpose (aid_resample_poly_adj).  Ratio 1:1 is the identity (torchaudio returns its input): no launch.
+    The tables are built at the first launch; the object itself holds no device memory and no per-call state."""
+
+    def __init__(self, orig_freq: int, new_freq: int, audio_len: int, device="cuda"):
+        o, n = int(orig_freq), int(new_freq)
+        if o < 1 or n < 1:
+            raise _lib.AidError(f"SincResample: the frequencies must be >= 1, got {orig_freq!r} and {new_freq!r}")
+        if int(audio_len) < 1:
+            raise _lib.AidError(f"SincResample: the signal must hold at least 1 sample, got audio_len = {audio_len!r}")
+        if torch.device(device).type != "cuda":
+            raise _lib.AidError("SincResample runs on the GPU only (no CPU fallback)")
+        g = math.gcd(o, n)
+        self.orig, self.new, self.L = o // g, n // g, int(audio_len)
+        self.L_out = (self.new * self.L + self.orig - 1) // self.orig
+        self.identity = self.orig == self.new
+
+    @classmethod
+    def from_factor(cls, factor, audio_len: int, device="cuda"):
+        """the operator of predict_bwe(ylpf, factor, "resample"): ratio bwe_resample_ratio(factor)"""
+        return cls(*bwe_resample_ratio(factor), audio_len, device=device)
+
+    def apply(self, x):
+        """A(x): [B, L] -> [B, L_out]"""
+        if self.identity:
+            return x
+        return resample_poly(_check_signal(x.reshape(x.shape[0], -1), self.L, "SincResample"), self.orig, self.new)
+
+    def adjoint(self, g):
+        """A^T(g): [B, L_out] -> [B, L]"""
+        if self.identity:
+            return g
+        g = _check_signal(g.reshape(g.shape[0], -1), self.L_out, "SincResample.adjoint")
+        k, width, kT, j_lo, j_hi = resample_tables(self.orig, self.new, g.device)
+        gx = torch.empty(g.shape[0], self.L, device=g.device, dtype=torch.float32)
+        _lib.call("aid_resample_poly_adj", _lib.ResamplePolyAdjParams(g.data_ptr(), gx.data_ptr(), kT.data_ptr(), j_lo.data_ptr(), j_hi.data_ptr(),
+                                                                      g.stride(0), gx.stride(0), self.L, self.L_out, g.shape[0],
+                                                                      self.orig, self.new, width, kT.shape[0]))
+        return gx

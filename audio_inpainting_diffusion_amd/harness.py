@@ -193,28 +193,13 @@ def declip_long(sampler, files: Sequence[torch.Tensor], clip_values, seeds: Opti
 
 
 # ---- waveform pre-/post-processing of the tester --------------------------------------------------------------------------------
-def _sinc_kernel(orig: int, new: int, lowpass_filter_width: int = 6, rolloff: float = 0.99):
-    """Hann-windowed sinc per output phase, [new, 2*width + orig] float64 -- torchaudio's default resampling kernel."""
-    import math
-    import numpy as np
-    base = min(orig, new) * rolloff
-    width = math.ceil(lowpass_filter_width * orig / base)
-    idx = np.arange(-width, width + orig, dtype=np.float64)[None, :] / orig
-    t = np.arange(0, -new, -1, dtype=np.float64)[:, None] / new + idx
-    t = np.clip(t * base, -lowpass_filter_width, lowpass_filter_width)
-    window = np.cos(t * math.pi / lowpass_filter_width / 2) ** 2
-    t = t * math.pi
-    k = np.where(t == 0, 1.0, np.sin(t) / np.where(t == 0, 1.0, t)) * window * (base / orig)
-    return k, width
-
-
-_KERNELS = {}
+# (torchaudio's default resampling kernel: one builder and one table cache, in degrade.py, serve this module and degrade.SincResample)
+from .degrade import sinc_kernel as _sinc_kernel  # noqa: E402
 
 
 def resample(x: torch.Tensor, orig_freq: int, new_freq: int) -> torch.Tensor:
     """x [B, L] on the GPU -> [B, ceil(new*L/orig)]   (aid_resample_poly; replaces torchaudio.functional.resample)"""
     import math
-    import numpy as np
     from . import _lib
     g = math.gcd(int(orig_freq), int(new_freq))
     o, n = int(orig_freq) // g, int(new_freq) // g
@@ -222,18 +207,8 @@ def resample(x: torch.Tensor, orig_freq: int, new_freq: int) -> torch.Tensor:
         return x
     if not x.is_cuda:
         raise _lib.AidError("harness.resample runs on the GPU only (no CPU fallback)")
-    key = (o, n, x.device)
-    if key not in _KERNELS:
-        k, width = _sinc_kernel(o, n)
-        _KERNELS[key] = (torch.from_numpy(np.ascontiguousarray(k, dtype=np.float32)).to(x.device), width)
-    k, width = _KERNELS[key]
-    x = x.contiguous().float()
-    B, L = x.shape
-    Lout = (n * L + o - 1) // o
-    y = torch.empty(B, Lout, device=x.device, dtype=torch.float32)
-    p = _lib.ResamplePolyParams(x.data_ptr(), y.data_ptr(), k.data_ptr(), x.stride(0), y.stride(0), L, Lout, B, o, n, width, k.shape[1])
-    _lib.call("aid_resample_poly", p)
-    return y
+    from .degrade import resample_poly
+    return resample_poly(x.contiguous().float(), o, n)
 
 
 def _resample_one_rate(audio, f: int, fs_target: int, length_target: int) -> torch.Tensor:

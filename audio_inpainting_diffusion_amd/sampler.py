@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .degrade import Decimate, FIRFilter, HardClip, IIRFilter
+from .degrade import Decimate, FIRFilter, HardClip, IIRFilter, SincResample
 from .phase import STFTMagnitude, observation_shape
 from .stft import SpectralMask
 
@@ -386,7 +386,8 @@ class Sampler:
         """Bandwidth extension (edm_sampler.py:266-300) through the native operators of degrade.py:
         "firwin" / "firwin_hpf": taps [K], [1, K] or [1, 1, K] (conv1d padding="same");  "cheby1": (b, a) (lfilter, clamp=False);
         "biquad": (b0, b1, b2, a0, a1, a2) (torchaudio's biquad, clamp=True);  "decimate": an integer factor, ylpf [B, ceil((L-1)/f)]
-        with L = args.exp.audio_len.  "resample" is not built."""
+        with L = args.exp.audio_len;  "resample": a factor in (0, 16] -- torchaudio's default resampler from int(100 * factor) to 100
+        (degrade.SincResample.from_factor: 2 -> 2:1, 1.47 -> 147:100), ylpf [B, ceil(new*L/orig)] on the GPU."""
         dev = ylpf.device
         L = ylpf.shape[-1]
         if filt_type in ("firwin", "firwin_hpf"):
@@ -400,8 +401,13 @@ class Sampler:
             op = Decimate(filt, self.args.exp.audio_len, device=dev)
             return self.predict_resample(ylpf, (ylpf.shape[0], self.args.exp.audio_len), op)
         elif filt_type == "resample":
-            raise _lib.AidError("predict_bwe: filt_type 'resample' is not built (it needs torchaudio's resampler and an adjoint of "
-                                "aid_resample_poly); use 'decimate' or pass a degradation lambda to predict_resample")
+            if not ylpf.is_cuda:
+                raise _lib.AidError("predict_bwe: filt_type 'resample' is not built for CPU tensors: the resampling operator runs on the GPU only")
+            op = SincResample.from_factor(filt, self.args.exp.audio_len, device=dev)
+            if ylpf.dim() != 2 or ylpf.shape[1] != op.L_out:
+                raise _lib.AidError(f"predict_bwe: 'resample' at factor {filt!r} ({op.orig}:{op.new}) observes [B, {op.L_out}] of the "
+                                    f"{op.L} samples of args.exp.audio_len, got ylpf {tuple(ylpf.shape)}")
+            return self.predict_resample(ylpf, (ylpf.shape[0], self.args.exp.audio_len), op)
         else:
             raise NotImplementedError(f"predict_bwe: unknown filt_type {filt_type!r}")
         return self.predict_conditional(ylpf, op)

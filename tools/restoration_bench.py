@@ -2,8 +2,10 @@
 """Guided denoiser evaluations/s of the restoration entry points at the BASELINE.json configs[1] shape (B = 8, L = 184184,
 T = 36 schedule, xi = 0.25): one warm-up step, then --steps timed steps of each mode, alternated --rounds times.  Prints one
 JSON line.  Modes: predict_inpainting, predict_bwe firwin (K = 501), predict_bwe cheby1, predict_declipping, predict_resample with the
-equivalent torch conv1d lambda (the generic single-stream path), and phase retrieval (predict_pr: |STFT| with N = 1024, hop = 256;
-norm 2 is the spectral norm there, seeded by power iteration -- its per-item iteration counts are reported)."""
+equivalent torch conv1d lambda (the generic single-stream path), phase retrieval (predict_pr: |STFT| with N = 1024, hop = 256;
+norm 2 is the spectral norm there, seeded by power iteration -- its per-item iteration counts are reported), and, on request
+(--modes ...,bwe_resample,bwe_resample_lambda), predict_bwe "resample" at --resample-factor (degrade.SincResample) and the same
+resampler as a torch lambda through predict_resample (autograd, one stream)."""
 import argparse
 import json
 import os
@@ -20,7 +22,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--cheby-order", type=int, default=8)
     ap.add_argument("--cheby-fc", type=float, default=3000.0)
-    ap.add_argument("--modes", default="", help="comma-separated subset of the modes (default: all)")
+    ap.add_argument("--modes", default="", help="comma-separated subset of the modes (default: all but bwe_resample and bwe_resample_lambda)")
+    ap.add_argument("--resample-factor", type=float, default=2.0, help="bandwidth-extension factor of the bwe_resample modes (2 -> 2:1, 1.47 -> 147:100)")
     ap.add_argument("--pr-trajectory", action="store_true", help="after timing, run phase retrieval over the whole schedule once and "
                     "report the power-iteration counts of the spectral-norm seed per evaluation (from sigma_max down to the last step)")
     a = ap.parse_args()
@@ -52,6 +55,15 @@ def main():
     y_pr = pr_op.apply(clean.to(dev))
     pr_op.diagnostics = []
     smp = Sampler(model=net, diff_params=EDM(args), args=args)
+    from audio_inpainting_diffusion_amd.degrade import SincResample, sinc_kernel
+    rs_op = SincResample.from_factor(a.resample_factor, L, device=dev)
+    rs_k, rs_width = sinc_kernel(rs_op.orig, rs_op.new)
+    rs_k = torch.from_numpy(rs_k).float().to(dev)[:, None, :]
+
+    def rs_lambda(x):                                       # torchaudio's resample as torch ops: pad, strided conv1d over the phases, interleave, cut
+        xp = torch.nn.functional.pad(x, (rs_width, rs_width + rs_op.orig))
+        y = torch.nn.functional.conv1d(xp[:, None], rs_k, stride=rs_op.orig).transpose(1, 2).reshape(x.shape[0], -1)
+        return y[..., :rs_op.L_out]
 
     def setup(mode):
         from audio_inpainting_diffusion_amd.degrade import FIRFilter, HardClip, IIRFilter
@@ -68,6 +80,11 @@ def main():
             smp.y, smp.spectral = y_clip, HardClip(0.05)
         elif mode == "phase_retrieval":
             smp.y, smp.spectral = y_pr, pr_op
+        elif mode == "bwe_resample":
+            smp.y, smp.spectral = rs_op.apply(clean.to(dev)), rs_op
+        elif mode == "bwe_resample_lambda":
+            from audio_inpainting_diffusion_amd.sampler import LambdaDegradation
+            smp.y, smp.spectral = rs_op.apply(clean.to(dev)), LambdaDegradation(rs_lambda)
         else:
             from audio_inpainting_diffusion_amd.sampler import LambdaDegradation
             smp.y, smp.spectral = y_fir, LambdaDegradation(fir)
@@ -75,7 +92,7 @@ def main():
 
     modes = ["inpainting", "bwe_firwin", "bwe_cheby1", "declipping", "resample_lambda", "phase_retrieval"]
     if a.modes:
-        modes = [m for m in modes if m in a.modes.split(",")]
+        modes = [m for m in modes + ["bwe_resample", "bwe_resample_lambda"] if m in a.modes.split(",")]
     rates = {m: [] for m in modes}
     for _ in range(a.rounds):
         for m in modes:
@@ -108,6 +125,7 @@ def main():
                               "iterations_max_per_launch": [int(d[:, 0].max()) for d in per_eval]}
     print(json.dumps({"metric": "guided denoiser evaluations/s", "shape": [B, L], "steps": a.steps, "rounds": a.rounds,
                       "cheby1": {"order": a.cheby_order, "fc": a.cheby_fc, "fs": 22050}, "fir_taps": 501,
+                      "resample": {"factor": a.resample_factor, "orig": rs_op.orig, "new": rs_op.new, "observed": rs_op.L_out},
                       "phase_retrieval": {"win_size": 1024, "hop_size": 256, "seed": seed},
                       "evals_per_s": {m: round(v, 2) for m, v in best.items()}, "all": {m: [round(x, 2) for x in v] for m, v in rates.items()},
                       "vs_inpainting": {m: round(best[m] / best["inpainting"], 4) for m in modes} if "inpainting" in best else None}))
