@@ -1,4 +1,4 @@
-"""ctypes binding of libaid_hip.so (the C ABI in include/aid_kernels.h, include/aid_degrade.h, include/aid_phase.h, include/aid_autoregressive.h, include/aid_restore.h, include/aid_declip.h and include/aid_resample_op.h).
+"""ctypes binding of libaid_hip.so (the C ABI in include/aid_kernels.h, include/aid_degrade.h, include/aid_phase.h, include/aid_autoregressive.h, include/aid_restore.h, include/aid_declip.h, include/aid_resample_op.h and include/aid_bwe_long.h).
 
 There is deliberately NO fallback: if the shared library is missing or a launcher returns an error code,
 ``AidError`` is raised.  Tensors are passed as raw device pointers + element strides; the stream is torch's
@@ -343,6 +343,21 @@ class ResamplePolyAdjParams(C.Structure):
 AID_RESAMPLE_OP_ABI_VERSION = 1
 RESAMPLE_OP_EXPORTS = ["aid_resample_op_abi_version", "aid_resample_poly_adj"]
 
+# ---- include/aid_bwe_long.h (bandwidth extension of whole recordings: the filtered / known / unobserved / absent FIR operator and its gather; a header and export list of their own) ----
+class FirObservedParams(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("state", C.c_void_p), ("h", C.c_void_p), ("out", C.c_void_p),
+                ("B", C.c_int), ("K", C.c_int), ("mode", C.c_int), ("L", C.c_int64), ("x_ld", C.c_int64), ("y_ld", C.c_int64),
+                ("state_ld", C.c_int64), ("out_ld", C.c_int64)]
+
+
+class BweGatherParams(C.Structure):
+    _fields_ = [("rec", C.c_void_p), ("out", C.c_void_p), ("y", C.c_void_p), ("state", C.c_void_p), ("jobs", C.c_void_p),
+                ("J", C.c_int), ("R", C.c_int), ("K", C.c_int), ("L", C.c_int64), ("N", C.c_int64), ("rec_ld", C.c_int64), ("out_ld", C.c_int64)]
+
+
+AID_BWE_LONG_ABI_VERSION = 1
+BWE_LONG_EXPORTS = ["aid_bwe_long_abi_version", "aid_fir_observed", "aid_bwe_gather"]
+
 EXPORTS = ["aid_abi_version", "aid_last_error", "aid_last_kernel", "aid_group_stats", "aid_conv2d", "aid_conv2d_pack_dims", "aid_conv2d_stat_partials", "aid_pack_conv_weight", "aid_wino_gy", "aid_conv2d_wgrad_tiles", "aid_resample",
            "aid_time_attention", "aid_embed", "aid_modulation", "aid_cqt_analysis", "aid_cqt_synthesis",
            "aid_cqt_gather", "aid_axpby", "aid_score_step", "aid_add2", "aid_group_dot", "aid_norm_bwd",
@@ -457,6 +472,14 @@ def lib():
         L.aid_resample_op_abi_version.argtypes = []
         if L.aid_resample_op_abi_version() != AID_RESAMPLE_OP_ABI_VERSION:
             raise AidError("include/aid_resample_op.h ABI version mismatch")
+        for name in BWE_LONG_EXPORTS:
+            if not hasattr(L, name):
+                raise AidError(f"libaid_hip.so does not export {name}")
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
+            getattr(L, name).restype = C.c_int
+        L.aid_bwe_long_abi_version.argtypes = []
+        if L.aid_bwe_long_abi_version() != AID_BWE_LONG_ABI_VERSION:
+            raise AidError("include/aid_bwe_long.h ABI version mismatch")
         _lib = L
     return _lib
 

@@ -4,17 +4,16 @@
 //        are staged in LDS in chunks of 1024 taps; each lane owns 8 consecutive outputs and walks the taps in blocks of
 //        8 with a 16-float register window (float4 LDS reads, 64 FMAs per 24 floats read).  The 8-tap partial sums are
 //        fp32, the running sums fp64, so long filters (K = 4096) stay at fp32 rounding.  The adjoint of a stride-1
-//        correlation is the correlation with reversed taps and pad K-1-pad, so it runs the same kernel.
+//        correlation is the correlation with reversed taps and pad K-1-pad, so it runs the same kernel.  The tile loop is
+//        fir_tile of aid_fir_tile.h, which aid_fir_observed (aid_bwe_long.hip) instantiates too.
 //   fir (stride > 1): one lane per output gathers straight from global memory (decimation, short strided low-passes).
 //   iir: three launches (chunk zero-state recursion, carry scan of the N-sample state, correction), see aid_degrade.h.
 //   clip: element-wise.
 #include "aid_common.h"
 #include "aid_degrade.h"
+#include "aid_fir_tile.h"
 
 #define DG_THREADS 256
-#define FIR_R 8                          // outputs per lane (stride 1)
-#define FIR_TO (DG_THREADS * FIR_R)      // outputs per workgroup
-#define FIR_KC 1024                      // taps per LDS chunk
 #define FIR_MAX_STRIDE 16
 #define FIR_MAX_K_STRIDED 4096
 #define IIR_MAX_N 16
@@ -32,57 +31,15 @@ __device__ __forceinline__ float dg_epilogue(float a, float c0, const float* add
 }
 
 // out[b, i] = c0 * sum_k hk[k] * in[b, i + k - pad] + add1 + add2,  hk[k] = rev ? h[K-1-k] : h[k]
-__global__ __launch_bounds__(DG_THREADS) void fir_unit_kernel(const float* __restrict__ in, int64_t in_ld, int64_t Lin,
+__global__ __launch_bounds__(FIR_THREADS) void fir_unit_kernel(const float* __restrict__ in, int64_t in_ld, int64_t Lin,
                                                                float* __restrict__ out, int64_t out_ld, int64_t Lout,
                                                                const float* __restrict__ h, int K, int pad, int rev,
                                                                const float* add1, const float* add2, float c0) {
-    __shared__ __attribute__((aligned(16))) float hs[FIR_KC];
-    __shared__ __attribute__((aligned(16))) float xs[FIR_TO + FIR_KC];
     const int b = blockIdx.y, t = threadIdx.x;
     const int64_t tile0 = (int64_t)blockIdx.x * FIR_TO;
     const float* x = in + (int64_t)b * in_ld;
     double accd[FIR_R];
-#pragma unroll
-    for (int r = 0; r < FIR_R; ++r) accd[r] = 0.0;
-    for (int kc0 = 0; kc0 < K; kc0 += FIR_KC) {
-        const int kn = min(FIR_KC, K - kc0);
-        const int knp = (kn + FIR_R - 1) / FIR_R * FIR_R;
-        for (int k = t; k < knp; k += DG_THREADS) {
-            const int kg = kc0 + k;
-            hs[k] = k < kn ? h[rev ? K - 1 - kg : kg] : 0.f;
-        }
-        const int64_t q0 = tile0 + kc0 - pad;
-        for (int m = t; m < FIR_TO + knp; m += DG_THREADS) {
-            const int64_t q = q0 + m;
-            xs[m] = (q >= 0 && q < Lin) ? x[q] : 0.f;
-        }
-        __syncthreads();
-        for (int kk = 0; kk < knp; kk += FIR_R) {
-            float xw[2 * FIR_R], hv[FIR_R];
-            const float4* xp = reinterpret_cast<const float4*>(xs + t * FIR_R + kk);
-            const float4* hp = reinterpret_cast<const float4*>(hs + kk);
-#pragma unroll
-            for (int v = 0; v < FIR_R / 2; ++v) {
-                const float4 a = xp[v];
-                xw[4 * v] = a.x; xw[4 * v + 1] = a.y; xw[4 * v + 2] = a.z; xw[4 * v + 3] = a.w;
-            }
-#pragma unroll
-            for (int v = 0; v < FIR_R / 4; ++v) {
-                const float4 a = hp[v];
-                hv[4 * v] = a.x; hv[4 * v + 1] = a.y; hv[4 * v + 2] = a.z; hv[4 * v + 3] = a.w;
-            }
-            float acc[FIR_R];
-#pragma unroll
-            for (int r = 0; r < FIR_R; ++r) acc[r] = 0.f;
-#pragma unroll
-            for (int j = 0; j < FIR_R; ++j)
-#pragma unroll
-                for (int r = 0; r < FIR_R; ++r) acc[r] = fmaf(hv[j], xw[r + j], acc[r]);
-#pragma unroll
-            for (int r = 0; r < FIR_R; ++r) accd[r] += (double)acc[r];
-        }
-        __syncthreads();
-    }
+    fir_tile([&](int64_t q) { return (q >= 0 && q < Lin) ? x[q] : 0.f; }, tile0, h, K, pad, rev, accd);
 #pragma unroll
     for (int r = 0; r < FIR_R; ++r) {
         const int64_t i = tile0 + t * FIR_R + r;
@@ -129,7 +86,7 @@ extern "C" int aid_fir(const aid_fir_params* p, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (p->stride == 1) {
         const int pad = p->adjoint ? p->K - 1 - p->pad_left : p->pad_left;   // (may be negative: a plain shift)
-        hipLaunchKernelGGL(fir_unit_kernel, dim3(aid_cdiv(Lout, FIR_TO), p->B), dim3(DG_THREADS), 0, st,
+        hipLaunchKernelGGL(fir_unit_kernel, dim3(aid_cdiv(Lout, FIR_TO), p->B), dim3(FIR_THREADS), 0, st,
                            p->x, p->x_ld, Lin, p->out, p->out_ld, Lout, p->h, p->K, pad, p->adjoint, p->add1, p->add2, p->c0);
     } else {
         AID_REQUIRE(p->K <= FIR_MAX_K_STRIDED, "aid_fir: strided filters take at most 4096 taps");

@@ -1,4 +1,4 @@
-// Row helpers shared by the streaming kernels of whole-recording restoration (aid_restore.hip, aid_declip.hip): the job table of
+// Row helpers shared by the streaming kernels of whole-recording restoration (aid_restore.hip, aid_declip.hip, aid_bwe_long.hip): the job table of
 // include/aid_restore.h, float4 access over the 16-byte-aligned body of a row with scalars at its ragged ends, and the tile count.
 //
 //   A row is written with float4 stores over the 16-byte-aligned body of the DESTINATION and scalar stores over its head (< 4 elements)

@@ -192,6 +192,26 @@ def declip_long(sampler, files: Sequence[torch.Tensor], clip_values, seeds: Opti
     return out
 
 
+def bwe_long(sampler, files: Sequence[torch.Tensor], filt, filt_type: str = "firwin", seeds: Optional[Sequence[int]] = None, max_batch: int = 8,
+             device="cuda") -> List[torch.Tensor]:
+    """Bandwidth-extend every 1-D waveform of ``files`` (any lengths), each low-passed as a whole with the FIR taps ``filt`` (one filter for all
+    files), and return the full-length results on ``device``, in the order of ``files``.  Files of equal length go through ONE
+    Sampler.predict_bwe_long call, so their windows share the two batched passes; every other length is a call of its own.  ``seeds``: one RNG
+    seed per file (file i's result then depends on seeds[i] alone, not on the grouping)."""
+    if seeds is not None and len(seeds) != len(files):
+        raise ValueError(f"bwe_long: {len(seeds)} seeds for {len(files)} files")
+    groups = {}
+    for i, x in enumerate(files):
+        groups.setdefault(x.numel(), []).append(i)
+    out: List[Optional[torch.Tensor]] = [None] * len(files)
+    for idx in groups.values():
+        y = torch.stack([files[i].reshape(-1).float() for i in idx]).to(device)
+        res = sampler.predict_bwe_long(y, filt, filt_type, max_batch=max_batch, seeds=None if seeds is None else [int(seeds[i]) for i in idx])
+        for k, i in enumerate(idx):
+            out[i] = res[k]
+    return out
+
+
 # ---- waveform pre-/post-processing of the tester --------------------------------------------------------------------------------
 # (torchaudio's default resampling kernel: one builder and one table cache, in degrade.py, serve this module and degrade.SincResample)
 from .degrade import sinc_kernel as _sinc_kernel  # noqa: E402

@@ -16,7 +16,7 @@ autoregressive mode, testing/edm_sampler.py:416).
 
 ``restore_plan`` is host code (the only part that looks at the mask on the host); ``window_gather`` / ``window_scatter`` launch the
 two HIP kernels of csrc/aid_restore.hip; ``restore_passes`` is the pass code, driven with anything that has ``predict_inpainting``;
-``run_passes`` is the loop it shares with the declipping of whole recordings (declip_long.py).
+``run_passes`` is the loop it shares with the declipping (declip_long.py) and the bandwidth extension (bwe_long.py) of whole recordings.
 """
 from __future__ import annotations
 

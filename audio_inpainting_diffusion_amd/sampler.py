@@ -528,6 +528,24 @@ class Sampler:
         self._check_model()
         return declip_long.declip_passes(self, y, clip_value, L, end, max_batch, seeds)      # (validates its arguments before anything is launched)
 
+    def predict_bwe_long(self, y, filt, filt_type, max_batch=8, seeds=None):
+        """Bandwidth-extend whole recordings y[R, N] -- N any length, low-passed as a whole with the FIR taps ``filt`` ([K], [1, K] or [1, 1, K],
+        conv1d padding="same", as predict_bwe takes them) -> [R, N] on y.device (bwe_long.py).  filt_type "firwin" / "firwin_hpf" only: an IIR
+        filter ("cheby1", "biquad") carries state from the start of the recording and a decimator's phase ("decimate", "resample") depends on
+        the window start, so neither windows; they are refused.  The window grid, the two batched passes and the seeds are those of
+        predict_inpainting_long, with every window a job and the ownership trimmed by K - 1 samples (more than one window needs
+        end = int(overlap * L) >= 2 (K - 1)).  Each chunk of at most ``max_batch`` windows is one predict_resample through bwe_long.FIRObserved,
+        which uses a filtered sample as an observation only where the window holds its whole filter support and takes the overlaps its
+        neighbours restored as known.  tester.data_consistency off / "end" / "always" mean what they mean for predict_bwe."""
+        from . import bwe_long
+        if self.rid:
+            raise _lib.AidError("predict_bwe_long returns the restored recordings only: rid must be False")
+        L = int(self.args.exp.audio_len)
+        end = int(autoregressive_overlap(self.args) * L)
+        bwe_long.check_bwe_args(y, filt, filt_type, L, end, max_batch, seeds)
+        self._check_model()
+        return bwe_long.bwe_passes(self, y, filt, filt_type, L, end, max_batch, seeds)
+
     # ---- the remaining public methods of the reference class (its testers never call them; kept so that code written against
     # ---- testing.edm_sampler_inpainting.Sampler finds every name).  They run outside the sampling loop. ------------------------------
     def apply_mask(self, x, mask=None):

@@ -1,0 +1,81 @@
+/*
+ * aid_bwe_long.h -- C ABI of bandwidth extension of whole recordings in libaid_hip.so (gfx950): the observation operator of a
+ * window seen through a stride-1 FIR filter, whose samples are filtered, known, unobserved or absent, and the gather that
+ * builds its per-window inputs.
+ *
+ * A low-passed recording longer than one model segment is restored on the window grid of aid_restore.h (bwe_long.py): every
+ * even window as one batch, then the odd ones, whose first and last samples are the already restored overlaps.  The recording
+ * was filtered as a whole ("same" padding: zeros before its first and after its last sample), so inside a window only the
+ * samples that hold the whole filter support behind them are observations of the window.  Every sample of a window carries a
+ * STATE, one float:
+ *
+ *      0   filtered:    y = sum_k h[k] xin[i + k - P]     (the low-passed recording; P = (K-1)/2)
+ *      1   known:       y = x                             (an overlap sample another window restored)
+ *     -1   unobserved:  no observation                    (the sample exists and feeds its neighbours' observations; its own
+ *                                                          filtered value depends on samples outside the window)
+ *     -2   absent:      no observation                    (the sample lies beyond the end of the recording: it enters the
+ *                                                          filter as 0, the recording's own padding)
+ *
+ * Any state > 0 is read as 1, any state <= -2 as -2 and any other state < 0 as -1.
+ *
+ * Same boundary contract as aid_kernels.h: raw device pointers, sizes, offsets and row strides in ELEMENTS, a
+ * hipStream_t passed as void*, 0 or a negative AID_E_* code, no allocation, no synchronisation.
+ */
+#ifndef AID_BWE_LONG_H
+#define AID_BWE_LONG_H
+
+#include <stdint.h>
+#include "aid_kernels.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define AID_BWE_LONG_ABI_VERSION 1
+int aid_bwe_long_abi_version(void);
+
+/* ---------------------------------------------------------------------------------------------------
+ * aid_fir_observed -- signals [B, L] fp32, taps h[K], k = state[b, i], P = (K-1)/2; samples outside [0, L) are 0.
+ *   mode 0 (apply):       xin = k <= -2 ? 0 : x;  c[i] = sum_{j<K} h[j] xin[i + j - P]
+ *                         out = k > 0 ? x : (k == 0 ? c : 0)
+ *   mode 1 (adjoint):     gin = k == 0 ? x : 0;   a[i] = sum_{j<K} h[j] gin[i - j + P]         x: incoming gradient
+ *                         out = k <= -2 ? 0 : (k > 0 ? a + x : a)
+ *   mode 2 (projection):  c as in mode 0;  out = k > 0 ? y : (k == 0 ? (y - c) + x : x)
+ *   x, out: row strides x_ld, out_ld >= L; y (mode 2): row stride y_ld >= L, may be null otherwise; state: [B, L] with row
+ *   stride state_ld >= L, or one shared row (state_ld = 0).  out must not overlap an input.  The sums are those of aid_fir at
+ *   stride 1 (aid_degrade.h), in the same order: with every state 0, modes 0 and 1 give aid_fir's bits ("same" padding and its
+ *   adjoint), and mode 2 those of aid_fir's epilogue -c + y + x.  Selections are exact: a known output of mode 0 is x itself.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct {
+    const float* x; const float* y; const float* state; const float* h;
+    float* out;
+    int B, K, mode;
+    int64_t L, x_ld, y_ld, state_ld, out_ld;
+} aid_fir_observed_params;
+int aid_fir_observed(const aid_fir_observed_params* p, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * aid_bwe_gather -- for job j of the table of aid_restore.h (r, s, head, tail, lo, hi; 6 int64) and i < L, q = s_j + i,
+ *   P = (K-1)/2, Q = K-1-P; the first match decides:
+ *   q >= N                                                   state[j, i] = -2,  y[j, i] = 0
+ *   i < head_j  or  i >= L - tail_j                          state[j, i] =  1,  y[j, i] = out[r_j, q]
+ *   (s_j > 0 and i < P)  or  (s_j + L < N and i >= L - Q)    state[j, i] = -1,  y[j, i] = 0
+ *   otherwise                                                state[j, i] =  0,  y[j, i] = rec[r_j, q]
+ *   rec, out: [R, N] with row strides rec_ld, out_ld >= N; y, state: contiguous [J, L].  y and state must not overlap rec or
+ *   out.  The table is device memory: a job whose r is outside [0, R) or whose s is outside [0, N) is skipped (y = 0,
+ *   state = -2 over its row); head and tail are clamped to [0, L].  One launch serves a whole pass; copies only (bit-exact).
+ *   The samples go back with aid_window_scatter.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct {
+    const float* rec; const float* out;
+    float* y; float* state;
+    const int64_t* jobs;
+    int J, R, K;
+    int64_t L, N, rec_ld, out_ld;
+} aid_bwe_gather_params;
+int aid_bwe_gather(const aid_bwe_gather_params* p, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* AID_BWE_LONG_H */
