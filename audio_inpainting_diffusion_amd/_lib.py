@@ -1,4 +1,4 @@
-"""ctypes binding of libaid_hip.so (the C ABI in include/aid_kernels.h, include/aid_degrade.h, include/aid_phase.h, include/aid_autoregressive.h, include/aid_restore.h, include/aid_declip.h, include/aid_resample_op.h and include/aid_bwe_long.h).
+"""ctypes binding of libaid_hip.so (the C ABI in include/aid_kernels.h, include/aid_degrade.h, include/aid_phase.h, include/aid_autoregressive.h, include/aid_restore.h, include/aid_declip.h, include/aid_resample_op.h, include/aid_bwe_long.h and include/aid_lowrate_long.h).
 
 There is deliberately NO fallback: if the shared library is missing or a launcher returns an error code,
 ``AidError`` is raised.  Tensors are passed as raw device pointers + element strides; the stream is torch's
@@ -358,6 +358,22 @@ class BweGatherParams(C.Structure):
 AID_BWE_LONG_ABI_VERSION = 1
 BWE_LONG_EXPORTS = ["aid_bwe_long_abi_version", "aid_fir_observed", "aid_bwe_gather"]
 
+# ---- include/aid_lowrate_long.h (bandwidth extension of whole low-sample-rate recordings: the known / observed / unobserved / absent resampling operator and its gather; a header and export list of their own) ----
+class RateObservedParams(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("state", C.c_void_p), ("k", C.c_void_p), ("kT", C.c_void_p), ("j_lo", C.c_void_p), ("j_hi", C.c_void_p), ("out", C.c_void_p),
+                ("L", C.c_int64), ("Mw", C.c_int64), ("x_ld", C.c_int64), ("state_ld", C.c_int64), ("out_ld", C.c_int64),
+                ("B", C.c_int), ("mode", C.c_int), ("orig_freq", C.c_int), ("new_freq", C.c_int), ("width", C.c_int), ("K", C.c_int)]
+
+
+class LowrateGatherParams(C.Structure):
+    _fields_ = [("rec", C.c_void_p), ("out", C.c_void_p), ("y", C.c_void_p), ("state", C.c_void_p), ("jobs", C.c_void_p),
+                ("L", C.c_int64), ("Mw", C.c_int64), ("N", C.c_int64), ("M", C.c_int64), ("rec_ld", C.c_int64), ("out_ld", C.c_int64),
+                ("J", C.c_int), ("R", C.c_int), ("orig_freq", C.c_int), ("new_freq", C.c_int), ("width", C.c_int), ("K", C.c_int)]
+
+
+AID_LOWRATE_LONG_ABI_VERSION = 1
+LOWRATE_LONG_EXPORTS = ["aid_lowrate_long_abi_version", "aid_rate_observed", "aid_lowrate_gather"]
+
 EXPORTS = ["aid_abi_version", "aid_last_error", "aid_last_kernel", "aid_group_stats", "aid_conv2d", "aid_conv2d_pack_dims", "aid_conv2d_stat_partials", "aid_pack_conv_weight", "aid_wino_gy", "aid_conv2d_wgrad_tiles", "aid_resample",
            "aid_time_attention", "aid_embed", "aid_modulation", "aid_cqt_analysis", "aid_cqt_synthesis",
            "aid_cqt_gather", "aid_axpby", "aid_score_step", "aid_add2", "aid_group_dot", "aid_norm_bwd",
@@ -480,6 +496,14 @@ def lib():
         L.aid_bwe_long_abi_version.argtypes = []
         if L.aid_bwe_long_abi_version() != AID_BWE_LONG_ABI_VERSION:
             raise AidError("include/aid_bwe_long.h ABI version mismatch")
+        for name in LOWRATE_LONG_EXPORTS:
+            if not hasattr(L, name):
+                raise AidError(f"libaid_hip.so does not export {name}")
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
+            getattr(L, name).restype = C.c_int
+        L.aid_lowrate_long_abi_version.argtypes = []
+        if L.aid_lowrate_long_abi_version() != AID_LOWRATE_LONG_ABI_VERSION:
+            raise AidError("include/aid_lowrate_long.h ABI version mismatch")
         _lib = L
     return _lib
 

@@ -212,6 +212,30 @@ def bwe_long(sampler, files: Sequence[torch.Tensor], filt, filt_type: str = "fir
     return out
 
 
+def bwe_lowrate_long(sampler, files: Sequence[torch.Tensor], factor, filt_type: str = "resample", lengths: Optional[Sequence[Optional[int]]] = None,
+                     seeds: Optional[Sequence[int]] = None, max_batch: int = 8, device="cuda") -> List[torch.Tensor]:
+    """Bandwidth-extend every 1-D low-sample-rate waveform of ``files`` (any lengths; one ``factor`` and ``filt_type`` for all files) and return the
+    high-rate results on ``device``, in the order of ``files``.  ``lengths``: the number of high-rate samples per file (None, for all files or for
+    one: the largest consistent with the file).  Files of equal (low-rate length, length) go through ONE Sampler.predict_bwe_lowrate_long call, so
+    their windows share the two batched passes; every other pair is a call of its own.  ``seeds``: one RNG seed per file (file i's result then
+    depends on seeds[i] alone, not on the grouping)."""
+    if lengths is not None and len(lengths) != len(files):
+        raise ValueError(f"bwe_lowrate_long: {len(lengths)} lengths for {len(files)} files")
+    if seeds is not None and len(seeds) != len(files):
+        raise ValueError(f"bwe_lowrate_long: {len(seeds)} seeds for {len(files)} files")
+    groups = {}
+    for i, x in enumerate(files):
+        n = None if lengths is None or lengths[i] is None else int(lengths[i])
+        groups.setdefault((x.numel(), n), []).append(i)
+    out: List[Optional[torch.Tensor]] = [None] * len(files)
+    for (_, n), idx in groups.items():
+        y = torch.stack([files[i].reshape(-1).float() for i in idx]).to(device)
+        res = sampler.predict_bwe_lowrate_long(y, factor, filt_type, length=n, max_batch=max_batch, seeds=None if seeds is None else [int(seeds[i]) for i in idx])
+        for k, i in enumerate(idx):
+            out[i] = res[k]
+    return out
+
+
 # ---- waveform pre-/post-processing of the tester --------------------------------------------------------------------------------
 # (torchaudio's default resampling kernel: one builder and one table cache, in degrade.py, serve this module and degrade.SincResample)
 from .degrade import sinc_kernel as _sinc_kernel  # noqa: E402

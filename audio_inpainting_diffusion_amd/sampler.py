@@ -536,7 +536,8 @@ class Sampler:
         predict_inpainting_long, with every window a job and the ownership trimmed by K - 1 samples (more than one window needs
         end = int(overlap * L) >= 2 (K - 1)).  Each chunk of at most ``max_batch`` windows is one predict_resample through bwe_long.FIRObserved,
         which uses a filtered sample as an observation only where the window holds its whole filter support and takes the overlaps its
-        neighbours restored as known.  tester.data_consistency off / "end" / "always" mean what they mean for predict_bwe."""
+        neighbours restored as known.  tester.data_consistency off / "end" / "always" mean what they mean for predict_bwe.  A recording that
+        exists only at a low sample rate ("decimate", "resample") goes through predict_bwe_lowrate_long, whose grid is aligned to the input period."""
         from . import bwe_long
         if self.rid:
             raise _lib.AidError("predict_bwe_long returns the restored recordings only: rid must be False")
@@ -545,6 +546,30 @@ class Sampler:
         bwe_long.check_bwe_args(y, filt, filt_type, L, end, max_batch, seeds)
         self._check_model()
         return bwe_long.bwe_passes(self, y, filt, filt_type, L, end, max_batch, seeds)
+
+    def predict_bwe_lowrate_long(self, y, factor, filt_type="resample", length=None, max_batch=8, seeds=None):
+        """Bandwidth-extend whole recordings that exist only at a low sample rate: y[R, M] on the GPU -> [R, N] at the high rate, N any length
+        (lowrate_long.py).  filt_type "resample": torchaudio's default resampler at degrade.bwe_resample_ratio(factor), as predict_bwe's
+        (2 -> 2:1, 1.47 -> 147:100); "decimate": every factor-th sample (an integer in [1, 16]; the reference's 0:-1:factor).  ``length`` is N; it
+        must be consistent with M, and defaults to the largest such N (resample: floor(M * orig / new); decimate: M * factor + 1).  The window
+        grid, the two batched passes and the seeds are those of predict_bwe_long with K = 2 * width + orig, after the overlap
+        end = int(overlap * L) is widened to end' = end + ((L - end) % orig): every window then starts at a multiple of the input period and
+        resamples to the recording's own low-rate samples (more than one window needs end' >= 2 (K - 1); 2 end' < L).  Each chunk of at most
+        ``max_batch`` windows is one predict_resample through lowrate_long.RateObserved, which observes [B, L + ceil(new * L / orig)] entries
+        per window: the overlaps its neighbours restored as known, and the low-rate samples whose whole kernel support the window holds.
+        Guidance only: an identity ratio, rid and tester.data_consistency in use are refused (the reference's y + x - A(x) is undefined for an
+        operator that changes the length)."""
+        from . import lowrate_long
+        if self.rid:
+            raise _lib.AidError("predict_bwe_lowrate_long returns the restored recordings only: rid must be False")
+        if self.data_consistency or self.data_consistency_end:
+            raise _lib.AidError("predict_bwe_lowrate_long runs without data consistency (y + x - A(x) is undefined for an operator that changes "
+                                "the length): set tester.data_consistency.use = False")
+        L = int(self.args.exp.audio_len)
+        end = int(autoregressive_overlap(self.args) * L)
+        lowrate_long.check_lowrate_args(y, factor, filt_type, length, L, end, max_batch, seeds)
+        self._check_model()
+        return lowrate_long.lowrate_passes(self, y, factor, filt_type, L, end, length, max_batch, seeds)
 
     # ---- the remaining public methods of the reference class (its testers never call them; kept so that code written against
     # ---- testing.edm_sampler_inpainting.Sampler finds every name).  They run outside the sampling loop. ------------------------------

@@ -1,0 +1,328 @@
+"""CPU tests (no GPU) of bandwidth extension of whole low-sample-rate recordings (lowrate_long.py, include/aid_lowrate_long.h,
+Sampler.predict_bwe_lowrate_long, harness.bwe_lowrate_long): the C ABI and its ctypes mirror, the aligned window grid (every start a multiple
+of the input period; ownership tiles the recording), the exactness of the observed low-rate samples of a window in float64, the lengths, and
+the refusals, all raised before anything touches a GPU."""
+import ctypes
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import ROOT
+
+# (factor, filt_type) -> (orig, new): 2:1, 3:2, 147:100, decimation by 3 and by 4
+RATES = [(2, "resample", (2, 1)), (1.5, "resample", (3, 2)), (1.47, "resample", (147, 100)), (3, "decimate", (3, 1)), (4, "decimate", (4, 1))]
+GRIDS = [(4096, 1024), (1000, 250)]
+LENGTHS = [9557, 9217, 2999]                                                  # (9217 - 1) % 3 == 0 == (9217 - 1) % 4
+
+
+def _refused(ratio, L):
+    return ratio == (147, 100) and L == 1000                                  # end' = 265 < 2 (K - 1) = 328
+
+
+LOWRATE_CASES = [(f, t, ratio, L, end, N) for f, t, ratio in RATES for L, end in GRIDS for N in LENGTHS if not _refused(ratio, L)]
+
+
+# ---- C ABI ---------------------------------------------------------------------------------------------------------------------------
+def test_lowrate_long_header_compiles_as_c_and_struct_sizes_match_the_binding(tmp_path):
+    from audio_inpainting_diffusion_amd import _lib
+    gcc = shutil.which("gcc")
+    if gcc is None:
+        pytest.skip("no gcc")
+    pairs = {"aid_rate_observed_params": "RateObservedParams", "aid_lowrate_gather_params": "LowrateGatherParams"}
+    hdr = open(os.path.join(ROOT, "include", "aid_lowrate_long.h")).read()
+    assert set(re.findall(r"\}\s*(aid_\w+)\s*;", hdr)) == set(pairs)
+    assert int(re.search(r"#define AID_LOWRATE_LONG_ABI_VERSION (\d+)", hdr).group(1)) == _lib.AID_LOWRATE_LONG_ABI_VERSION == 1
+    fields = {"aid_rate_observed_params": ("out", "L", "out_ld", "B", "K"), "aid_lowrate_gather_params": ("jobs", "L", "out_ld", "J", "K")}
+    src = tmp_path / "sizes.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "aid_lowrate_long.h"\nint main(void) {\n' +
+                   "".join(f'    printf("{c} %zu\\n", sizeof({c}));\n' for c in pairs) +
+                   "".join(f'    printf("{c}.{f} %zu\\n", offsetof({c}, {f}));\n' for c, fs in fields.items() for f in fs) + "    return 0;\n}\n")
+    exe = tmp_path / "sizes"
+    subprocess.check_call([gcc, "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    out = dict(line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())
+    for c, py in pairs.items():
+        assert int(out[c]) == ctypes.sizeof(getattr(_lib, py)), (c, out[c], ctypes.sizeof(getattr(_lib, py)))
+        for f in fields[c]:
+            assert int(out[f"{c}.{f}"]) == getattr(getattr(_lib, py), f).offset, (c, f)
+
+
+def test_lowrate_long_exports_every_declared_symbol_and_shares_none():
+    from audio_inpainting_diffusion_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "aid_lowrate_long.h")).read()
+    declared = set(re.findall(r"^\s*(?:int|void)\s+(aid_\w+)\s*\(", hdr, flags=re.M))
+    assert declared == set(_lib.LOWRATE_LONG_EXPORTS) == {"aid_lowrate_long_abi_version", "aid_rate_observed", "aid_lowrate_gather"}
+    assert not declared & (set(_lib.EXPORTS) | set(_lib.DEGRADE_EXPORTS) | set(_lib.PHASE_EXPORTS) | set(_lib.AR_EXPORTS) | set(_lib.RESTORE_EXPORTS)
+                           | set(_lib.DECLIP_EXPORTS) | set(_lib.RESAMPLE_OP_EXPORTS) | set(_lib.BWE_LONG_EXPORTS))
+    so = os.path.join(ROOT, "audio_inpainting_diffusion_amd", "libaid_hip.so")
+    if not os.path.exists(so):
+        import build
+        build.build()
+    lib = ctypes.CDLL(so)
+    for name in declared:
+        assert hasattr(lib, name), f"{name} declared in aid_lowrate_long.h but not exported"
+    assert _lib.lib().aid_lowrate_long_abi_version() == _lib.AID_LOWRATE_LONG_ABI_VERSION
+    assert _lib.lib().aid_abi_version() == 14 and _lib.lib().aid_bwe_long_abi_version() == 1
+
+
+# ---- the grid ------------------------------------------------------------------------------------------------------------------------
+def test_rates_are_those_of_predict_bwe():
+    from audio_inpainting_diffusion_amd import degrade
+    from audio_inpainting_diffusion_amd.lowrate_long import Rate, rate_of, rate_tables
+    for factor, ftype, (o, n) in RATES:
+        rate = rate_of(factor, ftype)
+        assert (rate.orig, rate.new) == (o, n) and rate.K == 2 * rate.width + o and rate.decimate == (ftype == "decimate")
+        if ftype == "resample":
+            assert rate.width == degrade.sinc_kernel(o, n)[1] > 0
+        else:
+            assert rate.width == 0
+            k, width, kT, j_lo, j_hi = rate_tables(rate, "cpu")
+            assert width == 0 and k.tolist() == [[1.0] + [0.0] * (o - 1)] and kT.tolist() == [[1.0]] + [[0.0]] * (o - 1)
+            assert j_lo.tolist() == [0] * o and j_hi.tolist() == [1] + [0] * (o - 1) and j_lo.dtype == j_hi.dtype == torch.int32
+    assert rate_of(2, "resample") == Rate(2, 1, 13, 28) and rate_of(1.47, "resample") == Rate(147, 100, 9, 165)
+
+
+@pytest.mark.parametrize("factor,ftype,ratio,L,end,N", LOWRATE_CASES)
+def test_window_starts_are_multiples_of_the_input_period_and_owned_ranges_tile_the_recording(factor, ftype, ratio, L, end, N):
+    from audio_inpainting_diffusion_amd.bwe_long import bwe_windows
+    from audio_inpainting_diffusion_amd.lowrate_long import aligned_end, low_len, lowrate_plan, lowrate_windows, rate_of, window_len, window_state
+    rate = rate_of(factor, ftype)
+    o = rate.orig
+    end2 = aligned_end(L, end, o)
+    assert end2 == end + ((L - end) % o) and end <= end2 < end + o and (L - end2) % o == 0
+    step, m, M = L - end2, rate.K - 1, low_len(N, rate)
+    wins = lowrate_windows(N, L, end, rate)
+    assert wins == bwe_windows(N, L, end2, rate.K) and (len(wins) > 1) == (N > L)
+    assert [w[0] for w in wins] == [w * step for w in range(len(wins))] and all(w[0] % o == 0 for w in wins)
+    count = np.zeros(N, dtype=np.int64)
+    Mw = window_len(L, rate)
+    assert Mw == -(-rate.new * L // o)
+    for w, (s, head, tail, lo, hi) in enumerate(wins):
+        assert 0 <= lo < hi <= min(L, N - s), (w, lo, hi)
+        count[s + lo:s + hi] += 1
+        if w % 2 == 0:
+            assert (head, tail) == (0, 0)
+        else:
+            assert head == end2 - m and tail == (0 if w == len(wins) - 1 else end2 - m)
+        k = window_state(N, M, L, rate, s, head, tail)
+        assert k.dtype == np.float32 and k.shape == (L + Mw,)
+        kh, kl = k[:L], k[L:]
+        assert set(np.unique(kh)) <= {-2.0, -1.0, 1.0} and set(np.unique(kl)) <= {-2.0, -1.0, 0.0}
+        assert bool((kh[N - s:] == -2).all()) and bool((kh[:min(L, N - s)] != -2).all())
+        assert bool((kh[:head] == 1).all()) and bool((kh[L - tail:] == 1).all() if tail else True) and int((kh == 1).sum()) == head + tail
+        assert bool((kl == 0).any())
+        # an observed low-rate entry holds its whole kernel support in the window, or the recording ends there
+        n = np.arange(Mw)[kl == 0]
+        a0 = (n // rate.new) * o - rate.width
+        assert bool(((a0 >= 0) | (s == 0)).all()) and bool(((a0 + rate.K <= L) | (s + L >= N)).all())
+        assert bool(((s // o) * rate.new + n < M).all())
+    assert bool((count == 1).all())                                              # [0, N) exactly once
+    A, B = lowrate_plan(2, N, L, end, rate)
+    assert A == [(r,) + w for r in range(2) for w in wins[0::2]] and B == [(r,) + w for r in range(2) for w in wins[1::2]]
+
+
+def test_the_grid_refuses_an_aligned_overlap_below_twice_the_kernel_reach():
+    from audio_inpainting_diffusion_amd import _lib
+    from audio_inpainting_diffusion_amd.lowrate_long import aligned_end, lowrate_windows, rate_of
+    rate = rate_of(1.47, "resample")
+    assert aligned_end(1000, 250, 147) == 265 and 2 * (rate.K - 1) == 328
+    for N in LENGTHS:
+        with pytest.raises(_lib.AidError, match=r"end = 265 must be >= 2 \(K - 1\) = 328"):
+            lowrate_windows(N, 1000, 250, rate)
+    assert lowrate_windows(1000, 1000, 250, rate) == [(0, 0, 0, 0, 1000)]      # one window: any K
+    assert len(lowrate_windows(9557, 1000, 499, rate_of(3, "decimate"))) > 1     # end' = 499 + (501 % 3) = 499: 2 end' < L holds
+    with pytest.raises(_lib.AidError, match="end"):
+        lowrate_windows(9557, 1000, 499, rate_of(4, "decimate"))                # end' = 499 + (501 % 4) = 500: 2 end' = L
+
+
+# ---- the observed samples --------------------------------------------------------------------------------------------------------------
+def _table64(rate):
+    from audio_inpainting_diffusion_amd.degrade import sinc_kernel
+    if rate.decimate:
+        k = np.zeros((1, rate.K))
+        k[0, 0] = 1.0
+        return k
+    return sinc_kernel(rate.orig, rate.new)[0]
+
+
+def resample64(x, k, rate, n_out):
+    """float64 model of aid_resample_poly over x [n]: out[i*new + j] = sum_t k[j][t] x[i*orig + t - width], zeros outside, taps ascending"""
+    frames = -(-n_out // rate.new)
+    xp = np.concatenate([np.zeros(rate.width), x, np.zeros(frames * rate.orig + rate.K)])
+    acc = np.zeros((frames, rate.new))
+    for t in range(rate.K):
+        acc = acc + k[None, :, t] * xp[t:t + frames * rate.orig:rate.orig][:, None]
+    return acc.reshape(-1)[:n_out]
+
+
+def rate_observed_host(x, k, rate, state, mode="apply"):
+    """float64 numpy model of RateObserved on one window: x [L] (apply) or [L + Mw] (adjoint), state [L + Mw]"""
+    L = state.size * rate.orig // (rate.orig + rate.new)
+    Mw = state.size - L
+    kh, kl = state[:L], state[L:]
+    if mode == "apply":
+        c = resample64(np.where(kh == -2, 0.0, x), k, rate, Mw)
+        return np.concatenate([np.where(kh == 1, x, 0.0), np.where(kl == 0, c, 0.0)])
+    gin = np.where(kl == 0, x[L:], 0.0)
+    a = np.zeros(L + rate.width + Mw * rate.orig + rate.K)
+    for n in range(Mw):
+        i, j = divmod(n, rate.new)
+        a[i * rate.orig:i * rate.orig + rate.K] += k[j] * gin[n]                # (index shifted by width)
+    a = a[rate.width:rate.width + L]
+    return np.where(kh == -2, 0.0, np.where(kh == 1, a + x[:L], a))
+
+
+@pytest.mark.parametrize("factor,ftype,ratio,L,end,N", LOWRATE_CASES)
+def test_every_observed_low_rate_entry_of_a_window_is_the_recordings_sample_exactly(factor, ftype, ratio, L, end, N):
+    """rec = the whole recording resampled (or decimated, 0:-1:f).  In every window, the operator applied to the true window equals rec wherever
+    the low-rate state is 0, with difference exactly 0.0 in float64: the same taps over the same samples in the same order."""
+    from audio_inpainting_diffusion_amd.lowrate_long import low_len, lowrate_windows, rate_of, window_state
+    rate = rate_of(factor, ftype)
+    rng = np.random.default_rng(N + L + rate.K)
+    x, k = rng.standard_normal(N), _table64(rate)
+    M = low_len(N, rate)
+    rec = x[0:-1:rate.orig] if rate.decimate else resample64(x, k, rate, M)
+    assert rec.shape == (M,)
+    seen = np.zeros(M, dtype=bool)
+    for w, (s, head, tail, lo, hi) in enumerate(lowrate_windows(N, L, end, rate)):
+        n_in = min(L, N - s)
+        xw = np.concatenate([x[s:s + n_in], rng.standard_normal(L - n_in)])      # (what stands at absent samples must not matter)
+        st = window_state(N, M, L, rate, s, head, tail)
+        got = rate_observed_host(xw, k, rate, st)
+        obs = st[L:] == 0
+        m0 = (s // rate.orig) * rate.new
+        idx = m0 + np.arange(st.size - L)[obs]
+        assert idx.size and idx.max() < M
+        assert float(np.abs(got[L:][obs] - rec[idx]).max()) == 0.0
+        assert bool((got[L:][~obs] == 0).all()) and bool((got[:L][st[:L] == 1] == xw[st[:L] == 1]).all()) and bool((got[:L][st[:L] != 1] == 0).all())
+        seen[idx] = True
+        if w == 0:                                                                # the adjoint of the host model is the transpose of its apply
+            g = rng.standard_normal(st.size)
+            lhs, rhs = float(np.dot(got, g)), float(np.dot(xw, rate_observed_host(g, k, rate, st, "adjoint")))
+            assert abs(lhs - rhs) <= 1e-12 * (np.abs(xw).sum() * np.abs(k).max() * np.abs(g).max() + 1)
+    assert bool(seen.all())                                                       # every low-rate sample of the recording is observed by a window
+
+
+# ---- lengths ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("factor,ftype,ratio", RATES)
+def test_the_default_length_is_the_largest_consistent_one_and_an_inconsistent_one_is_refused(factor, ftype, ratio):
+    from audio_inpainting_diffusion_amd import _lib
+    from audio_inpainting_diffusion_amd.lowrate_long import check_length, default_length, low_len, rate_of
+    rate = rate_of(factor, ftype)
+    o, n = ratio
+    for M in (1, 2, 7, 100, 1000, 6501):
+        N = default_length(M, rate)
+        assert N == (M * o + 1 if ftype == "decimate" else M * o // n)
+        assert low_len(N, rate) == M and low_len(N + 1, rate) == M + 1 and check_length(M, None, rate) == N
+        consistent = [q for q in range(max(1, N - 2 * o), N + 2) if low_len(q, rate) == M]
+        assert consistent and consistent[-1] == N and all(check_length(M, q, rate) == q for q in consistent)
+        for bad in (N + 1, consistent[0] - 1, 0, -5, N + 0.5):
+            if bad == consistent[0] - 1 and bad >= 1 and low_len(bad, rate) == M:
+                continue
+            with pytest.raises(_lib.AidError, match="not consistent") as e:
+                check_length(M, bad, rate)
+            assert str(e.value).count(". ") == 0
+    for N in LENGTHS:                                                              # the reference's forms
+        assert low_len(N, rate) == (len(range(0, N - 1, o)) if ftype == "decimate" else -(-n * N // o))
+
+
+# ---- refusals that need no GPU, the harness wrapper --------------------------------------------------------------------------------------
+def _stub_sampler(rid=False, overlap=0.25, dc=None):
+    from test_bwe_long_host import _Fused
+    from audio_inpainting_diffusion_amd.config import small_args
+    from audio_inpainting_diffusion_amd.edm import EDM
+    from audio_inpainting_diffusion_amd.sampler import Sampler
+    args = small_args(xi=0.25)
+    args.tester.autoregressive.overlap = overlap
+    args.tester.data_consistency.use = dc is not None
+    if dc is not None:
+        args.tester.data_consistency.type = dc
+    return Sampler(model=_Fused(), diff_params=EDM(args), args=args, rid=rid), int(args.exp.audio_len)
+
+
+def test_every_refusal_is_raised_before_any_launch(monkeypatch):
+    from audio_inpainting_diffusion_amd import _lib, lowrate_long
+    launched = []
+    monkeypatch.setattr(_lib, "call", lambda name, p: launched.append(name))
+    monkeypatch.setattr(lowrate_long, "lowrate_plan", lambda *a, **k: launched.append("plan"))
+    smp, L = _stub_sampler()
+    smp.seeds = [5]
+    end = L // 4
+    M = 3 * L // 2
+    y = torch.zeros(2, M)                                                    # (on the host: a valid call is refused for that, every other one for its own reason)
+    sentences = []
+
+    def refused(match, call, exc=_lib.AidError):
+        with pytest.raises(exc, match=match) as e:
+            call()
+        sentences.append(str(e.value))
+
+    refused("GPU only", lambda: smp.predict_bwe_lowrate_long(y, 2, max_batch=1, seeds=[1, 2]))
+    refused("GPU only", lambda: smp.predict_bwe_lowrate_long(y, 2, "resample", length=2 * M - 1))
+    refused("GPU only", lambda: smp.predict_bwe_lowrate_long(y, 3, "decimate"))
+    refused("GPU only", lambda: smp.predict_bwe_lowrate_long(y, 1.47))
+    refused("GPU only", lambda: lowrate_long.lowrate_passes(smp, y, 2, "resample", L, end))
+    for factor, ftype in ((1, "resample"), (1.0, "resample"), (1.005, "resample"), (1, "decimate")):
+        refused("identity", lambda: smp.predict_bwe_lowrate_long(y, factor, ftype))
+    for dc in ("always", "end"):
+        refused("data consistency", lambda: _stub_sampler(dc=dc)[0].predict_bwe_lowrate_long(y, 2))
+    refused("rid", lambda: _stub_sampler(rid=True)[0].predict_bwe_lowrate_long(y, 2))
+    for bad in (0, -1, 17, "two", None):
+        refused("factor", lambda: smp.predict_bwe_lowrate_long(y, bad))
+    for bad in (0, 17, 2.5, "three", None):
+        refused("factor", lambda: smp.predict_bwe_lowrate_long(y, bad, "decimate"))
+    for ftype in ("firwin", "cheby1", "butterworth"):
+        with pytest.raises(NotImplementedError):
+            smp.predict_bwe_lowrate_long(y, 2, ftype)
+    for bad in (2 * M + 1, 2 * M - 2, 0, -3):
+        refused("not consistent", lambda: smp.predict_bwe_lowrate_long(y, 2, length=bad))
+    refused("not consistent", lambda: smp.predict_bwe_lowrate_long(y, 3, "decimate", length=3 * M + 2))
+    for bad in ([1], [1, 2, 3]):
+        refused("seeds", lambda: smp.predict_bwe_lowrate_long(y, 2, seeds=bad))
+    for bad in (0, -2):
+        refused("max_batch", lambda: smp.predict_bwe_lowrate_long(y, 2, max_batch=bad))
+    for bad in (y.double(), y.half(), y.long(), y[0], y.numpy(), y[:, :0], y[:, ::2]):
+        refused("float32 low-rate recordings", lambda: smp.predict_bwe_lowrate_long(bad, 2))
+    for ov in (0.5, 0.75, 0.0):
+        refused("end", lambda: _stub_sampler(overlap=ov)[0].predict_bwe_lowrate_long(y, 2))
+    refused(r"2 \(K - 1\)", lambda: _stub_sampler(overlap=0.01)[0].predict_bwe_lowrate_long(y, 1.47))     # end' < 328, more than one window
+    refused("GPU only", lambda: _stub_sampler(overlap=0.01)[0].predict_bwe_lowrate_long(y[:, :100], 1.47))   # one window: any K (refused for the device alone)
+    # the device of y is judged last: a host y with any other fault is refused for that fault
+    refused("seeds", lambda: lowrate_long.check_lowrate_args(y, 2, "resample", None, L, end, 8, [1]))
+    refused("GPU only", lambda: lowrate_long.check_lowrate_args(y, 2, "resample", None, L, end, 8, [1, 2]))
+    assert all(s.count(". ") == 0 and not s.rstrip().endswith(".") for s in sentences), [s for s in sentences if s.count(". ")]    # one sentence each
+    assert launched == [] and smp.seeds == [5] and smp.y is None and smp.spectral is None and smp.n_evals == 0
+
+
+def test_bwe_lowrate_long_groups_equal_lengths_and_checks_its_arguments():
+    from audio_inpainting_diffusion_amd.harness import bwe_lowrate_long
+
+    class Rec:
+        def __init__(self):
+            self.calls = []
+
+        def predict_bwe_lowrate_long(self, y, factor, filt_type="resample", length=None, max_batch=8, seeds=None):
+            self.calls.append((tuple(y.shape), factor, filt_type, length, max_batch, seeds))
+            return torch.cat([y, y], dim=1) + 1
+
+    files = [torch.full((n,), float(k)) for k, n in enumerate((700, 300, 700, 301, 300, 700))]
+    rec = Rec()
+    out = bwe_lowrate_long(rec, files, 2, "resample", lengths=[1400, None, 1400, 602, None, 1399], seeds=[10, 11, 12, 13, 14, 15], max_batch=4, device="cpu")
+    assert [(c[0], c[3]) for c in rec.calls] == [((2, 700), 1400), ((2, 300), None), ((1, 301), 602), ((1, 700), 1399)]
+    assert all(c[4] == 4 and c[2] == "resample" and c[1] == 2 for c in rec.calls)
+    assert [c[5] for c in rec.calls] == [[10, 12], [11, 14], [13], [15]]
+    assert all(torch.equal(o, torch.cat([f, f]) + 1) for o, f in zip(out, files))        # in the order of the files
+    rec = Rec()
+    bwe_lowrate_long(rec, files, 3, "decimate", device="cpu")                           # default lengths, the global generator
+    assert [c[0] for c in rec.calls] == [(3, 700), (2, 300), (1, 301)] and all(c[2] == "decimate" and c[3] is None and c[5] is None for c in rec.calls)
+    rec = Rec()
+    bwe_lowrate_long(rec, files[:1], 1.47, device="cpu")
+    assert rec.calls[0][1:4] == (1.47, "resample", None)
+    with pytest.raises(ValueError):
+        bwe_lowrate_long(rec, files, 2, seeds=[1], device="cpu")
+    with pytest.raises(ValueError):
+        bwe_lowrate_long(rec, files, 2, lengths=[1400], device="cpu")
