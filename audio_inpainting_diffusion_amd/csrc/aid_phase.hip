@@ -8,13 +8,14 @@
 //                              for k <= N/2 and 0 above (the output is one-sided: no Hermitian mirror), unnormalised inverse
 //                              FFT, real part times window -> frame buffer [B, T, N].
 //   stft_mag_ola_kernel      : one lane per sample q < L gathers the frames covering it (no atomics -> deterministic).
+//   The bodies of the three are device functions in aid_stft_mag_tile.h, which aid_phase_long.hip instantiates with selects.
 //   Bins with |X_k| = 0 contribute 0.  The reference's autograd (sqrt of re^2 + im^2) gives 0 * inf = NaN there; in
 //   practice that only happens in the all-zero last frame when hop divides L, which covers the appended zeros only, so its
 //   NaN lands on the padding that torch.cat's backward drops and the reference's gradient w.r.t. x stays finite -- as here.
 //
 //   mnorm1_kernel / mnorm2_kernel: one 1024-lane workgroup per item, fp64 accumulation, see aid_phase.h.
 #include "aid_common.h"
-#include "aid_fft_lds.h"
+#include "aid_stft_mag_tile.h"
 #include "aid_phase.h"
 
 #define MN_THREADS 1024
@@ -24,68 +25,36 @@
 extern "C" int aid_phase_abi_version(void) { return AID_PHASE_ABI_VERSION; }
 
 // ---- STFT magnitude ------------------------------------------------------------------------------------------------
-// frame t of item b times the window, forward FFT; returns the LDS buffer that holds X
-__device__ float2* pm_frame_fft(const aid_stft_mag_params& p, float2* A, float2* Bf, int b, int t) {
-    const int N = p.n_fft;
-    const float* x = p.x + (int64_t)b * p.x_ld;
-    const int64_t s0 = (int64_t)t * p.hop;
-    for (int j = threadIdx.x; j < N; j += STFT_THREADS) {
-        const int64_t q = s0 + j;
-        const float v = q < p.L ? x[q] : 0.f;
-        A[j] = make_float2(v * p.window[j], 0.f);
-    }
-    __syncthreads();
-    return st_fft(A, Bf, N, reinterpret_cast<const float2*>(p.twiddle), -1.f);
-}
+// (the frame and overlap-add bodies live in aid_stft_mag_tile.h, shared with aid_stft_mag_observed; here without selects)
+struct pm_row {                                                    // sample q of the row, 0 at and past L
+    const float* __restrict__ x; int64_t L;
+    __device__ __forceinline__ float operator()(int64_t q) const { return q < L ? x[q] : 0.f; }
+};
+struct pm_all {
+    __device__ __forceinline__ bool operator()(int64_t) const { return true; }
+};
 
 __global__ __launch_bounds__(STFT_THREADS) void stft_mag_kernel(const aid_stft_mag_params p) {
     const int b = blockIdx.x / p.n_frames, t = blockIdx.x - b * p.n_frames;
     extern __shared__ __attribute__((aligned(16))) float2 pm_lds[];
-    const int N = p.n_fft, F = (N >> 1) + 1;
-    const float2* X = pm_frame_fft(p, pm_lds, pm_lds + N, b, t);
-    float* out = p.out + (int64_t)b * F * p.n_frames + t;
-    for (int k = threadIdx.x; k < F; k += STFT_THREADS) {
-        const float2 c = X[k];
-        out[(int64_t)k * p.n_frames] = sqrtf(c.x * c.x + c.y * c.y);
-    }
+    const int F = (p.n_fft >> 1) + 1;
+    pm_mag_frame(pm_row{p.x + (int64_t)b * p.x_ld, p.L}, (int64_t)t * p.hop, p.n_fft, p.window, p.twiddle, pm_lds,
+                 p.out + (int64_t)b * F * p.n_frames + t, p.n_frames);
 }
 
 __global__ __launch_bounds__(STFT_THREADS) void stft_mag_vjp_frames_kernel(const aid_stft_mag_params p) {
     const int b = blockIdx.x / p.n_frames, t = blockIdx.x - b * p.n_frames;
     extern __shared__ __attribute__((aligned(16))) float2 pm_lds[];
-    const int N = p.n_fft, half = N >> 1, F = half + 1;
-    float2* A = pm_lds;
-    float2* Bf = pm_lds + N;
-    float2* X = pm_frame_fft(p, A, Bf, b, t);
-    const float* g = p.g + (int64_t)b * F * p.n_frames + t;
-    for (int k = threadIdx.x; k < N; k += STFT_THREADS) {      // in place: lane-private k
-        float2 z = make_float2(0.f, 0.f);
-        if (k <= half) {
-            const float2 c = X[k];
-            const float m = sqrtf(c.x * c.x + c.y * c.y);
-            if (m > 0.f) {
-                const float s = g[(int64_t)k * p.n_frames] / m;
-                z = make_float2(c.x * s, c.y * s);
-            }
-        }
-        X[k] = z;
-    }
-    __syncthreads();
-    const float2* S = st_fft(X, X == A ? Bf : A, N, reinterpret_cast<const float2*>(p.twiddle), +1.f);
-    float* fr = p.frames + ((int64_t)b * p.n_frames + t) * N;
-    for (int j = threadIdx.x; j < N; j += STFT_THREADS) fr[j] = S[j].x * p.window[j];
+    const int N = p.n_fft, F = (N >> 1) + 1;
+    pm_vjp_frame(pm_row{p.x + (int64_t)b * p.x_ld, p.L}, (int64_t)t * p.hop, N, p.window, p.twiddle, pm_lds,
+                 p.g + (int64_t)b * F * p.n_frames + t, p.n_frames, p.frames + ((int64_t)b * p.n_frames + t) * N);
 }
 
 __global__ __launch_bounds__(256) void stft_mag_ola_kernel(const aid_stft_mag_params p) {
-    const int b = blockIdx.y, N = p.n_fft, hop = p.hop;
+    const int b = blockIdx.y, N = p.n_fft;
     const float* fr = p.frames + (int64_t)b * p.n_frames * N;
-    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < p.L; q += (int64_t)gridDim.x * 256) {
-        const int64_t t1 = q / hop;                                      // < n_frames because q < L
-        const int64_t t0 = q < N ? 0 : (q - (N - 1) + hop - 1) / hop;
-        float acc = 0.f;
-        for (int64_t t = t0; t <= t1; ++t) acc += fr[t * N + (q - t * hop)];
-        p.out[(int64_t)b * p.out_ld + q] = acc;
-    }
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < p.L; q += (int64_t)gridDim.x * 256)
+        p.out[(int64_t)b * p.out_ld + q] = pm_ola(pm_all{}, fr, q, N, p.hop);
 }
 
 extern "C" int aid_stft_mag(const aid_stft_mag_params* p, void* stream) {

@@ -236,6 +236,32 @@ def bwe_lowrate_long(sampler, files: Sequence[torch.Tensor], factor, filt_type: 
     return out
 
 
+def pr_long(sampler, spectrograms: Sequence[torch.Tensor], lengths: Optional[Sequence[Optional[int]]] = None, seeds: Optional[Sequence[int]] = None,
+            max_batch: int = 8, device="cuda") -> List[torch.Tensor]:
+    """Retrieve the phase of every 2-D magnitude spectrogram [F, T_rec] of ``spectrograms`` (any numbers of frames) and return the waveforms on
+    ``device``, in the order of ``spectrograms``.  ``lengths``: the number of samples per file (None, for all files or for one: the largest
+    consistent with the file's frames).  Files of equal (T_rec, length) go through ONE Sampler.predict_pr_long call, so their windows share the
+    two batched passes; every other pair is a call of its own.  ``seeds``: one RNG seed per file (file i's result then depends on seeds[i] alone,
+    not on the grouping)."""
+    if lengths is not None and len(lengths) != len(spectrograms):
+        raise ValueError(f"pr_long: {len(lengths)} lengths for {len(spectrograms)} files")
+    if seeds is not None and len(seeds) != len(spectrograms):
+        raise ValueError(f"pr_long: {len(seeds)} seeds for {len(spectrograms)} files")
+    groups = {}
+    for i, x in enumerate(spectrograms):
+        if x.dim() != 2:
+            raise ValueError(f"pr_long: file {i} must be a magnitude spectrogram [F, T_rec], got {tuple(x.shape)}")
+        n = None if lengths is None or lengths[i] is None else int(lengths[i])
+        groups.setdefault((tuple(x.shape), n), []).append(i)
+    out: List[Optional[torch.Tensor]] = [None] * len(spectrograms)
+    for (_, n), idx in groups.items():
+        y = torch.stack([spectrograms[i].float() for i in idx]).to(device)
+        res = sampler.predict_pr_long(y, length=n, max_batch=max_batch, seeds=None if seeds is None else [int(seeds[i]) for i in idx])
+        for k, i in enumerate(idx):
+            out[i] = res[k]
+    return out
+
+
 # ---- waveform pre-/post-processing of the tester --------------------------------------------------------------------------------
 # (torchaudio's default resampling kernel: one builder and one table cache, in degrade.py, serve this module and degrade.SincResample)
 from .degrade import sinc_kernel as _sinc_kernel  # noqa: E402

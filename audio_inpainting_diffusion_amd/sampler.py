@@ -571,6 +571,35 @@ class Sampler:
         self._check_model()
         return lowrate_long.lowrate_passes(self, y, factor, filt_type, L, end, length, max_batch, seeds)
 
+    def predict_pr_long(self, y, length=None, max_batch=8, seeds=None):
+        """Retrieve the phase of whole recordings known only by their STFT magnitude: y[R, F, T_rec] on the GPU (|STFT| as predict_pr takes it:
+        win_size zeros appended, periodic Hamming window, center=False; F = win_size / 2 + 1, T_rec = 1 + N // hop_size) -> [R, N], N any length
+        (phase_long.py).  win_size / hop_size as for predict_pr (phase_retrieval_sizes).  ``length`` is N; it must be consistent with T_rec, and
+        defaults to the largest such N (T_rec * hop_size - 1).  The window grid, the two batched passes and the seeds are those of
+        predict_inpainting_long with the ownership trimmed by win_size - 1, after the overlap end = int(overlap * L) is widened to
+        end' = end + ((L - end) % hop_size): every window then starts on the hop grid and its frames are the recording's own (more than one window
+        needs end' >= 2 (win_size - 1); 2 end' < L).  Each chunk of at most ``max_batch`` windows is one predict_resample through
+        phase_long.STFTMagObserved, which observes [B, L + F * (1 + L // hop_size)] entries per window: the overlaps its neighbours restored as
+        known, and the magnitude columns of the frames that lie inside the window (or over the end of the recording).
+        THE NORM DIFFERS FROM predict_pr: the operator declares no matrix_obs, so tester.posterior_sampling.norm = 2 / 1 is the element-wise norm
+        over the whole observation row, not the induced matrix norm of one segment's spectrogram that the reference's dim=(1, 2) gives predict_pr --
+        an induced matrix norm has no meaning across windows, and known samples do not fit in the matrix.
+        Guidance only: xi <= 0, rid and tester.data_consistency in use are refused."""
+        from . import phase_long
+        if self.rid:
+            raise _lib.AidError("predict_pr_long returns the restored recordings only: rid must be False")
+        if not self.xi > 0:
+            raise _lib.AidError("predict_pr_long needs reconstruction guidance: tester.posterior_sampling.xi must be > 0 (the reference asserts xi > 0)")
+        if self.data_consistency or self.data_consistency_end:
+            raise _lib.AidError("predict_pr_long runs without data consistency (no data-consistency step exists for phase retrieval): "
+                                "set tester.data_consistency.use = False")
+        win, hop = phase_retrieval_sizes(self.args)
+        L = int(self.args.exp.audio_len)
+        end = int(autoregressive_overlap(self.args) * L)
+        phase_long.check_pr_args(y, win, hop, length, L, end, max_batch, seeds)
+        self._check_model()
+        return phase_long.pr_passes(self, y, win, hop, L, end, length, max_batch, seeds)
+
     # ---- the remaining public methods of the reference class (its testers never call them; kept so that code written against
     # ---- testing.edm_sampler_inpainting.Sampler finds every name).  They run outside the sampling loop. ------------------------------
     def apply_mask(self, x, mask=None):
