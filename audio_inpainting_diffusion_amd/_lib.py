@@ -1,4 +1,4 @@
-"""ctypes binding of libaid_hip.so (the C ABI in include/aid_kernels.h, include/aid_degrade.h, include/aid_phase.h, include/aid_autoregressive.h, include/aid_restore.h, include/aid_declip.h, include/aid_resample_op.h, include/aid_bwe_long.h, include/aid_lowrate_long.h and include/aid_phase_long.h).
+"""ctypes binding of libaid_hip.so (the C ABI in include/aid_kernels.h, include/aid_degrade.h, include/aid_phase.h, include/aid_autoregressive.h, include/aid_restore.h, include/aid_declip.h, include/aid_resample_op.h, include/aid_bwe_long.h, include/aid_lowrate_long.h, include/aid_phase_long.h and include/aid_spec_long.h).
 
 There is deliberately NO fallback: if the shared library is missing or a launcher returns an error code,
 ``AidError`` is raised.  Tensors are passed as raw device pointers + element strides; the stream is torch's
@@ -390,6 +390,26 @@ class PrGatherParams(C.Structure):
 AID_PHASE_LONG_ABI_VERSION = 1
 PHASE_LONG_EXPORTS = ["aid_phase_long_abi_version", "aid_stft_mag_observed", "aid_pr_gather"]
 
+# ---- include/aid_spec_long.h (spectrogram inpainting of whole recordings: the known / observed / unobserved / absent STFT-masking operator and its gather; a header and export list of their own) ----
+class StftMaskObservedParams(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("state", C.c_void_p), ("items", C.c_void_p),
+                ("window", C.c_void_p), ("twiddle", C.c_void_p), ("inv_env", C.c_void_p), ("mask", C.c_void_p),
+                ("frames", C.c_void_p), ("out", C.c_void_p),
+                ("L", C.c_int64), ("Np", C.c_int64), ("x_ld", C.c_int64), ("y_ld", C.c_int64), ("state_ld", C.c_int64), ("out_ld", C.c_int64),
+                ("mask_sB", C.c_int64), ("mask_ld", C.c_int64),
+                ("B", C.c_int), ("Rm", C.c_int), ("n_fft", C.c_int), ("hop", C.c_int), ("n_frames", C.c_int), ("mode", C.c_int)]
+
+
+class SpecGatherParams(C.Structure):
+    _fields_ = [("rec", C.c_void_p), ("out", C.c_void_p), ("y", C.c_void_p), ("state", C.c_void_p), ("items", C.c_void_p), ("jobs", C.c_void_p),
+                ("L", C.c_int64), ("N", C.c_int64), ("Np", C.c_int64), ("rec_ld", C.c_int64), ("out_ld", C.c_int64),
+                ("J", C.c_int), ("R", C.c_int), ("n_fft", C.c_int), ("hop", C.c_int), ("n_frames", C.c_int)]
+
+
+AID_SPEC_LONG_ABI_VERSION = 1
+AID_SPEC_ITEM_FIELDS = 3
+SPEC_LONG_EXPORTS = ["aid_spec_long_abi_version", "aid_stft_mask_observed", "aid_spec_gather"]
+
 EXPORTS = ["aid_abi_version", "aid_last_error", "aid_last_kernel", "aid_group_stats", "aid_conv2d", "aid_conv2d_pack_dims", "aid_conv2d_stat_partials", "aid_pack_conv_weight", "aid_wino_gy", "aid_conv2d_wgrad_tiles", "aid_resample",
            "aid_time_attention", "aid_embed", "aid_modulation", "aid_cqt_analysis", "aid_cqt_synthesis",
            "aid_cqt_gather", "aid_axpby", "aid_score_step", "aid_add2", "aid_group_dot", "aid_norm_bwd",
@@ -528,6 +548,14 @@ def lib():
         L.aid_phase_long_abi_version.argtypes = []
         if L.aid_phase_long_abi_version() != AID_PHASE_LONG_ABI_VERSION:
             raise AidError("include/aid_phase_long.h ABI version mismatch")
+        for name in SPEC_LONG_EXPORTS:
+            if not hasattr(L, name):
+                raise AidError(f"libaid_hip.so does not export {name}")
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
+            getattr(L, name).restype = C.c_int
+        L.aid_spec_long_abi_version.argtypes = []
+        if L.aid_spec_long_abi_version() != AID_SPEC_LONG_ABI_VERSION:
+            raise AidError("include/aid_spec_long.h ABI version mismatch")
         _lib = L
     return _lib
 

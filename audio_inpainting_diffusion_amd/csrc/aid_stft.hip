@@ -14,18 +14,16 @@
 //            deterministic); forward: times 1/envelope, optional `c0*A(x) + add1 + add2` epilogue (the
 //            projection y + x - A(x) of :360); adjoint: folds the reflected borders back.
 // HBM-trivial (a few [B,L] arrays and one [B, 4L] frame buffer per call).
-#include "aid_common.h"
-#include "aid_fft_lds.h"
+#include "aid_stft_tile.h"
 
+// (the frame and overlap-add bodies are device functions in aid_stft_tile.h, which aid_spec_long.hip instantiates with selects)
 __global__ __launch_bounds__(STFT_THREADS) void stft_frames_kernel(const aid_stft_params p) {
     const int b = blockIdx.x / p.n_frames, n = blockIdx.x - b * p.n_frames;
     const int N = p.n_fft, half = N >> 1;
     extern __shared__ __attribute__((aligned(16))) float2 st_lds[];
-    float2* A = st_lds;
-    float2* Bf = st_lds + N;
     const float* x = p.x + (int64_t)b * p.L;
     const int64_t start = (int64_t)n * p.hop - half;
-    for (int j = threadIdx.x; j < N; j += STFT_THREADS) {
+    auto load = [&](int j) {
         int64_t q = start + j;
         float v = 0.f;
         bool in = true;
@@ -39,47 +37,23 @@ __global__ __launch_bounds__(STFT_THREADS) void stft_frames_kernel(const aid_stf
             v = x[q];
             if (p.adjoint) v *= p.inv_env[q];
         }
-        A[j] = make_float2(v * p.window[j], 0.f);
-    }
-    __syncthreads();
-    const float2* tw = reinterpret_cast<const float2*>(p.twiddle);
-    float2* R = st_fft(A, Bf, N, tw, -1.f);
-    const float* m = p.mask + (int64_t)b * p.mask_sB + n;
-    for (int f = threadIdx.x; f < N; f += STFT_THREADS) {
-        const int fm = f <= half ? f : N - f;
-        const float mv = m[(int64_t)fm * p.mask_ld];
-        R[f].x *= mv;
-        R[f].y *= mv;
-    }
-    __syncthreads();
-    float2* S = st_fft(R, R == A ? Bf : A, N, tw, +1.f);
-    float* fr = p.frames + ((int64_t)b * p.n_frames + n) * N;
-    const float inv = 1.0f / (float)N;
-    for (int j = threadIdx.x; j < N; j += STFT_THREADS) fr[j] = S[j].x * p.window[j] * inv;
-}
-
-// sum of the frames covering centred position q = pos + n_fft/2
-__device__ __forceinline__ float st_cover(const float* __restrict__ fr, int64_t pos, int N, int hop, int n_frames) {
-    const int64_t q = pos + (N >> 1);
-    int64_t n1 = q / hop;
-    int64_t n0 = (q - (N - 1) + hop - 1) / hop;
-    if (q - (N - 1) < 0) n0 = 0;
-    if (n1 > n_frames - 1) n1 = n_frames - 1;
-    float acc = 0.f;
-    for (int64_t n = n0; n <= n1; ++n) acc += fr[n * N + (q - n * hop)];
-    return acc;
+        return v;
+    };
+    st_mask_frame(load, N, p.window, p.twiddle, p.mask + (int64_t)b * p.mask_sB + n, p.mask_ld, st_lds, st_lds + N,
+                  p.frames + ((int64_t)b * p.n_frames + n) * N);
 }
 
 __global__ __launch_bounds__(256) void stft_ola_kernel(const aid_stft_params p) {
     const int b = blockIdx.y;
     const float* fr = p.frames + (int64_t)b * p.n_frames * p.n_fft;
     const int N = p.n_fft, half = N >> 1;
+    const int64_t T = p.n_frames;
     for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < p.L; t += (int64_t)gridDim.x * 256) {
-        float v = st_cover(fr, t, N, p.hop, p.n_frames);
+        float v = st_cover(st_all{}, fr, t, N, p.hop, T, 0, T);
         if (p.adjoint) {
-            if (t >= 1 && t <= half) v += st_cover(fr, -t, N, p.hop, p.n_frames);              // left reflection
+            if (t >= 1 && t <= half) v += st_cover(st_all{}, fr, -t, N, p.hop, T, 0, T);        // left reflection
             const int64_t r = 2 * (p.Lp - 1) - t;
-            if (r >= p.Lp && r < p.Lp + half) v += st_cover(fr, r, N, p.hop, p.n_frames);       // right reflection
+            if (r >= p.Lp && r < p.Lp + half) v += st_cover(st_all{}, fr, r, N, p.hop, T, 0, T); // right reflection
         } else {
             v *= p.inv_env[t];
         }

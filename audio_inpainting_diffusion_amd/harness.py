@@ -262,6 +262,32 @@ def pr_long(sampler, spectrograms: Sequence[torch.Tensor], lengths: Optional[Seq
     return out
 
 
+def spectrogram_inpainting_long(sampler, files: Sequence[torch.Tensor], masks: Sequence[torch.Tensor], seeds: Optional[Sequence[int]] = None,
+                                max_batch: int = 8, device="cuda") -> List[torch.Tensor]:
+    """Restore every waveform of ``files`` (any lengths; each masked as a whole in the STFT domain) under its mask [F, T_rec] of ``masks``
+    (masks.spectral_mask(audio_len=len(file), ...)) and return the waveforms on ``device``, in the order of ``files``.  Files of equal length
+    go through ONE Sampler.predict_spectrogram_inpainting_long call, so their windows share the two batched passes; every other length is a
+    call of its own.  ``seeds``: one RNG seed per file (file i's result then depends on seeds[i] alone, not on the grouping)."""
+    if len(masks) != len(files):
+        raise ValueError(f"spectrogram_inpainting_long: {len(masks)} masks for {len(files)} files")
+    if seeds is not None and len(seeds) != len(files):
+        raise ValueError(f"spectrogram_inpainting_long: {len(seeds)} seeds for {len(files)} files")
+    for i, m in enumerate(masks):
+        if m.dim() != 2:
+            raise ValueError(f"spectrogram_inpainting_long: mask {i} must be [F, T_rec], got {tuple(m.shape)}")
+    groups = {}
+    for i, x in enumerate(files):
+        groups.setdefault((x.numel(), tuple(masks[i].shape)), []).append(i)
+    out: List[Optional[torch.Tensor]] = [None] * len(files)
+    for idx in groups.values():
+        y = torch.stack([files[i].reshape(-1).float() for i in idx]).to(device)
+        m = torch.stack([masks[i].float() for i in idx]).to(device)
+        res = sampler.predict_spectrogram_inpainting_long(y, m, max_batch=max_batch, seeds=None if seeds is None else [int(seeds[i]) for i in idx])
+        for k, i in enumerate(idx):
+            out[i] = res[k]
+    return out
+
+
 # ---- waveform pre-/post-processing of the tester --------------------------------------------------------------------------------
 # (torchaudio's default resampling kernel: one builder and one table cache, in degrade.py, serve this module and degrade.SincResample)
 from .degrade import sinc_kernel as _sinc_kernel  # noqa: E402

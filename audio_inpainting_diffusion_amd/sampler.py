@@ -600,6 +600,28 @@ class Sampler:
         self._check_model()
         return phase_long.pr_passes(self, y, win, hop, L, end, length, max_batch, seeds)
 
+    def predict_spectrogram_inpainting_long(self, y, mask, max_batch=8, seeds=None):
+        """Restore whole recordings whose spectrogram was masked: y[R, N] on the GPU -- N any length, y = the reference's apply_spectral_mask of
+        the whole recording -- and mask[F, T_rec] or [R, F, T_rec] over the STFT of tester.spectrogram_inpainting.stft (F = n_fft / 2 + 1,
+        T_rec = 1 + Np // hop_length, Np = N + (n_fft - N % n_fft): masks.spectral_mask(audio_len=N, ...)) -> [R, N] (spec_long.py).  The window
+        grid, the two batched passes and the seeds are those of predict_inpainting_long with the ownership trimmed by 2 (n_fft - 1), after the
+        overlap end = int(overlap * L) is widened to end' = end + ((L - end) % hop_length): every window then starts on the hop grid and its
+        frames are the recording's own (more than one window needs end' >= 4 (n_fft - 1); 2 end' < L).  A window is a job when its owned range
+        holds a sample under a frame with a masked bin; the others cost nothing and keep the recording's samples.  Each chunk of at most
+        ``max_batch`` windows is one predict_resample through spec_long.SpectralMaskObserved, which uses a sample of y as an observation only
+        where the window can compute every frame that covers it, and takes the overlaps its neighbours restored as known.
+        tester.data_consistency off / "end" / "always" mean what they mean for predict_spectrogram_inpainting.  A window other than "hann", a
+        hop_length that does not divide n_fft and rid are refused."""
+        from . import spec_long
+        if self.rid:
+            raise _lib.AidError("predict_spectrogram_inpainting_long returns the restored recordings only: rid must be False")
+        st = self.args.tester.spectrogram_inpainting.stft
+        L = int(self.args.exp.audio_len)
+        end = int(autoregressive_overlap(self.args) * L)
+        spec_long.check_spec_args(y, mask, st.n_fft, st.hop_length, st.win_length, st.window, L, end, max_batch, seeds)
+        self._check_model()
+        return spec_long.spec_passes(self, y, mask, st.n_fft, st.hop_length, L, end, st.win_length, st.window, max_batch, seeds)
+
     # ---- the remaining public methods of the reference class (its testers never call them; kept so that code written against
     # ---- testing.edm_sampler_inpainting.Sampler finds every name).  They run outside the sampling loop. ------------------------------
     def apply_mask(self, x, mask=None):
