@@ -418,6 +418,18 @@ EXPORTS = ["aid_abi_version", "aid_last_error", "aid_last_kernel", "aid_group_st
            "aid_conv2d_wgrad", "aid_wgrad_reduce", "aid_channel_dot", "aid_relpos_bwd", "aid_scale_bwd", "aid_modulation_bwd", "aid_embed_bwd",
            "aid_adam", "aid_ema", "aid_sumsq", "aid_wino2d_gemm", "aid_wino2d_set_split", "aid_conv2d_wino2d_gemm", "aid_conv2d_wino2d_output", "aid_conv2d_wino2d_supported", "aid_conv2d_wino2d_positions", "aid_conv2d_wino2d_wanted", "aid_conv2d_wino2d_tform"]
 
+# the sub-ABIs, each with a header and a version of its own: (exports, version symbol, version, header under include/)
+SUB_ABIS = [(DEGRADE_EXPORTS, "aid_degrade_abi_version", AID_DEGRADE_ABI_VERSION, "aid_degrade.h"),
+            (PHASE_EXPORTS, "aid_phase_abi_version", AID_PHASE_ABI_VERSION, "aid_phase.h"),
+            (AR_EXPORTS, "aid_ar_abi_version", AID_AR_ABI_VERSION, "aid_autoregressive.h"),
+            (RESTORE_EXPORTS, "aid_restore_abi_version", AID_RESTORE_ABI_VERSION, "aid_restore.h"),
+            (DECLIP_EXPORTS, "aid_declip_abi_version", AID_DECLIP_ABI_VERSION, "aid_declip.h"),
+            (RESAMPLE_OP_EXPORTS, "aid_resample_op_abi_version", AID_RESAMPLE_OP_ABI_VERSION, "aid_resample_op.h"),
+            (BWE_LONG_EXPORTS, "aid_bwe_long_abi_version", AID_BWE_LONG_ABI_VERSION, "aid_bwe_long.h"),
+            (LOWRATE_LONG_EXPORTS, "aid_lowrate_long_abi_version", AID_LOWRATE_LONG_ABI_VERSION, "aid_lowrate_long.h"),
+            (PHASE_LONG_EXPORTS, "aid_phase_long_abi_version", AID_PHASE_LONG_ABI_VERSION, "aid_phase_long.h"),
+            (SPEC_LONG_EXPORTS, "aid_spec_long_abi_version", AID_SPEC_LONG_ABI_VERSION, "aid_spec_long.h")]
+
 _lib = None
 
 
@@ -476,86 +488,15 @@ def lib():
                 getattr(L, name).restype = C.c_int
         if L.aid_abi_version() != 14:
             raise AidError("ABI version mismatch")
-        for name in DEGRADE_EXPORTS:
-            if not hasattr(L, name):
-                raise AidError(f"libaid_hip.so does not export {name}")
-            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
-            getattr(L, name).restype = C.c_int
-        L.aid_degrade_abi_version.argtypes = []
-        if L.aid_degrade_abi_version() != AID_DEGRADE_ABI_VERSION:
-            raise AidError("include/aid_degrade.h ABI version mismatch")
-        for name in PHASE_EXPORTS:
-            if not hasattr(L, name):
-                raise AidError(f"libaid_hip.so does not export {name}")
-            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
-            getattr(L, name).restype = C.c_int
-        L.aid_phase_abi_version.argtypes = []
-        if L.aid_phase_abi_version() != AID_PHASE_ABI_VERSION:
-            raise AidError("include/aid_phase.h ABI version mismatch")
-        for name in AR_EXPORTS:
-            if not hasattr(L, name):
-                raise AidError(f"libaid_hip.so does not export {name}")
-            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
-            getattr(L, name).restype = C.c_int
-        L.aid_ar_abi_version.argtypes = []
-        if L.aid_ar_abi_version() != AID_AR_ABI_VERSION:
-            raise AidError("include/aid_autoregressive.h ABI version mismatch")
-        for name in RESTORE_EXPORTS:
-            if not hasattr(L, name):
-                raise AidError(f"libaid_hip.so does not export {name}")
-            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
-            getattr(L, name).restype = C.c_int
-        L.aid_restore_abi_version.argtypes = []
-        if L.aid_restore_abi_version() != AID_RESTORE_ABI_VERSION:
-            raise AidError("include/aid_restore.h ABI version mismatch")
-        for name in DECLIP_EXPORTS:
-            if not hasattr(L, name):
-                raise AidError(f"libaid_hip.so does not export {name}")
-            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
-            getattr(L, name).restype = C.c_int
-        L.aid_declip_abi_version.argtypes = []
-        if L.aid_declip_abi_version() != AID_DECLIP_ABI_VERSION:
-            raise AidError("include/aid_declip.h ABI version mismatch")
-        for name in RESAMPLE_OP_EXPORTS:
-            if not hasattr(L, name):
-                raise AidError(f"libaid_hip.so does not export {name}")
-            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
-            getattr(L, name).restype = C.c_int
-        L.aid_resample_op_abi_version.argtypes = []
-        if L.aid_resample_op_abi_version() != AID_RESAMPLE_OP_ABI_VERSION:
-            raise AidError("include/aid_resample_op.h ABI version mismatch")
-        for name in BWE_LONG_EXPORTS:
-            if not hasattr(L, name):
-                raise AidError(f"libaid_hip.so does not export {name}")
-            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
-            getattr(L, name).restype = C.c_int
-        L.aid_bwe_long_abi_version.argtypes = []
-        if L.aid_bwe_long_abi_version() != AID_BWE_LONG_ABI_VERSION:
-            raise AidError("include/aid_bwe_long.h ABI version mismatch")
-        for name in LOWRATE_LONG_EXPORTS:
-            if not hasattr(L, name):
-                raise AidError(f"libaid_hip.so does not export {name}")
-            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
-            getattr(L, name).restype = C.c_int
-        L.aid_lowrate_long_abi_version.argtypes = []
-        if L.aid_lowrate_long_abi_version() != AID_LOWRATE_LONG_ABI_VERSION:
-            raise AidError("include/aid_lowrate_long.h ABI version mismatch")
-        for name in PHASE_LONG_EXPORTS:
-            if not hasattr(L, name):
-                raise AidError(f"libaid_hip.so does not export {name}")
-            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
-            getattr(L, name).restype = C.c_int
-        L.aid_phase_long_abi_version.argtypes = []
-        if L.aid_phase_long_abi_version() != AID_PHASE_LONG_ABI_VERSION:
-            raise AidError("include/aid_phase_long.h ABI version mismatch")
-        for name in SPEC_LONG_EXPORTS:
-            if not hasattr(L, name):
-                raise AidError(f"libaid_hip.so does not export {name}")
-            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
-            getattr(L, name).restype = C.c_int
-        L.aid_spec_long_abi_version.argtypes = []
-        if L.aid_spec_long_abi_version() != AID_SPEC_LONG_ABI_VERSION:
-            raise AidError("include/aid_spec_long.h ABI version mismatch")
+        for exports, version_fn, version, header in SUB_ABIS:
+            for name in exports:
+                if not hasattr(L, name):
+                    raise AidError(f"libaid_hip.so does not export {name}")
+                getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
+                getattr(L, name).restype = C.c_int
+            getattr(L, version_fn).argtypes = []
+            if getattr(L, version_fn)() != version:
+                raise AidError(f"include/{header} ABI version mismatch")
         _lib = L
     return _lib
 

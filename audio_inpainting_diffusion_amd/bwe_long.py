@@ -42,28 +42,9 @@ NOT_WINDOWED = {
 
 
 def bwe_windows(N: int, L: int, end: int, K: int) -> List[Tuple[int, int, int, int, int]]:
-    """(start s, head, tail, lo, hi) of every window of a recording of N samples seen through K taps; [lo, hi) is the owned range relative
-    to s, cut at N.  The grid is restore.restore_windows'; heads, tails and owned ranges are trimmed by m = K - 1.  More than one window
-    needs end >= 2 m."""
-    K = int(K)
-    if K < 1:
-        raise _lib.AidError(f"bwe_windows: K = {K} taps must be >= 1")
-    grid = restore.restore_windows(N, L, end)                              # (N, L >= 1; end in [1, L/2))
-    N, L, end, m, W = int(N), int(L), int(end), K - 1, len(grid)
-    if W > 1 and end < 2 * m:
-        raise _lib.AidError(f"bwe_windows: the overlap end = {end} must be >= 2 (K - 1) = {2 * m} for a filter of K = {K} taps, so that every sample "
-                            "is observed with its whole filter support in the window that owns it")
-    wins = []
-    for w, (s, *_) in enumerate(grid):
-        last = w == W - 1
-        if w % 2 == 0:
-            head, tail, lo, hi = 0, 0, (m if w else 0), (L if last else L - m)
-        elif last:
-            head, tail, lo, hi = end - m, 0, end - m, L
-        else:
-            head, tail, lo, hi = end - m, end - m, end - m, L - end + m
-        wins.append((s, head, tail, lo, min(hi, N - s)))
-    return wins
+    """(start s, head, tail, lo, hi) of every window of a recording of N samples seen through K taps: restore.trimmed_windows(N, L, end, K),
+    the grid of restore.restore_windows with heads, tails and owned ranges trimmed by m = K - 1.  More than one window needs end >= 2 m."""
+    return restore.trimmed_windows(N, L, end, K)
 
 
 def window_state(N: int, L: int, K: int, s: int, head: int, tail: int) -> np.ndarray:
@@ -80,12 +61,7 @@ def window_state(N: int, L: int, K: int, s: int, head: int, tail: int) -> np.nda
 def bwe_plan(R: int, N: int, L: int, end: int, K: int):
     """(jobs_A, jobs_B): every even / odd window of every recording as (r, s, head, tail, lo, hi), ordered by recording and window -- all
     samples are degraded, so every window is a job."""
-    wins = bwe_windows(N, L, end, K)
-    jobs = ([], [])
-    for r in range(int(R)):
-        for w, win in enumerate(wins):
-            jobs[w % 2].append((r,) + win)
-    return jobs
+    return restore.every_window_plan(R, bwe_windows(N, L, end, K))
 
 
 def fir_taps(filt) -> torch.Tensor:
@@ -96,7 +72,7 @@ def fir_taps(filt) -> torch.Tensor:
     return t.reshape(-1).to("cpu", torch.float32).contiguous()
 
 
-class FIRObserved:
+class FIRObserved(restore.WindowOperator):
     """Observation of x[B, L] through taps[K] ("same" correlation, as degrade.FIRFilter) with state[1|B, L] (float32 on the GPU; 0 filtered,
     1 known, -1 unobserved, -2 absent).  With xin = 0 where absent, x elsewhere, and c = taps * xin:
 
@@ -105,42 +81,26 @@ class FIRObserved:
         project(x, y)  y where known, (-c + y) + x where filtered (the reference's data_consistency_step, in FIRFilter.project's order),
                        x where unobserved or absent
 
-    The operator protocol of degrade.py.  It holds per-item rows, so ``shared_mask`` is False; ``rows(lo, hi)`` is the operator of items
-    lo:hi, which is what lets network.denoise_guided run sub-batches of it on concurrent streams.  Linear: it keeps nothing between calls.
-    With every state 0, apply and adjoint give FIRFilter's bits."""
-    shared_mask = False
+    The operator protocol of degrade.py over restore.WindowOperator (``rows(lo, hi)``; the taps and a shared state row stay shared).
+    Linear: it keeps nothing between calls.  With every state 0, apply and adjoint give FIRFilter's bits."""
 
     def __init__(self, taps, state: torch.Tensor):
-        if not (torch.is_tensor(state) and state.is_cuda and state.dtype == torch.float32 and state.dim() == 2 and (state.stride(1) == 1 or state.shape[1] == 1)):
-            raise _lib.AidError("FIRObserved: state must be a float32 GPU tensor [1|B, L] with contiguous rows (no CPU fallback)")
+        super().__init__(state, "[1|B, L]")
         if torch.is_tensor(taps) and taps.is_cuda and taps.dtype == torch.float32 and taps.dim() == 1 and taps.is_contiguous() and taps.numel():
             self.taps = taps
         else:
             self.taps = fir_taps(taps).to(state.device)
-        self.state = state
         self.K, self.L = self.taps.numel(), state.shape[1]
-        self._sub = {}
 
-    def rows(self, lo: int, hi: int) -> "FIRObserved":
-        """The operator restricted to items lo:hi (views, no copy; the taps and a shared state row stay shared), kept per range."""
-        lo, hi = int(lo), int(hi)
-        rows = self.state.shape[0]
-        if not (0 <= lo < hi and (rows == 1 or hi <= rows)):
-            raise _lib.AidError(f"FIRObserved.rows: [{lo}, {hi}) is no range of {rows} items")
-        op = self._sub.get((lo, hi))
-        if op is None:
-            op = self._sub[(lo, hi)] = FIRObserved(self.taps, self.state if rows == 1 else self.state[lo:hi])
-        return op
+    def _slice(self, lo: int, hi: int) -> "FIRObserved":
+        return FIRObserved(self.taps, self._state_rows(lo, hi))
 
     def _run(self, mode, x, y=None):
-        x = x.reshape(x.shape[0], -1)
-        B, L, rows = x.shape[0], self.L, self.state.shape[0]
-        if not (x.is_cuda and x.dtype == torch.float32 and x.shape[1] == L and B >= 1 and rows in (1, B)):
-            raise _lib.AidError(f"FIRObserved: expected a float32 GPU tensor [{'B' if rows == 1 else rows}, {L}], got {tuple(x.shape)}")
-        x = x.contiguous()
+        x = self._signal(x, self.L)
         out = torch.empty_like(x)
+        L = self.L
         _lib.call("aid_fir_observed", _lib.FirObservedParams(x.data_ptr(), _lib.ptr(y), self.state.data_ptr(), self.taps.data_ptr(), out.data_ptr(),
-                                                             B, self.K, mode, L, L, L, self.state.stride(0) if rows > 1 else 0, L))
+                                                             x.shape[0], self.K, mode, L, L, L, self._state_ld, L))
         return out
 
     def apply(self, x):
@@ -150,13 +110,7 @@ class FIRObserved:
         return self._run(1, g)
 
     def project(self, x, y):
-        y = y.reshape(y.shape[0], -1)
-        if not (y.is_cuda and y.dtype == torch.float32 and tuple(y.shape) == (x.shape[0], self.L)):
-            raise _lib.AidError(f"FIRObserved.project: the observation must be a float32 GPU tensor [{x.shape[0]}, {self.L}], got {tuple(y.shape)}")
-        return self._run(2, x, y=y.contiguous())
-
-    def __call__(self, x):
-        return self.apply(x)
+        return self._run(2, x, y=self._observation(x, y, self.L))
 
 
 def bwe_gather(rec: torch.Tensor, out: torch.Tensor, jobs: torch.Tensor, L: int, K: int):
@@ -185,16 +139,10 @@ def check_bwe_args(y: torch.Tensor, filt, filt_type: str, L: int, end: int, max_
                             + NOT_WINDOWED[filt_type])
     if filt_type not in FIR_TYPES:
         raise NotImplementedError(f"predict_bwe_long: unknown filt_type {filt_type!r}")
-    if not (torch.is_tensor(y) and y.dtype == torch.float32 and y.dim() == 2 and (y.shape[1] <= 1 or y.stride(1) == 1)):
-        raise _lib.AidError(f"y must be float32 recordings [R, N] with contiguous rows, got {tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
+    restore.check_rows(y, "recordings [R, N]")
     taps = fir_taps(filt)
     bwe_windows(y.shape[1], L, end, taps.numel())                        # (end in [1, L/2); end >= 2 (K - 1) with more than one window)
-    if max_batch < 1:
-        raise _lib.AidError(f"max_batch must be >= 1, got {max_batch}")
-    if seeds is not None and len(seeds) != y.shape[0]:
-        raise _lib.AidError(f"{len(seeds)} seeds for {y.shape[0]} recordings")
-    if not y.is_cuda:
-        raise _lib.AidError("bandwidth extension of whole recordings runs on the GPU only (no CPU fallback): y must be a float32 tensor on the GPU")
+    restore.check_batch(y, max_batch, seeds, "bandwidth extension of whole recordings")
     return taps
 
 
@@ -207,8 +155,7 @@ def bwe_passes(sampler, y: torch.Tensor, filt, filt_type: str, L: int, end: int,
     R, N = y.shape
     K = taps.numel()
     jobs_A, jobs_B = bwe_plan(R, N, L, end, K)
-    out = torch.empty((R, N), dtype=torch.float32, device=y.device)
-    out.copy_(y)
+    out = y.clone(memory_format=torch.contiguous_format)
     dtaps = taps.to(y.device)
 
     def predict(win, c0, c1):

@@ -13,9 +13,6 @@
 #include "aid_fir_tile.h"
 #include "aid_bwe_long.h"
 
-__device__ __forceinline__ bool fo_known(float k) { return k > 0.f; }
-__device__ __forceinline__ bool fo_absent(float k) { return k <= -2.f; }
-
 // MODE 0 apply, 1 adjoint, 2 projection
 template <int MODE>
 __global__ __launch_bounds__(FIR_THREADS) void fir_observed_kernel(const aid_fir_observed_params p) {
@@ -27,7 +24,7 @@ __global__ __launch_bounds__(FIR_THREADS) void fir_observed_kernel(const aid_fir
     const int P = (p.K - 1) / 2;
     double accd[FIR_R];
     if (MODE == 1) fir_tile([&](int64_t q) { return (q >= 0 && q < L && k[q] == 0.f) ? x[q] : 0.f; }, tile0, p.h, p.K, p.K - 1 - P, 1, accd);
-    else           fir_tile([&](int64_t q) { return (q >= 0 && q < L && !fo_absent(k[q])) ? x[q] : 0.f; }, tile0, p.h, p.K, P, 0, accd);
+    else           fir_tile([&](int64_t q) { return (q >= 0 && q < L && !rs_absent(k[q])) ? x[q] : 0.f; }, tile0, p.h, p.K, P, 0, accd);
     float* __restrict__ out = p.out + b * p.out_ld;
 #pragma unroll
     for (int r = 0; r < FIR_R; ++r) {
@@ -35,11 +32,11 @@ __global__ __launch_bounds__(FIR_THREADS) void fir_observed_kernel(const aid_fir
         if (i < L) {
             const float c = (float)accd[r], kv = k[i], xv = x[i];
             float v;
-            if (MODE == 0) v = fo_known(kv) ? xv : (kv == 0.f ? c : 0.f);
-            else if (MODE == 1) v = fo_absent(kv) ? 0.f : (fo_known(kv) ? c + xv : c);
+            if (MODE == 0) v = rs_known(kv) ? xv : (kv == 0.f ? c : 0.f);
+            else if (MODE == 1) v = rs_absent(kv) ? 0.f : (rs_known(kv) ? c + xv : c);
             else {
                 const float yv = p.y[b * p.y_ld + i];
-                v = fo_known(kv) ? yv : (kv == 0.f ? (yv - c) + xv : xv);
+                v = rs_known(kv) ? yv : (kv == 0.f ? (yv - c) + xv : xv);
             }
             out[i] = v;
         }
@@ -50,14 +47,11 @@ __global__ __launch_bounds__(RS_THREADS) void bwe_gather_kernel(const aid_bwe_ga
     const int j = blockIdx.y;
     const int64_t L = p.L;
     const int64_t tid = (int64_t)blockIdx.x * RS_THREADS + threadIdx.x, nthreads = (int64_t)gridDim.x * RS_THREADS;
-    const rs_job b = rs_load_job(p.jobs, j, p.R, L, p.N);
-    // i < n_in  <=>  sample s + i exists; an invalid job gathers zeros, all absent
-    const int64_t n_in = b.ok ? (p.N - b.s < L ? p.N - b.s : L) : 0;
-    const int64_t head = b.ok ? b.head : 0, tail0 = L - (b.ok ? b.tail : 0);          // known from out: i < head or i >= tail0
-    const int64_t r = b.ok ? b.r : 0, s = b.ok ? b.s : 0;
+    const rs_window w = rs_load_window(p.jobs, j, p.R, L, p.N, 1);                   // (an invalid job gathers zeros, all absent)
+    const int64_t n_in = w.n_in, head = w.head, tail0 = w.tail0, r = w.r, s = w.s;
     const int64_t P = (p.K - 1) / 2, Q = p.K - 1 - P;
     // unobserved: i < u0 or i >= u1 (the filter support of such a sample leaves the window although the recording goes on there)
-    const int64_t u0 = s > 0 ? P : 0, u1 = (b.ok && s + L < p.N) ? L - Q : L;
+    const int64_t u0 = s > 0 ? P : 0, u1 = (w.ok && s + L < p.N) ? L - Q : L;
     // filtered exactly on [f0, f1), when that is a range
     const int64_t f0 = head > u0 ? head : u0, f1 = tail0 < u1 ? (tail0 < n_in ? tail0 : n_in) : (u1 < n_in ? u1 : n_in);
     const float* __restrict__ rec = p.rec + r * p.rec_ld + s;                         // (dereferenced at i < n_in only)
@@ -71,11 +65,8 @@ __global__ __launch_bounds__(RS_THREADS) void bwe_gather_kernel(const aid_bwe_ga
         yv = in ? (edge ? out[i] : (un ? 0.f : rec[i])) : 0.f;
     };
 
-    const int64_t lead = rs_lead(y, L);
-    const int64_t nvec = (L - lead) >> 2, body_end = lead + nvec * 4;
-    const bool k_al = rs_al16(k + lead), rec_al = rs_al16(rec + lead);
-    for (int64_t v = tid; v < nvec; v += nthreads) {
-        const int64_t i = lead + 4 * v;
+    const bool k_al = rs_aligned_as(k, y), rec_al = rs_aligned_as(rec, y);
+    rs_walk(y, L, tid, nthreads, [&](int64_t i) {
         float4 yv, kv;
         if (i >= f0 && i + 4 <= f1) {                                                // wholly the filtered recording
             kv = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -85,9 +76,7 @@ __global__ __launch_bounds__(RS_THREADS) void bwe_gather_kernel(const aid_bwe_ga
         }
         *reinterpret_cast<float4*>(y + i) = yv;
         rs_st4(k + i, k_al, kv);
-    }
-    if (tid < lead) elem(tid, y[tid], k[tid]);
-    if (tid < L - body_end) { const int64_t i = body_end + tid; elem(i, y[i], k[i]); }
+    }, [&](int64_t i) { elem(i, y[i], k[i]); });
 }
 
 extern "C" int aid_bwe_long_abi_version(void) { return AID_BWE_LONG_ABI_VERSION; }

@@ -29,34 +29,26 @@ __global__ __launch_bounds__(RS_THREADS) void clip_known_kernel(const aid_clip_k
 
     auto elem = [&](int64_t i) { out[i] = ck_elem<MODE>(x[i], MODE ? a[i] : 0.f, k[i], c); };
 
-    const int64_t lead = rs_lead(out, L);
-    const int64_t nvec = (L - lead) >> 2, body_end = lead + nvec * 4;
-    const bool x_al = rs_al16(x + lead), k_al = rs_al16(k + lead), a_al = rs_al16(a + lead);
-    for (int64_t v = tid; v < nvec; v += nthreads) {
-        const int64_t i = lead + 4 * v;
+    const bool x_al = rs_aligned_as(x, out), k_al = rs_aligned_as(k, out), a_al = rs_aligned_as(a, out);
+    rs_walk(out, L, tid, nthreads, [&](int64_t i) {
         const float4 xv = rs_ld4(x + i, x_al), kv = rs_ld4(k + i, k_al);
         const float4 av = MODE ? rs_ld4(a + i, a_al) : xv;
         *reinterpret_cast<float4*>(out + i) = make_float4(ck_elem<MODE>(xv.x, av.x, kv.x, c), ck_elem<MODE>(xv.y, av.y, kv.y, c),
                                                           ck_elem<MODE>(xv.z, av.z, kv.z, c), ck_elem<MODE>(xv.w, av.w, kv.w, c));
-    }
-    if (tid < lead) elem(tid);
-    if (tid < L - body_end) elem(body_end + tid);
+    }, elem);
 }
 
 __global__ __launch_bounds__(RS_THREADS) void declip_gather_kernel(const aid_declip_gather_params p) {
     const int j = blockIdx.y;
     const int64_t L = p.L;
     const int64_t tid = (int64_t)blockIdx.x * RS_THREADS + threadIdx.x, nthreads = (int64_t)gridDim.x * RS_THREADS;
-    const rs_job b = rs_load_job(p.jobs, j, p.R, L, p.N);
-    // i < n_in  <=>  sample s + i exists; an invalid job gathers zeros, all absent
-    const int64_t n_in = b.ok ? (p.N - b.s < L ? p.N - b.s : L) : 0;
-    const int64_t head = b.ok ? b.head : 0, tail0 = L - (b.ok ? b.tail : 0);          // known from out: i < head or i >= tail0
-    const int64_t r = b.ok ? b.r : 0, s = b.ok ? b.s : 0;
+    const rs_window w = rs_load_window(p.jobs, j, p.R, L, p.N, 1);                   // (an invalid job gathers zeros, all absent)
+    const int64_t n_in = w.n_in, head = w.head, tail0 = w.tail0, r = w.r, s = w.s;
     const float* __restrict__ rec = p.rec + r * p.rec_ld + s;                         // (dereferenced at i < n_in only)
     const float* __restrict__ out = p.out + r * p.out_ld + s;
     float* __restrict__ y = p.y + (int64_t)j * L;
     float* __restrict__ k = p.k + (int64_t)j * L;
-    if (tid == 0) p.c[j] = b.ok ? p.clip[r] : 0.f;
+    if (tid == 0) p.c[j] = w.ok ? p.clip[r] : 0.f;
 
     auto elem = [&](int64_t i, float& yv, float& kv) {
         const bool in = i < n_in, edge = i < head || i >= tail0;
@@ -64,11 +56,8 @@ __global__ __launch_bounds__(RS_THREADS) void declip_gather_kernel(const aid_dec
         yv = in ? (edge ? out[i] : rec[i]) : 0.f;
     };
 
-    const int64_t lead = rs_lead(y, L);
-    const int64_t nvec = (L - lead) >> 2, body_end = lead + nvec * 4;
-    const bool k_al = rs_al16(k + lead), rec_al = rs_al16(rec + lead), out_al = rs_al16(out + lead);
-    for (int64_t v = tid; v < nvec; v += nthreads) {
-        const int64_t i = lead + 4 * v;
+    const bool k_al = rs_aligned_as(k, y), rec_al = rs_aligned_as(rec, y), out_al = rs_aligned_as(out, y);
+    rs_walk(y, L, tid, nthreads, [&](int64_t i) {
         float4 yv, kv;
         if (i + 4 <= n_in && (i + 4 <= head || i >= tail0)) {                       // wholly known from the result so far
             kv = make_float4(1.f, 1.f, 1.f, 1.f);
@@ -84,9 +73,7 @@ __global__ __launch_bounds__(RS_THREADS) void declip_gather_kernel(const aid_dec
         }
         *reinterpret_cast<float4*>(y + i) = yv;
         rs_st4(k + i, k_al, kv);
-    }
-    if (tid < lead) elem(tid, y[tid], k[tid]);
-    if (tid < L - body_end) { const int64_t i = body_end + tid; elem(i, y[i], k[i]); }
+    }, [&](int64_t i) { elem(i, y[i], k[i]); });
 }
 
 extern "C" int aid_declip_abi_version(void) { return AID_DECLIP_ABI_VERSION; }

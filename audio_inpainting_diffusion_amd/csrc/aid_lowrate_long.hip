@@ -15,9 +15,6 @@
 
 #define RO_THREADS 256
 
-__device__ __forceinline__ bool ro_known(float k) { return k > 0.f; }
-__device__ __forceinline__ bool ro_absent(float k) { return k <= -2.f; }
-
 // MODE 0 apply, 1 adjoint
 template <int MODE>
 __global__ __launch_bounds__(RO_THREADS) void rate_observed_kernel(const aid_rate_observed_params p) {
@@ -31,7 +28,7 @@ __global__ __launch_bounds__(RO_THREADS) void rate_observed_kernel(const aid_rat
     if (MODE == 0) {
         if (e >= L + Mw) return;
         if (e < L) {
-            out[e] = ro_known(kh[e]) ? x[e] : 0.f;
+            out[e] = rs_known(kh[e]) ? x[e] : 0.f;
             return;
         }
         const int64_t n = e - L;
@@ -43,7 +40,7 @@ __global__ __launch_bounds__(RO_THREADS) void rate_observed_kernel(const aid_rat
             const int64_t base = i * orig - p.width;
             for (int t = 0; t < p.K; ++t) {
                 const int64_t q = base + t;
-                if (q >= 0 && q < L) acc += k[t] * (ro_absent(kh[q]) ? 0.f : x[q]);
+                if (q >= 0 && q < L) acc += k[t] * (rs_absent(kh[q]) ? 0.f : x[q]);
             }
         }
         out[e] = acc;
@@ -51,7 +48,7 @@ __global__ __launch_bounds__(RO_THREADS) void rate_observed_kernel(const aid_rat
         const int64_t q = e;
         if (q >= L) return;
         const float kv = kh[q];
-        if (ro_absent(kv)) {
+        if (rs_absent(kv)) {
             out[q] = 0.f;
             return;
         }
@@ -73,7 +70,7 @@ __global__ __launch_bounds__(RO_THREADS) void rate_observed_kernel(const aid_rat
             const float* __restrict__ k = p.kT + (int64_t)t * nw;
             for (int j = jl; j < jh; ++j) acc += k[j] * (kl[n0 + j] == 0.f ? g[n0 + j] : 0.f);
         }
-        out[q] = ro_known(kv) ? acc + x[q] : acc;
+        out[q] = rs_known(kv) ? acc + x[q] : acc;
     }
 }
 
@@ -81,14 +78,10 @@ __global__ __launch_bounds__(RS_THREADS) void lowrate_gather_kernel(const aid_lo
     const int j = blockIdx.y;
     const int64_t L = p.L, Mw = p.Mw, row = L + Mw;
     const int64_t tid = (int64_t)blockIdx.x * RS_THREADS + threadIdx.x, nthreads = (int64_t)gridDim.x * RS_THREADS;
-    rs_job b = rs_load_job(p.jobs, j, p.R, L, p.N);
-    b.ok = b.ok && b.s % p.orig_freq == 0;
-    // i < n_in  <=>  sample s + i exists; an invalid job gathers zeros, all absent
-    const int64_t n_in = b.ok ? (p.N - b.s < L ? p.N - b.s : L) : 0;
-    const int64_t head = b.ok ? b.head : 0, tail0 = L - (b.ok ? b.tail : 0);          // known from out: i < head or i >= tail0
-    const int64_t r = b.ok ? b.r : 0, s = b.ok ? b.s : 0;
+    const rs_window w = rs_load_window(p.jobs, j, p.R, L, p.N, p.orig_freq);                   // (an invalid job gathers zeros, all absent)
+    const int64_t n_in = w.n_in, head = w.head, tail0 = w.tail0, r = w.r, s = w.s;
     const int64_t m0 = (s / p.orig_freq) * p.new_freq;                               // the recording's low-rate sample of entry 0
-    const int64_t m_in = b.ok ? (p.M - m0 < 0 ? 0 : (p.M - m0 < Mw ? p.M - m0 : Mw)) : 0;   // n < m_in  <=>  low-rate sample m0 + n exists
+    const int64_t m_in = w.ok ? (p.M - m0 < 0 ? 0 : (p.M - m0 < Mw ? p.M - m0 : Mw)) : 0;   // n < m_in  <=>  low-rate sample m0 + n exists
     const bool cut_l = s > 0, cut_r = s + L < p.N;                                   // the recording goes on before / after the window
     const float* __restrict__ rec = p.rec + r * p.rec_ld + m0;                        // (dereferenced at n < m_in only)
     const float* __restrict__ out = p.out + r * p.out_ld + s;                         // (dereferenced at i < n_in only)

@@ -15,12 +15,9 @@
 #include "aid_stft_mag_tile.h"
 #include "aid_phase_long.h"
 
-__device__ __forceinline__ bool po_known(float k) { return k > 0.f; }
-__device__ __forceinline__ bool po_absent(float k) { return k <= -2.f; }
-
 struct po_row {                                                    // sample q of the row: 0 at and past L and where it is absent
     const float* __restrict__ x; const float* __restrict__ kh; int64_t L;
-    __device__ __forceinline__ float operator()(int64_t q) const { return q < L && !po_absent(kh[q]) ? x[q] : 0.f; }
+    __device__ __forceinline__ float operator()(int64_t q) const { return q < L && !rs_absent(kh[q]) ? x[q] : 0.f; }
 };
 struct po_observed {                                               // frame t was written to the scratch
     const float* __restrict__ kf;
@@ -35,7 +32,7 @@ __global__ __launch_bounds__(STFT_THREADS) void mag_observed_kernel(const aid_st
     const float* __restrict__ x = p.x + (int64_t)b * p.x_ld;
     const float* __restrict__ kh = p.state + (int64_t)b * p.state_ld;
     float* __restrict__ out = p.out + (int64_t)b * p.out_ld;
-    for (int64_t q = s0 + threadIdx.x; q < s0 + p.hop && q < L; q += STFT_THREADS) out[q] = po_known(kh[q]) ? x[q] : 0.f;
+    for (int64_t q = s0 + threadIdx.x; q < s0 + p.hop && q < L; q += STFT_THREADS) out[q] = rs_known(kh[q]) ? x[q] : 0.f;
     float* __restrict__ mag = out + L + t;                          // [F, Tw], frames contiguous
     if (kh[L + t] != 0.f) {                                         // (the same for every lane of the workgroup)
         for (int k = threadIdx.x; k < F; k += STFT_THREADS) mag[(int64_t)k * p.n_frames] = 0.f;
@@ -64,12 +61,12 @@ __global__ __launch_bounds__(256) void mag_observed_ola_kernel(const aid_stft_ma
     float* __restrict__ out = p.out + (int64_t)b * p.out_ld;
     for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < L; q += (int64_t)gridDim.x * 256) {
         const float kv = kh[q];
-        if (po_absent(kv)) {
+        if (rs_absent(kv)) {
             out[q] = 0.f;
             continue;
         }
         const float a = pm_ola(po_observed{kh + L}, fr, q, N, p.hop);
-        out[q] = po_known(kv) ? a + g[q] : a;
+        out[q] = rs_known(kv) ? a + g[q] : a;
     }
 }
 
@@ -77,14 +74,10 @@ __global__ __launch_bounds__(RS_THREADS) void pr_gather_kernel(const aid_pr_gath
     const int j = blockIdx.y;
     const int64_t L = p.L, Tw = p.n_frames, F = (p.n_fft >> 1) + 1, row = L + F * Tw;
     const int64_t tid = (int64_t)blockIdx.x * RS_THREADS + threadIdx.x, nthreads = (int64_t)gridDim.x * RS_THREADS;
-    rs_job b = rs_load_job(p.jobs, j, p.R, L, p.N);
-    b.ok = b.ok && b.s % p.hop == 0;
-    // i < n_in  <=>  sample s + i exists; an invalid job gathers zeros, all absent
-    const int64_t n_in = b.ok ? (p.N - b.s < L ? p.N - b.s : L) : 0;
-    const int64_t head = b.ok ? b.head : 0, tail0 = L - (b.ok ? b.tail : 0);          // known from out: i < head or i >= tail0
-    const int64_t r = b.ok ? b.r : 0, s = b.ok ? b.s : 0;
+    const rs_window w = rs_load_window(p.jobs, j, p.R, L, p.N, p.hop);                   // (an invalid job gathers zeros, all absent)
+    const int64_t n_in = w.n_in, head = w.head, tail0 = w.tail0, r = w.r, s = w.s;
     const int64_t t0 = s / p.hop;                                                    // the recording's frame of window frame 0
-    const int64_t t_in = b.ok ? (p.T_rec - t0 < 0 ? 0 : (p.T_rec - t0 < Tw ? p.T_rec - t0 : Tw)) : 0;   // f < t_in  <=>  frame t0 + f exists
+    const int64_t t_in = w.ok ? (p.T_rec - t0 < 0 ? 0 : (p.T_rec - t0 < Tw ? p.T_rec - t0 : Tw)) : 0;   // f < t_in  <=>  frame t0 + f exists
     const bool cut_r = s + L < p.N;                                                  // the recording goes on after the window
     const float* __restrict__ rec = p.rec + r * p.rec_ld + t0;                        // (dereferenced at f < t_in only)
     const float* __restrict__ out = p.out + r * p.out_ld + s;                         // (dereferenced at i < n_in only)

@@ -11,11 +11,8 @@ __global__ __launch_bounds__(RS_THREADS) void window_gather_kernel(const aid_win
     const int j = blockIdx.y;
     const int64_t L = p.L;
     const int64_t tid = (int64_t)blockIdx.x * RS_THREADS + threadIdx.x, nthreads = (int64_t)gridDim.x * RS_THREADS;
-    const rs_job b = rs_load_job(p.jobs, j, p.R, L, p.N);
-    // i < n_in  <=>  sample s + i exists; an invalid job gathers zeros with mask 0
-    const int64_t n_in = b.ok ? (p.N - b.s < L ? p.N - b.s : L) : 0;
-    const int64_t head = b.ok ? b.head : 0, tail0 = L - (b.ok ? b.tail : 0);          // observed from out: i < head or i >= tail0
-    const int64_t r = b.ok ? b.r : 0, s = b.ok ? b.s : 0;
+    const rs_window w = rs_load_window(p.jobs, j, p.R, L, p.N, 1);                   // (an invalid job gathers zeros with mask 0)
+    const int64_t n_in = w.n_in, head = w.head, tail0 = w.tail0, r = w.r, s = w.s;
     const float* __restrict__ rec = p.rec + r * p.rec_ld + s;                         // (dereferenced at i < n_in only)
     const float* __restrict__ out = p.out + r * p.out_ld + s;
     const float* __restrict__ mask = p.mask + r * p.mask_ld + s;
@@ -28,11 +25,8 @@ __global__ __launch_bounds__(RS_THREADS) void window_gather_kernel(const aid_win
         yv = mv * (in ? (edge ? out[i] : rec[i]) : 0.f);
     };
 
-    const int64_t lead = rs_lead(y, L);
-    const int64_t nvec = (L - lead) >> 2, body_end = lead + nvec * 4;
-    const bool m_al = rs_al16(m + lead), rec_al = rs_al16(rec + lead), out_al = rs_al16(out + lead), mask_al = rs_al16(mask + lead);
-    for (int64_t v = tid; v < nvec; v += nthreads) {
-        const int64_t i = lead + 4 * v;
+    const bool m_al = rs_aligned_as(m, y), rec_al = rs_aligned_as(rec, y), out_al = rs_aligned_as(out, y), mask_al = rs_aligned_as(mask, y);
+    rs_walk(y, L, tid, nthreads, [&](int64_t i) {
         float4 yv, mv;
         if (i + 4 <= n_in && (i + 4 <= head || i >= tail0)) {                       // wholly observed from the result so far
             mv = make_float4(1.f, 1.f, 1.f, 1.f);
@@ -46,22 +40,14 @@ __global__ __launch_bounds__(RS_THREADS) void window_gather_kernel(const aid_win
         }
         *reinterpret_cast<float4*>(y + i) = yv;
         rs_st4(m + i, m_al, mv);
-    }
-    if (tid < lead) elem(tid, y[tid], m[tid]);
-    if (tid < L - body_end) { const int64_t i = body_end + tid; elem(i, y[i], m[i]); }
+    }, [&](int64_t i) { elem(i, y[i], m[i]); });
 }
 
 // dst[i] = src[i] for i < n   (tid / nthreads: this lane's index and the lane count over the row)
 __device__ __forceinline__ void rs_copy_row(float* __restrict__ dst, const float* __restrict__ src, int64_t n, int64_t tid, int64_t nthreads) {
-    const int64_t lead = rs_lead(dst, n);
-    const int64_t nvec = (n - lead) >> 2, body_end = lead + nvec * 4;
-    const bool src_al = rs_al16(src + lead);
-    for (int64_t v = tid; v < nvec; v += nthreads) {
-        const int64_t i = lead + 4 * v;
-        *reinterpret_cast<float4*>(dst + i) = rs_ld4(src + i, src_al);
-    }
-    if (tid < lead) dst[tid] = src[tid];
-    if (tid < n - body_end) dst[body_end + tid] = src[body_end + tid];
+    const bool src_al = rs_aligned_as(src, dst);
+    rs_walk(dst, n, tid, nthreads, [&](int64_t i) { *reinterpret_cast<float4*>(dst + i) = rs_ld4(src + i, src_al); },
+            [&](int64_t i) { dst[i] = src[i]; });
 }
 
 __global__ __launch_bounds__(RS_THREADS) void window_scatter_kernel(const aid_window_scatter_params p) {

@@ -17,9 +17,6 @@
 #include "aid_stft_tile.h"
 #include "aid_spec_long.h"
 
-__device__ __forceinline__ bool so_known(float k) { return k > 0.f; }
-__device__ __forceinline__ bool so_absent(float k) { return k <= -2.f; }
-
 // Frame t in [0, T_rec) of a recording of N samples padded to Np is computable in the window [s, s + L): the positions it reads are
 // [a, a + n_fft), a = t*hop - half; folded at 0 they are [max(a, 0), max(a + n_fft - 1, -a)], folded at Np (a < Np) the part at and
 // past Np lands on [2 (Np - 1) - hi, Np - 2], next to the part below Np: one range again.  What of it lies below N must lie in the window.
@@ -87,7 +84,7 @@ __global__ __launch_bounds__(STFT_THREADS) void mask_observed_frames_kernel(cons
             }
             return v;
         }
-        return so_absent(kv) ? 0.f : x[i];
+        return rs_absent(kv) ? 0.f : x[i];
     };
     st_mask_frame(load, N, p.window, p.twiddle, p.mask + it.r * p.mask_sB + t, p.mask_ld, so_lds, so_lds + N,
                   p.frames + ((int64_t)b * p.n_frames + j) * N);
@@ -117,14 +114,14 @@ __global__ __launch_bounds__(256) void mask_observed_ola_kernel(const aid_stft_m
                 const int64_t r = 2 * (p.Np - 1) - n;
                 if (r >= p.Np && r < p.Np + half) a += st_cover(use, fr, r, N, p.hop, T_rec, it.t0, Tw);   // right reflection
             }
-            v = so_absent(kv) ? 0.f : (so_known(kv) ? a + xv : a);
+            v = rs_absent(kv) ? 0.f : (rs_known(kv) ? a + xv : a);
         } else {
             float c = 0.f;
             if (kv == 0.f && in) c = __fmul_rn(st_cover(use, fr, n, N, p.hop, T_rec, it.t0, Tw), p.inv_env[n]);
-            if (MODE == 0) v = so_known(kv) ? xv : (kv == 0.f ? c : 0.f);
+            if (MODE == 0) v = rs_known(kv) ? xv : (kv == 0.f ? c : 0.f);
             else {
                 const float yv = p.y[(int64_t)b * p.y_ld + i];
-                v = so_known(kv) ? yv : (kv == 0.f ? __fadd_rn(__fadd_rn(-c, yv), xv) : xv);
+                v = rs_known(kv) ? yv : (kv == 0.f ? __fadd_rn(__fadd_rn(-c, yv), xv) : xv);
             }
         }
         out[i] = v;
@@ -136,12 +133,8 @@ __global__ __launch_bounds__(RS_THREADS) void spec_gather_kernel(const aid_spec_
     const int64_t L = p.L, Tw = p.n_frames, row = L + Tw, T_rec = 1 + p.Np / p.hop;
     const int half = p.n_fft >> 1;
     const int64_t tid = (int64_t)blockIdx.x * RS_THREADS + threadIdx.x, nthreads = (int64_t)gridDim.x * RS_THREADS;
-    rs_job b = rs_load_job(p.jobs, j, p.R, L, p.N);
-    b.ok = b.ok && b.s % p.hop == 0;
-    // i < n_in  <=>  sample s + i exists; an invalid job gathers zeros, all absent
-    const int64_t n_in = b.ok ? (p.N - b.s < L ? p.N - b.s : L) : 0;
-    const int64_t head = b.ok ? b.head : 0, tail0 = L - (b.ok ? b.tail : 0);          // known from out: i < head or i >= tail0
-    const int64_t r = b.ok ? b.r : 0, s = b.ok ? b.s : 0;
+    const rs_window w = rs_load_window(p.jobs, j, p.R, L, p.N, p.hop);                   // (an invalid job gathers zeros, all absent)
+    const int64_t n_in = w.n_in, head = w.head, tail0 = w.tail0, r = w.r, s = w.s;
     const int64_t t0 = s / p.hop;
     const float* __restrict__ rec = p.rec + r * p.rec_ld + s;                         // (dereferenced at i < n_in only)
     const float* __restrict__ out = p.out + r * p.out_ld + s;
@@ -149,7 +142,7 @@ __global__ __launch_bounds__(RS_THREADS) void spec_gather_kernel(const aid_spec_
     float* __restrict__ st = p.state + (int64_t)j * row;
     if (tid == 0) {
         int64_t* it = p.items + (int64_t)j * AID_SPEC_ITEM_FIELDS;
-        it[0] = b.ok ? r : -1; it[1] = b.ok ? s : -1; it[2] = b.ok ? p.N : 0;
+        it[0] = w.ok ? r : -1; it[1] = w.ok ? s : -1; it[2] = w.ok ? p.N : 0;
     }
     for (int64_t e = tid; e < row; e += nthreads) {
         float kv = -2.f;
@@ -171,7 +164,7 @@ __global__ __launch_bounds__(RS_THREADS) void spec_gather_kernel(const aid_spec_
                 }
             }
             y[e] = yv;
-        } else if (b.ok) {
+        } else if (w.ok) {
             const int64_t t = t0 + (e - L);
             if (t < T_rec) kv = so_computable(t, s, L, p.N, p.Np, p.n_fft, p.hop) ? 0.f : -1.f;
         }

@@ -21,7 +21,7 @@ from . import _lib
 from . import restore
 
 
-class ClipObserved:
+class ClipObserved(restore.WindowOperator):
     """Observation of x[B, L] with state[1|B, L] (float32 on the GPU; 0 clipped, 1 known, -1 absent) and clip[B] (levels > 0; a float32 GPU
     tensor is used as it is and NOT inspected, anything else is checked on the host and uploaded):
 
@@ -31,13 +31,11 @@ class ClipObserved:
         project(x, y)  the point nearest to x among the signals consistent with y: y where known or |y| < c_b, max(x, c_b) where y >= c_b,
                        min(x, -c_b) where y <= -c_b, x where absent
 
-    The operator protocol of degrade.py.  It holds per-item rows, so ``shared_mask`` is False; ``rows(lo, hi)`` is the operator of items
-    lo:hi, which is what lets network.denoise_guided run sub-batches of it on concurrent streams."""
-    shared_mask = False
+    The operator protocol of degrade.py over restore.WindowOperator (``rows(lo, hi)``, the per-stream x_hat).  It holds one level per item,
+    so it serves exactly B items even through a shared state row."""
 
     def __init__(self, state: torch.Tensor, clip):
-        if not (torch.is_tensor(state) and state.is_cuda and state.dtype == torch.float32 and state.dim() == 2 and (state.stride(1) == 1 or state.shape[1] == 1)):
-            raise _lib.AidError("ClipObserved: state must be a float32 GPU tensor [1|B, L] with contiguous rows (no CPU fallback)")
+        super().__init__(state, "[1|B, L]")
         if torch.is_tensor(clip) and clip.is_cuda:
             if clip.dtype != torch.float32:
                 raise _lib.AidError("ClipObserved: clip levels on the GPU must be float32")
@@ -46,51 +44,34 @@ class ClipObserved:
             clip = torch.from_numpy(clip_levels(clip)).to(state.device)
         if state.shape[0] not in (1, clip.numel()):
             raise _lib.AidError(f"ClipObserved: {state.shape[0]} state rows for {clip.numel()} clip levels")
-        self.state, self.clip = state, clip
+        self.clip = clip
         self.B, self.L = clip.numel(), state.shape[1]
-        self._x, self._sub = {}, {}
 
-    def rows(self, lo: int, hi: int) -> "ClipObserved":
-        """The operator restricted to items lo:hi (views, no copy; a shared state row stays shared).  Kept per range, so that the apply / adjoint
-        pair of a sub-batch meets the same object."""
-        lo, hi = int(lo), int(hi)
-        if not 0 <= lo < hi <= self.B:
-            raise _lib.AidError(f"ClipObserved.rows: [{lo}, {hi}) is no range of {self.B} items")
-        op = self._sub.get((lo, hi))
-        if op is None:
-            op = self._sub[(lo, hi)] = ClipObserved(self.state if self.state.shape[0] == 1 else self.state[lo:hi], self.clip[lo:hi])
-        return op
+    @property
+    def items_held(self) -> int:
+        return self.B
+
+    def _slice(self, lo: int, hi: int) -> "ClipObserved":
+        return ClipObserved(self._state_rows(lo, hi), self.clip[lo:hi])
 
     def _run(self, mode, x, xref=None, y=None):
-        x = x.reshape(x.shape[0], -1)
-        if not (x.is_cuda and x.dtype == torch.float32 and tuple(x.shape) == (self.B, self.L)):
-            raise _lib.AidError(f"ClipObserved: expected a float32 GPU tensor [{self.B}, {self.L}], got {tuple(x.shape)}")
-        x = x.contiguous()
+        x = self._signal(x, self.L)
         out = torch.empty_like(x)
         L = self.L
         _lib.call("aid_clip_known", _lib.ClipKnownParams(x.data_ptr(), _lib.ptr(xref), _lib.ptr(y), self.state.data_ptr(), self.clip.data_ptr(), out.data_ptr(),
-                                                         self.B, mode, L, L, L, L, self.state.stride(0) if self.state.shape[0] > 1 else 0, L))
+                                                         self.B, mode, L, L, L, L, self._state_ld, L))
         return out, x
 
     def apply(self, x):
         out, x = self._run(0, x)
-        self._x[torch.cuda.current_stream().cuda_stream] = x
+        self._keep(x)
         return out
 
     def adjoint(self, g):
-        xref = self._x.get(torch.cuda.current_stream().cuda_stream)
-        if xref is None or xref.numel() != g.numel():
-            raise _lib.AidError("ClipObserved.adjoint needs the matching apply on this stream first")
-        return self._run(1, g, xref=xref)[0]
+        return self._run(1, g, xref=self._kept(g))[0]
 
     def project(self, x, y):
-        y = y.reshape(y.shape[0], -1)
-        if not (y.is_cuda and y.dtype == torch.float32 and tuple(y.shape) == (self.B, self.L)):
-            raise _lib.AidError(f"ClipObserved.project: the observation must be a float32 GPU tensor [{self.B}, {self.L}], got {tuple(y.shape)}")
-        return self._run(2, x, y=y.contiguous())[0]
-
-    def __call__(self, x):
-        return self.apply(x)
+        return self._run(2, x, y=self._observation(x, y, self.L))[0]
 
 
 def clip_levels(clip_value, R: Optional[int] = None) -> np.ndarray:
@@ -129,16 +110,10 @@ def declip_gather(rec: torch.Tensor, out: torch.Tensor, clip: torch.Tensor, jobs
 def check_declip_args(y: torch.Tensor, clip, L: int, end: int, max_batch: int, seeds) -> np.ndarray:
     """The refusals of a declipping run, all raised before anything is launched -> the R clip levels (float32, host).  What can be judged
     without a GPU is judged first; the device of y last."""
-    if not (torch.is_tensor(y) and y.dtype == torch.float32 and y.dim() == 2 and (y.shape[1] <= 1 or y.stride(1) == 1)):
-        raise _lib.AidError(f"y must be float32 recordings [R, N] with contiguous rows, got {tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
+    restore.check_rows(y, "recordings [R, N]")
     levels = clip_levels(clip, y.shape[0])
     restore.restore_windows(y.shape[1], L, end)                       # (end in [1, L/2))
-    if max_batch < 1:
-        raise _lib.AidError(f"max_batch must be >= 1, got {max_batch}")
-    if seeds is not None and len(seeds) != y.shape[0]:
-        raise _lib.AidError(f"{len(seeds)} seeds for {y.shape[0]} recordings")
-    if not y.is_cuda:
-        raise _lib.AidError("declipping of whole recordings runs on the GPU only (no CPU fallback): y must be a float32 tensor on the GPU")
+    restore.check_batch(y, max_batch, seeds, "declipping of whole recordings")
     return levels
 
 
@@ -155,10 +130,8 @@ def declip_passes(sampler, y: torch.Tensor, clip, L: int, end: int, max_batch: i
     aid_declip_gather launch, the sampler calls, one aid_window_scatter launch per call (restore.run_passes).  Recordings and result stay on
     the GPU; the plan is made on the host from |y| < c before pass A.  Seeds as restore.restore_passes."""
     levels = check_declip_args(y, clip, L, end, max_batch, seeds)
-    R, N = y.shape
     jobs_A, jobs_B, _ = declip_plan(y, levels, L, end)
-    out = torch.empty((R, N), dtype=torch.float32, device=y.device)
-    out.copy_(y)
+    out = y.clone(memory_format=torch.contiguous_format)
     if not (jobs_A or jobs_B):
         return out
     dclip = torch.from_numpy(levels).to(y.device)

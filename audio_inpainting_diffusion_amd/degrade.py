@@ -288,24 +288,31 @@ def resample_host_tables(orig: int, new: int):
     return k, width, kT, j_lo, j_hi
 
 
-_RESAMPLE_TABLES = {}
+_DEVICE_TABLES = {}
+
+
+def device_tables(key, device, build):
+    """``build(device)`` -> a tuple of tables on ``device``, made once per (key, device) and kept.  The upload is waited for, so that any
+    stream may read the tables afterwards."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    tab = _DEVICE_TABLES.get((key, device))
+    if tab is None:
+        tab = build(device)
+        if device.type == "cuda":
+            torch.cuda.current_stream(device).synchronize()
+        _DEVICE_TABLES[(key, device)] = tab
+    return tab
 
 
 def resample_tables(orig: int, new: int, device):
     """The device copies of resample_host_tables, built once per (ratio, device) and shared by harness.resample and SincResample:
-    (k, width, kT, j_lo, j_hi).  The upload is waited for, so that any stream may read the tables afterwards."""
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    key = (orig, new, device)
-    tab = _RESAMPLE_TABLES.get(key)
-    if tab is None:
+    (k, width, kT, j_lo, j_hi)."""
+    def build(device):
         k, width, kT, j_lo, j_hi = resample_host_tables(orig, new)
-        tab = (torch.from_numpy(k).to(device), width) + tuple(torch.from_numpy(a).to(device) for a in (kT, j_lo, j_hi))
-        if device.type == "cuda":
-            torch.cuda.current_stream(device).synchronize()
-        _RESAMPLE_TABLES[key] = tab
-    return tab
+        return (torch.from_numpy(k).to(device), width) + tuple(torch.from_numpy(a).to(device) for a in (kT, j_lo, j_hi))
+    return device_tables(("resample", orig, new), device, build)
 
 
 def resample_poly(x, orig: int, new: int):

@@ -141,6 +141,23 @@ def generate_long(sampler, n_items: int, n_windows: int, seeds: Optional[Sequenc
     return D.gather_outputs(local, n_items)
 
 
+def _long_groups(who: str, files, seeds, device, key, call, flat: bool = True) -> List[torch.Tensor]:
+    """The loop the *_long functions below share: the files with equal ``key(i)`` are stacked on ``device`` (``flat``: each as a 1-D waveform)
+    and go through ONE ``call(y, idx, key, seeds of idx)`` -> [len(idx), ...]; its rows come back in the order of ``files``."""
+    if seeds is not None and len(seeds) != len(files):
+        raise ValueError(f"{who}: {len(seeds)} seeds for {len(files)} files")
+    groups = {}
+    for i in range(len(files)):
+        groups.setdefault(key(i), []).append(i)
+    out: List[Optional[torch.Tensor]] = [None] * len(files)
+    for k, idx in groups.items():
+        y = torch.stack([(files[i].reshape(-1) if flat else files[i]).float() for i in idx]).to(device)
+        res = call(y, idx, k, None if seeds is None else [int(seeds[i]) for i in idx])
+        for j, i in enumerate(idx):
+            out[i] = res[j]
+    return out
+
+
 def restore_long(sampler, files: Sequence[torch.Tensor], masks: Sequence[torch.Tensor], seeds: Optional[Sequence[int]] = None, max_batch: int = 8,
                  device="cuda") -> List[torch.Tensor]:
     """Restore every 1-D waveform of ``files`` (any lengths) where its mask (same length; 1 = observed, 0 = gap, gaps anywhere) is 0 and return the
@@ -149,21 +166,13 @@ def restore_long(sampler, files: Sequence[torch.Tensor], masks: Sequence[torch.T
     depends on seeds[i] alone, not on the grouping)."""
     if len(masks) != len(files):
         raise ValueError(f"restore_long: {len(masks)} masks for {len(files)} files")
-    if seeds is not None and len(seeds) != len(files):
-        raise ValueError(f"restore_long: {len(seeds)} seeds for {len(files)} files")
-    groups = {}
-    for i, (x, m) in enumerate(zip(files, masks)):
-        if x.numel() != m.numel():
-            raise ValueError(f"restore_long: file {i} has {x.numel()} samples, its mask {m.numel()}")
-        groups.setdefault(x.numel(), []).append(i)
-    out: List[Optional[torch.Tensor]] = [None] * len(files)
-    for idx in groups.values():
-        y = torch.stack([files[i].reshape(-1).float() for i in idx]).to(device)
-        m = torch.stack([masks[i].reshape(-1).float() for i in idx])
-        res = sampler.predict_inpainting_long(y, m, max_batch=max_batch, seeds=None if seeds is None else [int(seeds[i]) for i in idx])
-        for k, i in enumerate(idx):
-            out[i] = res[k]
-    return out
+
+    def key(i):
+        if files[i].numel() != masks[i].numel():
+            raise ValueError(f"restore_long: file {i} has {files[i].numel()} samples, its mask {masks[i].numel()}")
+        return files[i].numel()
+    return _long_groups("restore_long", files, seeds, device, key, lambda y, idx, _, sd: sampler.predict_inpainting_long(
+        y, torch.stack([masks[i].reshape(-1).float() for i in idx]), max_batch=max_batch, seeds=sd))
 
 
 def declip_long(sampler, files: Sequence[torch.Tensor], clip_values, seeds: Optional[Sequence[int]] = None, max_batch: int = 8,
@@ -178,18 +187,8 @@ def declip_long(sampler, files: Sequence[torch.Tensor], clip_values, seeds: Opti
         raise ValueError(f"declip_long: {len(levels)} clip values for {len(files)} files")
     if len(levels) == 1:
         levels = levels * len(files)
-    if seeds is not None and len(seeds) != len(files):
-        raise ValueError(f"declip_long: {len(seeds)} seeds for {len(files)} files")
-    groups = {}
-    for i, x in enumerate(files):
-        groups.setdefault(x.numel(), []).append(i)
-    out: List[Optional[torch.Tensor]] = [None] * len(files)
-    for idx in groups.values():
-        y = torch.stack([files[i].reshape(-1).float() for i in idx]).to(device)
-        res = sampler.predict_declipping_long(y, [levels[i] for i in idx], max_batch=max_batch, seeds=None if seeds is None else [int(seeds[i]) for i in idx])
-        for k, i in enumerate(idx):
-            out[i] = res[k]
-    return out
+    return _long_groups("declip_long", files, seeds, device, lambda i: files[i].numel(), lambda y, idx, _, sd: sampler.predict_declipping_long(
+        y, [levels[i] for i in idx], max_batch=max_batch, seeds=sd))
 
 
 def bwe_long(sampler, files: Sequence[torch.Tensor], filt, filt_type: str = "firwin", seeds: Optional[Sequence[int]] = None, max_batch: int = 8,
@@ -198,18 +197,8 @@ def bwe_long(sampler, files: Sequence[torch.Tensor], filt, filt_type: str = "fir
     files), and return the full-length results on ``device``, in the order of ``files``.  Files of equal length go through ONE
     Sampler.predict_bwe_long call, so their windows share the two batched passes; every other length is a call of its own.  ``seeds``: one RNG
     seed per file (file i's result then depends on seeds[i] alone, not on the grouping)."""
-    if seeds is not None and len(seeds) != len(files):
-        raise ValueError(f"bwe_long: {len(seeds)} seeds for {len(files)} files")
-    groups = {}
-    for i, x in enumerate(files):
-        groups.setdefault(x.numel(), []).append(i)
-    out: List[Optional[torch.Tensor]] = [None] * len(files)
-    for idx in groups.values():
-        y = torch.stack([files[i].reshape(-1).float() for i in idx]).to(device)
-        res = sampler.predict_bwe_long(y, filt, filt_type, max_batch=max_batch, seeds=None if seeds is None else [int(seeds[i]) for i in idx])
-        for k, i in enumerate(idx):
-            out[i] = res[k]
-    return out
+    return _long_groups("bwe_long", files, seeds, device, lambda i: files[i].numel(), lambda y, idx, _, sd: sampler.predict_bwe_long(
+        y, filt, filt_type, max_batch=max_batch, seeds=sd))
 
 
 def bwe_lowrate_long(sampler, files: Sequence[torch.Tensor], factor, filt_type: str = "resample", lengths: Optional[Sequence[Optional[int]]] = None,
@@ -221,19 +210,9 @@ def bwe_lowrate_long(sampler, files: Sequence[torch.Tensor], factor, filt_type: 
     depends on seeds[i] alone, not on the grouping)."""
     if lengths is not None and len(lengths) != len(files):
         raise ValueError(f"bwe_lowrate_long: {len(lengths)} lengths for {len(files)} files")
-    if seeds is not None and len(seeds) != len(files):
-        raise ValueError(f"bwe_lowrate_long: {len(seeds)} seeds for {len(files)} files")
-    groups = {}
-    for i, x in enumerate(files):
-        n = None if lengths is None or lengths[i] is None else int(lengths[i])
-        groups.setdefault((x.numel(), n), []).append(i)
-    out: List[Optional[torch.Tensor]] = [None] * len(files)
-    for (_, n), idx in groups.items():
-        y = torch.stack([files[i].reshape(-1).float() for i in idx]).to(device)
-        res = sampler.predict_bwe_lowrate_long(y, factor, filt_type, length=n, max_batch=max_batch, seeds=None if seeds is None else [int(seeds[i]) for i in idx])
-        for k, i in enumerate(idx):
-            out[i] = res[k]
-    return out
+    return _long_groups("bwe_lowrate_long", files, seeds, device,
+                        lambda i: (files[i].numel(), None if lengths is None or lengths[i] is None else int(lengths[i])),
+                        lambda y, idx, k, sd: sampler.predict_bwe_lowrate_long(y, factor, filt_type, length=k[1], max_batch=max_batch, seeds=sd))
 
 
 def pr_long(sampler, spectrograms: Sequence[torch.Tensor], lengths: Optional[Sequence[Optional[int]]] = None, seeds: Optional[Sequence[int]] = None,
@@ -245,21 +224,13 @@ def pr_long(sampler, spectrograms: Sequence[torch.Tensor], lengths: Optional[Seq
     not on the grouping)."""
     if lengths is not None and len(lengths) != len(spectrograms):
         raise ValueError(f"pr_long: {len(lengths)} lengths for {len(spectrograms)} files")
-    if seeds is not None and len(seeds) != len(spectrograms):
-        raise ValueError(f"pr_long: {len(seeds)} seeds for {len(spectrograms)} files")
-    groups = {}
-    for i, x in enumerate(spectrograms):
-        if x.dim() != 2:
-            raise ValueError(f"pr_long: file {i} must be a magnitude spectrogram [F, T_rec], got {tuple(x.shape)}")
-        n = None if lengths is None or lengths[i] is None else int(lengths[i])
-        groups.setdefault((tuple(x.shape), n), []).append(i)
-    out: List[Optional[torch.Tensor]] = [None] * len(spectrograms)
-    for (_, n), idx in groups.items():
-        y = torch.stack([spectrograms[i].float() for i in idx]).to(device)
-        res = sampler.predict_pr_long(y, length=n, max_batch=max_batch, seeds=None if seeds is None else [int(seeds[i]) for i in idx])
-        for k, i in enumerate(idx):
-            out[i] = res[k]
-    return out
+
+    def key(i):
+        if spectrograms[i].dim() != 2:
+            raise ValueError(f"pr_long: file {i} must be a magnitude spectrogram [F, T_rec], got {tuple(spectrograms[i].shape)}")
+        return tuple(spectrograms[i].shape), None if lengths is None or lengths[i] is None else int(lengths[i])
+    return _long_groups("pr_long", spectrograms, seeds, device, key,
+                        lambda y, idx, k, sd: sampler.predict_pr_long(y, length=k[1], max_batch=max_batch, seeds=sd), flat=False)
 
 
 def spectrogram_inpainting_long(sampler, files: Sequence[torch.Tensor], masks: Sequence[torch.Tensor], seeds: Optional[Sequence[int]] = None,
@@ -270,22 +241,13 @@ def spectrogram_inpainting_long(sampler, files: Sequence[torch.Tensor], masks: S
     call of its own.  ``seeds``: one RNG seed per file (file i's result then depends on seeds[i] alone, not on the grouping)."""
     if len(masks) != len(files):
         raise ValueError(f"spectrogram_inpainting_long: {len(masks)} masks for {len(files)} files")
-    if seeds is not None and len(seeds) != len(files):
-        raise ValueError(f"spectrogram_inpainting_long: {len(seeds)} seeds for {len(files)} files")
-    for i, m in enumerate(masks):
-        if m.dim() != 2:
-            raise ValueError(f"spectrogram_inpainting_long: mask {i} must be [F, T_rec], got {tuple(m.shape)}")
-    groups = {}
-    for i, x in enumerate(files):
-        groups.setdefault((x.numel(), tuple(masks[i].shape)), []).append(i)
-    out: List[Optional[torch.Tensor]] = [None] * len(files)
-    for idx in groups.values():
-        y = torch.stack([files[i].reshape(-1).float() for i in idx]).to(device)
-        m = torch.stack([masks[i].float() for i in idx]).to(device)
-        res = sampler.predict_spectrogram_inpainting_long(y, m, max_batch=max_batch, seeds=None if seeds is None else [int(seeds[i]) for i in idx])
-        for k, i in enumerate(idx):
-            out[i] = res[k]
-    return out
+
+    def key(i):
+        if masks[i].dim() != 2:
+            raise ValueError(f"spectrogram_inpainting_long: mask {i} must be [F, T_rec], got {tuple(masks[i].shape)}")
+        return files[i].numel(), tuple(masks[i].shape)
+    return _long_groups("spectrogram_inpainting_long", files, seeds, device, key, lambda y, idx, _, sd: sampler.predict_spectrogram_inpainting_long(
+        y, torch.stack([masks[i].float() for i in idx]).to(device), max_batch=max_batch, seeds=sd))
 
 
 # ---- waveform pre-/post-processing of the tester --------------------------------------------------------------------------------

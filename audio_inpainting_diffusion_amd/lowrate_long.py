@@ -9,7 +9,7 @@ sample's whole kernel support.  The grid of restore.py carries over with the req
 
     end' = end + ((L - end) % orig)            so that step = L - end' and with it every window start is a multiple of orig,
 
-and windows, heads, tails and owned ranges are bwe_long.bwe_windows(N, L, end', K), trimmed by m = K - 1 as for a FIR filter of K taps (more
+and windows, heads, tails and owned ranges are restore.trimmed_windows(N, L, end', K), trimmed by m = K - 1 as for a FIR filter of K taps (more
 than one window needs end' >= 2 m).  Every window is a job.  A window's observation row has L + Mw entries, Mw = ceil(new * L / orig): the
 first L on the high-rate side (1 known from the result so far, -1 no direct observation, -2 absent), the rest on the low-rate side (0 observed:
 y = the recording's low-rate sample, -1 unobserved: the kernel support leaves the window although the recording goes on there, -2 absent:
@@ -27,9 +27,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from . import bwe_long
 from . import degrade
 from . import restore
+from .restore import aligned_end
 
 LOWRATE_TYPES = ("resample", "decimate")
 
@@ -86,20 +86,15 @@ def check_length(M: int, length, rate: Rate) -> int:
     return N
 
 
-def aligned_end(L: int, end: int, orig: int) -> int:
-    """end' >= end with (L - end') a multiple of orig"""
-    return int(end) + (int(L) - int(end)) % int(orig)
-
-
 def lowrate_windows(N: int, L: int, end: int, rate: Rate):
-    """(start s, head, tail, lo, hi) of every window, as bwe_long.bwe_windows(N, L, end', K) with the aligned overlap end': every s is a
+    """(start s, head, tail, lo, hi) of every window, as restore.trimmed_windows(N, L, end', K) with the aligned overlap end': every s is a
     multiple of rate.orig."""
-    return bwe_long.bwe_windows(N, L, aligned_end(L, end, rate.orig), rate.K)
+    return restore.trimmed_windows(N, L, aligned_end(L, end, rate.orig), rate.K)
 
 
 def lowrate_plan(R: int, N: int, L: int, end: int, rate: Rate):
     """(jobs_A, jobs_B): every even / odd window of every recording as (r, s, head, tail, lo, hi), ordered by recording and window"""
-    return bwe_long.bwe_plan(R, N, L, aligned_end(L, end, rate.orig), rate.K)
+    return restore.every_window_plan(R, lowrate_windows(N, L, end, rate))
 
 
 def window_len(L: int, rate: Rate) -> int:
@@ -123,31 +118,22 @@ def window_state(N: int, M: int, L: int, rate: Rate, s: int, head: int, tail: in
     return np.concatenate([high, low]).astype(np.float32)
 
 
-_DECIMATE_TABLES = {}
-
-
 def rate_tables(rate: Rate, device):
     """(k [new, K], width, kT [K, new], j_lo [K], j_hi [K]) on ``device``: degrade.resample_tables for "resample"; for "decimate" the one-row
     table [1, 0, ..., 0] of K = f entries, built once per (f, device)."""
     if not rate.decimate:
         return degrade.resample_tables(rate.orig, rate.new, device)
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    tab = _DECIMATE_TABLES.get((rate.orig, device))
-    if tab is None:
+
+    def build(device):
         k = torch.zeros(1, rate.K, dtype=torch.float32)
         k[0, 0] = 1.0
         j_hi = torch.zeros(rate.K, dtype=torch.int32)
         j_hi[0] = 1
-        tab = (k.to(device), 0, k.t().contiguous().to(device), torch.zeros(rate.K, dtype=torch.int32).to(device), j_hi.to(device))
-        if device.type == "cuda":
-            torch.cuda.current_stream(device).synchronize()
-        _DECIMATE_TABLES[(rate.orig, device)] = tab
-    return tab
+        return (k.to(device), 0, k.t().contiguous().to(device), torch.zeros(rate.K, dtype=torch.int32).to(device), j_hi.to(device))
+    return degrade.device_tables(("decimate", rate.orig), device, build)
 
 
-class RateObserved:
+class RateObserved(restore.WindowOperator):
     """Observation of x[B, L] through the resampler of ``tables`` = (k [new, K], width, kT [K, new], j_lo [K], j_hi [K]) on the GPU
     (degrade.resample_tables / rate_tables) with state[1|B, L + Mw] (float32 on the GPU; Mw = ceil(new * L / orig), L is taken from the row
     length).  With kh the first L states, kl the rest, xin = 0 where kh is absent, x elsewhere, and c = resample(xin):
@@ -156,15 +142,12 @@ class RateObserved:
         adjoint(g)     [B, L]: with a = the resampler's adjoint of (g_low where kl == 0, else 0): 0 where kh is absent, a + g_high where known,
                        a elsewhere
 
-    The operator protocol of degrade.py.  It holds per-item rows, so ``shared_mask`` is False; ``rows(lo, hi)`` is the operator of items
-    lo:hi, which is what lets network.denoise_guided run sub-batches of it on concurrent streams.  Linear: it keeps nothing between calls.
-    It changes the length, so there is no data-consistency projection.  With no known or absent sample and every low-rate state 0, the low
-    side of apply and the adjoint of [0 | g] give SincResample's bits."""
-    shared_mask = False
+    The operator protocol of degrade.py over restore.WindowOperator (``rows(lo, hi)``; the tables and a shared state row stay shared).
+    Linear: it keeps nothing between calls.  It changes the length, so there is no data-consistency projection.  With no known or absent
+    sample and every low-rate state 0, the low side of apply and the adjoint of [0 | g] give SincResample's bits."""
 
     def __init__(self, tables, state: torch.Tensor):
-        if not (torch.is_tensor(state) and state.is_cuda and state.dtype == torch.float32 and state.dim() == 2 and (state.stride(1) == 1 or state.shape[1] == 1)):
-            raise _lib.AidError("RateObserved: state must be a float32 GPU tensor [1|B, L + Mw] with contiguous rows (no CPU fallback)")
+        super().__init__(state, "[1|B, L + Mw]")
         k, width, kT, j_lo, j_hi = tables
         ok = all(torch.is_tensor(t) and t.is_cuda and t.is_contiguous() for t in (k, kT, j_lo, j_hi))
         if not (ok and k.dim() == 2 and k.dtype == kT.dtype == torch.float32 and tuple(kT.shape) == (k.shape[1], k.shape[0])
@@ -179,31 +162,18 @@ class RateObserved:
         self.Mw = -(-self.new * self.L // self.orig)
         if self.L < 1 or self.L + self.Mw != row:
             raise _lib.AidError(f"RateObserved: a state row of {row} entries is no L + ceil({self.new} L / {self.orig}) for any L >= 1")
-        self.state = state
-        self._sub = {}
 
-    def rows(self, lo: int, hi: int) -> "RateObserved":
-        """The operator restricted to items lo:hi (views, no copy; the tables and a shared state row stay shared), kept per range."""
-        lo, hi = int(lo), int(hi)
-        rows = self.state.shape[0]
-        if not (0 <= lo < hi and (rows == 1 or hi <= rows)):
-            raise _lib.AidError(f"RateObserved.rows: [{lo}, {hi}) is no range of {rows} items")
-        op = self._sub.get((lo, hi))
-        if op is None:
-            op = self._sub[(lo, hi)] = RateObserved(self.tables, self.state if rows == 1 else self.state[lo:hi])
-        return op
+    def _slice(self, lo: int, hi: int) -> "RateObserved":
+        return RateObserved(self.tables, self._state_rows(lo, hi))
 
     def _run(self, mode, x):
-        x = x.reshape(x.shape[0], -1)
-        B, rows = x.shape[0], self.state.shape[0]
         n_in, n_out = (self.L, self.L + self.Mw) if mode == 0 else (self.L + self.Mw, self.L)
-        if not (x.is_cuda and x.dtype == torch.float32 and x.shape[1] == n_in and B >= 1 and rows in (1, B)):
-            raise _lib.AidError(f"RateObserved: expected a float32 GPU tensor [{'B' if rows == 1 else rows}, {n_in}], got {tuple(x.shape)}")
-        x = x.contiguous()
+        x = self._signal(x, n_in)
+        B = x.shape[0]
         out = torch.empty((B, n_out), dtype=torch.float32, device=x.device)
         k, _, kT, j_lo, j_hi = self.tables
         _lib.call("aid_rate_observed", _lib.RateObservedParams(x.data_ptr(), self.state.data_ptr(), k.data_ptr(), kT.data_ptr(), j_lo.data_ptr(), j_hi.data_ptr(),
-                                                               out.data_ptr(), self.L, self.Mw, n_in, self.state.stride(0) if rows > 1 else 0, n_out,
+                                                               out.data_ptr(), self.L, self.Mw, n_in, self._state_ld, n_out,
                                                                B, mode, self.orig, self.new, self.width, self.K))
         return out
 
@@ -214,12 +184,6 @@ class RateObserved:
     def adjoint(self, g):
         """A^T(g): [B, L + Mw] -> [B, L]"""
         return self._run(1, g)
-
-    def project(self, x, y):
-        return degrade._Operator.project(self, x, y)
-
-    def __call__(self, x):
-        return self.apply(x)
 
 
 def lowrate_gather(rec: torch.Tensor, out: torch.Tensor, jobs: torch.Tensor, L: int, rate: Rate):
@@ -245,16 +209,10 @@ def check_lowrate_args(y: torch.Tensor, factor, filt_type: str, length, L: int, 
     """The refusals of a bandwidth extension of whole low-rate recordings, all raised before anything is launched -> (rate, N).
     What can be judged without a GPU is judged first; the device of y last."""
     rate = rate_of(factor, filt_type)
-    if not (torch.is_tensor(y) and y.dtype == torch.float32 and y.dim() == 2 and y.shape[0] >= 1 and y.shape[1] >= 1 and (y.shape[1] == 1 or y.stride(1) == 1)):
-        raise _lib.AidError(f"y must be float32 low-rate recordings [R, M] with contiguous rows, got {tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
+    restore.check_rows(y, "low-rate recordings [R, M]", nonempty=True)
     N = check_length(y.shape[1], length, rate)
     lowrate_windows(N, L, end, rate)                                       # (end' in [1, L/2); end' >= 2 (K - 1) with more than one window)
-    if max_batch < 1:
-        raise _lib.AidError(f"max_batch must be >= 1, got {max_batch}")
-    if seeds is not None and len(seeds) != y.shape[0]:
-        raise _lib.AidError(f"{len(seeds)} seeds for {y.shape[0]} recordings")
-    if not y.is_cuda:
-        raise _lib.AidError("bandwidth extension of whole low-rate recordings runs on the GPU only (no CPU fallback): y must be a float32 tensor on the GPU")
+    restore.check_batch(y, max_batch, seeds, "bandwidth extension of whole low-rate recordings")
     return rate, N
 
 

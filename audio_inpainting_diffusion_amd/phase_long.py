@@ -8,9 +8,9 @@ multiple of hop is the recording's own frame -- the same n_fft samples times the
 requested overlap end = int(overlap * L) widened to
 
     end' = end + ((L - end) % hop)              so that step = L - end' and with it every window start is a multiple of hop
-                                                (lowrate_long.aligned_end),
+                                                (restore.aligned_end),
 
-and windows, heads, tails and owned ranges are bwe_long.bwe_windows(N, L, end', K = n_fft), trimmed by m = n_fft - 1 as for a FIR filter of
+and windows, heads, tails and owned ranges are restore.trimmed_windows(N, L, end', K = n_fft), trimmed by m = n_fft - 1 as for a FIR filter of
 n_fft taps (more than one window needs end' >= 2 m; always 2 end' < L).  Every window is a job.  A window's observation row has L + F*Tw
 entries, Tw = 1 + L // hop: the first L are samples (1 known from the result so far, -1 no direct observation, -2 absent), the rest is the
 [F, Tw] magnitude block with frames contiguous (STFTMagnitude's layout).  Its state row has L + Tw entries, one per sample and one per frame
@@ -34,10 +34,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from . import bwe_long
+from . import degrade
 from . import phase
 from . import restore
-from .lowrate_long import aligned_end
+from .restore import aligned_end
 
 
 def frames_of(N: int, hop: int) -> int:
@@ -65,14 +65,14 @@ def check_length(T_rec: int, length, hop: int) -> int:
 
 
 def pr_windows(N: int, L: int, end: int, n_fft: int, hop: int):
-    """(start s, head, tail, lo, hi) of every window, as bwe_long.bwe_windows(N, L, end', n_fft) with the aligned overlap end': every s is a
-    multiple of hop."""
-    return bwe_long.bwe_windows(N, L, aligned_end(L, end, hop), n_fft)
+    """(start s, head, tail, lo, hi) of every window, as restore.trimmed_windows(N, L, end', n_fft) with the aligned overlap end': every s
+    is a multiple of hop."""
+    return restore.trimmed_windows(N, L, aligned_end(L, end, hop), n_fft)
 
 
 def pr_plan(R: int, N: int, L: int, end: int, n_fft: int, hop: int):
     """(jobs_A, jobs_B): every even / odd window of every recording as (r, s, head, tail, lo, hi), ordered by recording and window"""
-    return bwe_long.bwe_plan(R, N, L, aligned_end(L, end, hop), n_fft)
+    return restore.every_window_plan(R, pr_windows(N, L, end, n_fft, hop))
 
 
 def window_state(N: int, L: int, n_fft: int, hop: int, s: int, head: int, tail: int) -> np.ndarray:
@@ -89,25 +89,14 @@ def window_state(N: int, L: int, n_fft: int, hop: int, s: int, head: int, tail: 
     return np.concatenate([samples, frames]).astype(np.float32)
 
 
-_TABLES = {}
-
-
 def tables(n_fft: int, device):
     """(window [n_fft], twiddle [n_fft/2, 2]) of phase.hamming_tables as float32 on ``device``, built once per (n_fft, device)"""
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    tab = _TABLES.get((n_fft, device))
-    if tab is None:
-        w, tw = phase.hamming_tables(n_fft)
-        tab = tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device) for a in (w, tw))
-        if device.type == "cuda":
-            torch.cuda.current_stream(device).synchronize()
-        _TABLES[(n_fft, device)] = tab
-    return tab
+    def build(device):
+        return tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device) for a in phase.hamming_tables(n_fft))
+    return degrade.device_tables(("hamming", n_fft), device, build)
 
 
-class STFTMagObserved:
+class STFTMagObserved(restore.WindowOperator):
     """Observation of x[B, L] through the STFT magnitude of phase.STFTMagnitude(win_size, hop_size, L) with state[1|B, L + Tw] (float32 on the
     GPU; Tw = 1 + L // hop, L is taken from the row length).  With kh the first L states, kf the rest, xin = 0 where kh is absent, x
     elsewhere, and M = |STFT(xin)| [F, Tw]:
@@ -116,17 +105,15 @@ class STFTMagObserved:
         adjoint(g)     [B, L]: the VJP at the x_hat of the last apply on the current stream; with a = STFTMagnitude's VJP of the magnitude
                        part of g over the observed frames: 0 where kh is absent, a + g[:L] where known, a elsewhere
 
-    The operator protocol of degrade.py.  It holds per-item rows, so ``shared_mask`` is False; ``rows(lo, hi)`` is the operator of items
-    lo:hi, kept per range, which is what lets network.denoise_guided run sub-batches of it on concurrent streams.  The frame scratch is kept
-    per (B, stream).  It declares NO ``matrix_obs``: the guidance norm is the element-wise norm over the whole row, not predict_pr's induced
-    matrix norm of one segment's spectrogram (see the module docstring).  There is no data-consistency projection.  With every frame observed
-    and no sample known or absent, the magnitude block of apply and the adjoint of [0 | g] give STFTMagnitude's bits."""
-    shared_mask = False
+    The operator protocol of degrade.py over restore.WindowOperator (``rows(lo, hi)``; the tables and a shared state row stay shared; the
+    x_hat per stream and the frame scratch per (B, stream)).  It declares NO ``matrix_obs``: the guidance norm is the element-wise norm over
+    the whole row, not predict_pr's induced matrix norm of one segment's spectrogram (see the module docstring).  There is no
+    data-consistency projection.  With every frame observed and no sample known or absent, the magnitude block of apply and the adjoint of
+    [0 | g] give STFTMagnitude's bits."""
 
     def __init__(self, win_size: int, hop_size: int, state: torch.Tensor):
         self.N, self.hop = phase.check_sizes(win_size, hop_size)
-        if not (torch.is_tensor(state) and state.is_cuda and state.dtype == torch.float32 and state.dim() == 2 and (state.stride(1) == 1 or state.shape[1] == 1)):
-            raise _lib.AidError("STFTMagObserved: state must be a float32 GPU tensor [1|B, L + Tw] with contiguous rows (no CPU fallback)")
+        super().__init__(state, "[1|B, L + Tw]")
         q, m = divmod(state.shape[1] - 1, self.hop + 1)                  # L = q hop + m, m < hop  <=>  L + L // hop = q (hop + 1) + m
         self.L = q * self.hop + m
         if m == self.hop or self.L < 1:
@@ -134,63 +121,35 @@ class STFTMagObserved:
         self.F, self.T = phase.observation_shape(self.N, self.hop, self.L)
         self.row = self.L + self.F * self.T
         self.window, self.twiddle = tables(self.N, state.device)
-        self.state = state
-        self._sub, self._x, self._frames = {}, {}, {}
 
-    def rows(self, lo: int, hi: int) -> "STFTMagObserved":
-        """The operator restricted to items lo:hi (views, no copy; the tables and a shared state row stay shared), kept per range."""
-        lo, hi = int(lo), int(hi)
-        rows = self.state.shape[0]
-        if not (0 <= lo < hi and (rows == 1 or hi <= rows)):
-            raise _lib.AidError(f"STFTMagObserved.rows: [{lo}, {hi}) is no range of {rows} items")
-        op = self._sub.get((lo, hi))
-        if op is None:
-            op = self._sub[(lo, hi)] = STFTMagObserved(self.N, self.hop, self.state if rows == 1 else self.state[lo:hi])
-        return op
+    def _slice(self, lo: int, hi: int) -> "STFTMagObserved":
+        return STFTMagObserved(self.N, self.hop, self._state_rows(lo, hi))
 
     def project(self, x, y):
         raise AttributeError("STFTMagObserved: no data-consistency step exists for phase retrieval (the reference calls a "
                              "data_consistency_step_phase_retrieval it never defines): set tester.data_consistency.use = False")
 
     def _params(self, x, g, frames, out, mode):
-        rows = self.state.shape[0]
         return _lib.StftMagObservedParams(x.data_ptr(), _lib.ptr(g), self.state.data_ptr(), self.window.data_ptr(), self.twiddle.data_ptr(),
-                                          _lib.ptr(frames), out.data_ptr(), self.L, self.L, self.row, self.state.stride(0) if rows > 1 else 0,
+                                          _lib.ptr(frames), out.data_ptr(), self.L, self.L, self.row, self._state_ld,
                                           out.shape[1], x.shape[0], self.N, self.hop, self.T, mode)
-
-    def _check(self, x, n, what):
-        x = x.reshape(x.shape[0], -1)
-        B, rows = x.shape[0], self.state.shape[0]
-        if not (x.is_cuda and x.dtype == torch.float32 and x.shape[1] == n and B >= 1 and rows in (1, B)):
-            raise _lib.AidError(f"STFTMagObserved.{what}: expected a float32 GPU tensor [{'B' if rows == 1 else rows}, {n}], got {tuple(x.shape)}")
-        return x.contiguous()
 
     def apply(self, x):
         """A(x): [B, L] -> [B, L + F*Tw]"""
-        x = self._check(x, self.L, "apply")
+        x = self._signal(x, self.L, ".apply")
         out = torch.empty((x.shape[0], self.row), dtype=torch.float32, device=x.device)
         _lib.call("aid_stft_mag_observed", self._params(x, None, None, out, 0))
-        self._x[torch.cuda.current_stream().cuda_stream] = x
+        self._keep(x)
         return out
 
     def adjoint(self, g):
         """VJP of apply at the x_hat of the last apply on this stream: [B, L + F*Tw] -> [B, L]"""
-        stream = torch.cuda.current_stream().cuda_stream
-        x = self._x.get(stream)
-        if x is None or x.shape[0] != g.shape[0]:
-            raise _lib.AidError("STFTMagObserved.adjoint needs the matching apply on this stream first")
-        g = self._check(g, self.row, "adjoint")
+        x = self._kept(g)
+        g = self._signal(g, self.row, ".adjoint")
         B = g.shape[0]
-        key = (B, stream)                                         # (sub-batches on concurrent streams must not share the frame scratch)
-        fr = self._frames.get(key)
-        if fr is None:
-            fr = self._frames[key] = torch.empty(B, self.T, self.N, device=g.device, dtype=torch.float32)
         out = torch.empty((B, self.L), dtype=torch.float32, device=g.device)
-        _lib.call("aid_stft_mag_observed", self._params(x, g, fr, out, 1))
+        _lib.call("aid_stft_mag_observed", self._params(x, g, self._scratch(B, self.T, self.N, device=g.device), out, 1))
         return out
-
-    def __call__(self, x):
-        return self.apply(x)
 
 
 def pr_gather(rec: torch.Tensor, out: torch.Tensor, jobs: torch.Tensor, L: int, n_fft: int, hop: int):
@@ -226,12 +185,7 @@ def check_pr_args(y: torch.Tensor, win_size, hop_size, length, L: int, end: int,
                             f"got {tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
     N = check_length(y.shape[2], length, hop)
     pr_windows(N, L, end, n_fft, hop)                                      # (end' in [1, L/2); end' >= 2 (n_fft - 1) with more than one window)
-    if isinstance(max_batch, bool) or not isinstance(max_batch, int) or max_batch < 1:
-        raise _lib.AidError(f"max_batch must be an integer >= 1, got {max_batch!r}")
-    if seeds is not None and len(seeds) != y.shape[0]:
-        raise _lib.AidError(f"{len(seeds)} seeds for {y.shape[0]} recordings")
-    if not y.is_cuda:
-        raise _lib.AidError("phase retrieval of whole recordings runs on the GPU only (no CPU fallback): y must be a float32 tensor on the GPU")
+    restore.check_batch(y, max_batch, seeds, "phase retrieval of whole recordings")
     return n_fft, hop, N
 
 

@@ -15,8 +15,12 @@ it.  A window whose owned range has no gap is no job and costs nothing.  Hard co
 autoregressive mode, testing/edm_sampler.py:416).
 
 ``restore_plan`` is host code (the only part that looks at the mask on the host); ``window_gather`` / ``window_scatter`` launch the
-two HIP kernels of csrc/aid_restore.hip; ``restore_passes`` is the pass code, driven with anything that has ``predict_inpainting``;
-``run_passes`` is the loop it shares with the declipping (declip_long.py) and the bandwidth extension (bwe_long.py) of whole recordings.
+two HIP kernels of csrc/aid_restore.hip; ``restore_passes`` is the pass code, driven with anything that has ``predict_inpainting``.
+
+This module is also the one home of what the other whole-recording modes share (declip_long.py, bwe_long.py, lowrate_long.py, phase_long.py,
+spec_long.py; DESIGN.md, "The window scheme of whole recordings"): ``aligned_end`` / ``trimmed_windows`` / ``every_window_plan`` (the grid
+aligned to a period, the ownership trimmed by an operator's reach, every window a job), ``check_rows`` / ``check_batch`` (the refusals
+every mode raises), ``WindowOperator`` (the base of the five window operators) and ``run_passes`` (the pass loop).
 """
 from __future__ import annotations
 
@@ -25,6 +29,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
+from . import degrade
 
 Job = Tuple[int, int, int, int, int, int]            # (recording r, start s, head, tail, lo, hi)
 SEED_STRIDE = 65536                                  # the job of window w of recording r runs with seed seeds[r] * SEED_STRIDE + w
@@ -50,6 +55,52 @@ def restore_windows(N: int, L: int, end: int) -> List[Tuple[int, int, int, int, 
             head, tail, lo, hi = end, end, end, L - end
         wins.append((s, head, tail, lo, min(hi, N - s)))
     return wins
+
+
+def aligned_end(L: int, end: int, period: int) -> int:
+    """end' >= end with (L - end') a multiple of ``period``: every window of the grid then starts at a multiple of it"""
+    return int(end) + (int(L) - int(end)) % int(period)
+
+
+def trimmed_windows(N: int, L: int, end: int, K: int) -> List[Tuple[int, int, int, int, int]]:
+    """(start s, head, tail, lo, hi) of every window of a recording of N samples seen through an operator that reaches K - 1 samples (a
+    filter of K taps); [lo, hi) is the owned range relative to s, cut at N.  The grid is restore_windows'; heads, tails and owned ranges are
+    trimmed by m = K - 1, so that every window owns only samples whose observation it used:
+
+        even w                      [s_w + (m if w else 0), s_w + L - (0 if last else m))
+        odd  w                      [s_w + end - m, s_w + L - end + m)       head = tail = end - m known from the result so far
+        odd last w (no neighbour)   [s_w + end - m, s_w + L)                 head = end - m, tail = 0
+
+    which tiles [0, N) whenever end >= 2 m (required with more than one window)."""
+    K = int(K)
+    if K < 1:
+        raise _lib.AidError(f"trimmed_windows: K = {K} taps must be >= 1")
+    grid = restore_windows(N, L, end)                                      # (N, L >= 1; end in [1, L/2))
+    N, L, end, m, W = int(N), int(L), int(end), K - 1, len(grid)
+    if W > 1 and end < 2 * m:
+        raise _lib.AidError(f"trimmed_windows: the overlap end = {end} must be >= 2 (K - 1) = {2 * m} for a filter of K = {K} taps, so that every "
+                            "sample is observed with its whole filter support in the window that owns it")
+    wins = []
+    for w, (s, *_) in enumerate(grid):
+        last = w == W - 1
+        if w % 2 == 0:
+            head, tail, lo, hi = 0, 0, (m if w else 0), (L if last else L - m)
+        elif last:
+            head, tail, lo, hi = end - m, 0, end - m, L
+        else:
+            head, tail, lo, hi = end - m, end - m, end - m, L - end + m
+        wins.append((s, head, tail, lo, min(hi, N - s)))
+    return wins
+
+
+def every_window_plan(R: int, wins) -> Tuple[List[Job], List[Job]]:
+    """(jobs_A, jobs_B): every even / odd window of ``wins`` for every recording as (r, s, head, tail, lo, hi), ordered by recording and
+    window -- the plan of a degradation that touches all samples, so that every window is a job."""
+    jobs = ([], [])
+    for r in range(int(R)):
+        for w, win in enumerate(wins):
+            jobs[w % 2].append((r,) + win)
+    return jobs
 
 
 def restore_plan(mask: torch.Tensor, L: int, end: int, R: Optional[int] = None) -> Tuple[List[Job], List[Job], int]:
@@ -127,21 +178,105 @@ def window_scatter(x: torch.Tensor, out: torch.Tensor, jobs: torch.Tensor):
 
 
 def check_restore_args(y: torch.Tensor, mask: torch.Tensor, L: int, end: int, max_batch: int, seeds) -> torch.Tensor:
-    """The refusals of a restoration, all raised before anything is launched -> the mask as [1|R, N]."""
-    if not (torch.is_tensor(y) and y.is_cuda and y.dtype == torch.float32):
-        raise _lib.AidError("restoration of whole recordings runs on the GPU only (no CPU fallback): y must be a float32 tensor on the GPU")
+    """The refusals of a restoration, all raised before anything is launched -> the mask as [1|R, N].  What can be judged without a GPU is
+    judged first; the device of y last."""
+    check_rows(y, "recordings [R, N]")
     if mask.dim() == 1:
         mask = mask.reshape(1, -1)
-    if y.dim() != 2 or mask.dim() != 2 or mask.shape[1] != y.shape[1] or mask.shape[0] not in (1, y.shape[0]):
+    if mask.dim() != 2 or mask.shape[1] != y.shape[1] or mask.shape[0] not in (1, y.shape[0]):
         raise _lib.AidError(f"mask {tuple(mask.shape)} does not match recordings {tuple(y.shape)} (y [R, N], mask [1, N] or [R, N])")
-    if y.shape[1] > 1 and y.stride(1) != 1:
-        raise _lib.AidError("the rows of y must be contiguous")
     restore_windows(y.shape[1], L, end)                               # (end in [1, L/2))
-    if max_batch < 1:
-        raise _lib.AidError(f"max_batch must be >= 1, got {max_batch}")
+    check_batch(y, max_batch, seeds, "restoration of whole recordings")
+    return mask
+
+
+def check_rows(y, what: str, nonempty: bool = False) -> None:
+    """The first refusal of a whole-recording mode: y is float32 [R, N] with contiguous rows, on any device (``what`` names it in the text)."""
+    if not (torch.is_tensor(y) and y.dtype == torch.float32 and y.dim() == 2 and (y.shape[1] <= 1 or y.stride(1) == 1)
+            and not (nonempty and 0 in y.shape)):
+        raise _lib.AidError(f"y must be float32 {what} with contiguous rows, got {tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
+
+
+def check_batch(y: torch.Tensor, max_batch, seeds, task: str) -> None:
+    """The last refusals of a whole-recording mode, after the mode's own: max_batch, one seed per recording and, judged last so that a host
+    tensor with any other fault is refused for that fault, the device of y.  All before anything is launched."""
+    if isinstance(max_batch, bool) or not isinstance(max_batch, int) or max_batch < 1:
+        raise _lib.AidError(f"max_batch must be an integer >= 1, got {max_batch!r}")
     if seeds is not None and len(seeds) != y.shape[0]:
         raise _lib.AidError(f"{len(seeds)} seeds for {y.shape[0]} recordings")
-    return mask
+    if not y.is_cuda:
+        raise _lib.AidError(f"{task} runs on the GPU only (no CPU fallback): y must be a float32 tensor on the GPU")
+
+
+class WindowOperator(degrade._Operator):
+    """What the observation operators of a window share (ClipObserved, FIRObserved, RateObserved, STFTMagObserved, SpectralMaskObserved): the
+    operator protocol of degrade.py over a per-sample ``state`` [1|B, row] (float32 on the GPU; aid_rows.h describes the codes).  They hold
+    per-item rows, so ``shared_mask`` is False; ``rows(lo, hi)`` is the operator of items lo:hi, kept per range so that the apply / adjoint
+    pair of a sub-batch meets the same object, which is what lets network.denoise_guided run sub-batches on concurrent streams.  A subclass
+    calls ``__init__`` with its state, says in ``_slice`` how the operator of a slice is built and, where it holds more per item than the
+    state, in ``items_held`` how many items it serves.  What an operator keeps between calls is kept per stream: the x_hat of the last apply
+    (``_keep`` / ``_kept``) and scratch per (B, stream) (``_scratch``)."""
+    shared_mask = False
+
+    def __init__(self, state: torch.Tensor, row: str):
+        if not (torch.is_tensor(state) and state.is_cuda and state.dtype == torch.float32 and state.dim() == 2 and (state.stride(1) == 1 or state.shape[1] == 1)):
+            raise _lib.AidError(f"{type(self).__name__}: state must be a float32 GPU tensor {row} with contiguous rows (no CPU fallback)")
+        self.state = state
+        self._sub, self._x, self._frames = {}, {}, {}
+
+    @property
+    def items_held(self) -> Optional[int]:
+        """the number of items the operator serves; None: any number, through one shared state row"""
+        return None if self.state.shape[0] == 1 else self.state.shape[0]
+
+    @property
+    def _state_ld(self) -> int:
+        return self.state.stride(0) if self.state.shape[0] > 1 else 0
+
+    def _state_rows(self, lo: int, hi: int) -> torch.Tensor:
+        return self.state if self.state.shape[0] == 1 else self.state[lo:hi]
+
+    def rows(self, lo: int, hi: int):
+        """The operator restricted to items lo:hi (views, no copy; tables and a shared state row stay shared), kept per range."""
+        lo, hi, held = int(lo), int(hi), self.items_held
+        if not (0 <= lo < hi and (held is None or hi <= held)):
+            raise _lib.AidError(f"{type(self).__name__}.rows: [{lo}, {hi}) is no range of {'its' if held is None else held} items")
+        op = self._sub.get((lo, hi))
+        if op is None:
+            op = self._sub[(lo, hi)] = self._slice(lo, hi)
+        return op
+
+    def _signal(self, x, n: int, what: str = ""):
+        """x as contiguous [B, n], refused unless it is float32 on the GPU with as many items as the operator holds"""
+        x = x.reshape(x.shape[0], -1)
+        held = self.items_held
+        if not (x.is_cuda and x.dtype == torch.float32 and x.shape[1] == n and x.shape[0] >= 1 and held in (None, x.shape[0])):
+            raise _lib.AidError(f"{type(self).__name__}{what}: expected a float32 GPU tensor [{'B' if held is None else held}, {n}], got {tuple(x.shape)}")
+        return x.contiguous()
+
+    def _observation(self, x, y, n: int):
+        """the y of project(x, y) as contiguous [B, n]"""
+        y = y.reshape(y.shape[0], -1)
+        if not (y.is_cuda and y.dtype == torch.float32 and tuple(y.shape) == (x.shape[0], n)):
+            raise _lib.AidError(f"{type(self).__name__}.project: the observation must be a float32 GPU tensor [{x.shape[0]}, {n}], got {tuple(y.shape)}")
+        return y.contiguous()
+
+    def _keep(self, x):
+        self._x[torch.cuda.current_stream().cuda_stream] = x
+
+    def _kept(self, g):
+        """the x_hat of the last apply on this stream, for the adjoint of ``g``"""
+        x = self._x.get(torch.cuda.current_stream().cuda_stream)
+        if x is None or x.shape[0] != g.shape[0]:
+            raise _lib.AidError(f"{type(self).__name__}.adjoint needs the matching apply on this stream first")
+        return x
+
+    def _scratch(self, B: int, *shape, device):
+        key = (B, torch.cuda.current_stream().cuda_stream)          # (sub-batches on concurrent streams must not share scratch)
+        fr = self._frames.get(key)
+        if fr is None:
+            fr = self._frames[key] = torch.empty(B, *shape, device=device, dtype=torch.float32)
+        return fr
 
 
 def run_passes(sampler, out: torch.Tensor, passes: Sequence[Sequence[Job]], step: int, max_batch: int, seeds, gather, predict) -> None:
@@ -170,8 +305,7 @@ def restore_passes(sampler, y: torch.Tensor, mask: torch.Tensor, L: int, end: in
     mask = check_restore_args(y, mask, L, end, max_batch, seeds)
     R, N = y.shape
     jobs_A, jobs_B, _ = restore_plan(mask, L, end, R)
-    out = torch.empty((R, N), dtype=torch.float32, device=y.device)
-    out.copy_(y)
+    out = y.clone(memory_format=torch.contiguous_format)
     if not (jobs_A or jobs_B):
         return out
     dmask = mask.to(y.device, torch.float32).contiguous()

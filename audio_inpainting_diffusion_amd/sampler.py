@@ -496,6 +496,16 @@ class Sampler:
             self._keep_gens = False
         return out
 
+    def _long_grid(self, who: str, what: str = "restored", consistency: Optional[str] = None):
+        """(L, end) of the window grid of the predict_*_long methods, after the refusals they share: rid, and -- for an operator without a
+        projection, ``consistency`` saying why -- tester.data_consistency in use."""
+        if self.rid:
+            raise _lib.AidError(f"{who} returns the {what} recordings only: rid must be False")
+        if consistency and (self.data_consistency or self.data_consistency_end):
+            raise _lib.AidError(f"{who} runs without data consistency ({consistency}): set tester.data_consistency.use = False")
+        L = int(self.args.exp.audio_len)
+        return L, int(autoregressive_overlap(self.args) * L)
+
     def predict_inpainting_long(self, y, mask, max_batch=8, seeds=None):
         """Restore whole recordings y[R, N] -- N any length, gaps wherever mask[1|R, N] is 0 -> [R, N] on y.device (restore.py).  Windows of
         L = args.exp.audio_len samples on the autoregressive grid (end = int(overlap * L) shared samples, 1 <= end < L/2); the even windows that
@@ -504,10 +514,7 @@ class Sampler:
         chunk.  Windows without a gap cost nothing; samples outside every gap's window stay the recording's.  ``seeds`` [R]: window w of recording
         r runs with seed seeds[r] * 65536 + w, so a recording's result depends neither on the other recordings nor on max_batch."""
         from . import restore
-        if self.rid:
-            raise _lib.AidError("predict_inpainting_long returns the restored recordings only: rid must be False")
-        L = int(self.args.exp.audio_len)
-        end = int(autoregressive_overlap(self.args) * L)
+        L, end = self._long_grid("predict_inpainting_long")
         mask = restore.check_restore_args(y, mask, L, end, max_batch, seeds)
         self._check_model()
         return restore.restore_passes(self, y, mask, L, end, max_batch, seeds)
@@ -521,10 +528,7 @@ class Sampler:
         projection onto the signals consistent with the clipped recording at every evaluation / once on the final state.  Windows without a
         clipped sample cost nothing and keep the recording's samples."""
         from . import declip_long
-        if self.rid:
-            raise _lib.AidError("predict_declipping_long returns the declipped recordings only: rid must be False")
-        L = int(self.args.exp.audio_len)
-        end = int(autoregressive_overlap(self.args) * L)
+        L, end = self._long_grid("predict_declipping_long", "declipped")
         self._check_model()
         return declip_long.declip_passes(self, y, clip_value, L, end, max_batch, seeds)      # (validates its arguments before anything is launched)
 
@@ -539,10 +543,7 @@ class Sampler:
         neighbours restored as known.  tester.data_consistency off / "end" / "always" mean what they mean for predict_bwe.  A recording that
         exists only at a low sample rate ("decimate", "resample") goes through predict_bwe_lowrate_long, whose grid is aligned to the input period."""
         from . import bwe_long
-        if self.rid:
-            raise _lib.AidError("predict_bwe_long returns the restored recordings only: rid must be False")
-        L = int(self.args.exp.audio_len)
-        end = int(autoregressive_overlap(self.args) * L)
+        L, end = self._long_grid("predict_bwe_long")
         bwe_long.check_bwe_args(y, filt, filt_type, L, end, max_batch, seeds)
         self._check_model()
         return bwe_long.bwe_passes(self, y, filt, filt_type, L, end, max_batch, seeds)
@@ -560,13 +561,7 @@ class Sampler:
         Guidance only: an identity ratio, rid and tester.data_consistency in use are refused (the reference's y + x - A(x) is undefined for an
         operator that changes the length)."""
         from . import lowrate_long
-        if self.rid:
-            raise _lib.AidError("predict_bwe_lowrate_long returns the restored recordings only: rid must be False")
-        if self.data_consistency or self.data_consistency_end:
-            raise _lib.AidError("predict_bwe_lowrate_long runs without data consistency (y + x - A(x) is undefined for an operator that changes "
-                                "the length): set tester.data_consistency.use = False")
-        L = int(self.args.exp.audio_len)
-        end = int(autoregressive_overlap(self.args) * L)
+        L, end = self._long_grid("predict_bwe_lowrate_long", consistency="y + x - A(x) is undefined for an operator that changes the length")
         lowrate_long.check_lowrate_args(y, factor, filt_type, length, L, end, max_batch, seeds)
         self._check_model()
         return lowrate_long.lowrate_passes(self, y, factor, filt_type, L, end, length, max_batch, seeds)
@@ -586,16 +581,10 @@ class Sampler:
         an induced matrix norm has no meaning across windows, and known samples do not fit in the matrix.
         Guidance only: xi <= 0, rid and tester.data_consistency in use are refused."""
         from . import phase_long
-        if self.rid:
-            raise _lib.AidError("predict_pr_long returns the restored recordings only: rid must be False")
+        L, end = self._long_grid("predict_pr_long", consistency="no data-consistency step exists for phase retrieval")
         if not self.xi > 0:
             raise _lib.AidError("predict_pr_long needs reconstruction guidance: tester.posterior_sampling.xi must be > 0 (the reference asserts xi > 0)")
-        if self.data_consistency or self.data_consistency_end:
-            raise _lib.AidError("predict_pr_long runs without data consistency (no data-consistency step exists for phase retrieval): "
-                                "set tester.data_consistency.use = False")
         win, hop = phase_retrieval_sizes(self.args)
-        L = int(self.args.exp.audio_len)
-        end = int(autoregressive_overlap(self.args) * L)
         phase_long.check_pr_args(y, win, hop, length, L, end, max_batch, seeds)
         self._check_model()
         return phase_long.pr_passes(self, y, win, hop, L, end, length, max_batch, seeds)
@@ -613,11 +602,8 @@ class Sampler:
         tester.data_consistency off / "end" / "always" mean what they mean for predict_spectrogram_inpainting.  A window other than "hann", a
         hop_length that does not divide n_fft and rid are refused."""
         from . import spec_long
-        if self.rid:
-            raise _lib.AidError("predict_spectrogram_inpainting_long returns the restored recordings only: rid must be False")
+        L, end = self._long_grid("predict_spectrogram_inpainting_long")
         st = self.args.tester.spectrogram_inpainting.stft
-        L = int(self.args.exp.audio_len)
-        end = int(autoregressive_overlap(self.args) * L)
         spec_long.check_spec_args(y, mask, st.n_fft, st.hop_length, st.win_length, st.window, L, end, max_batch, seeds)
         self._check_model()
         return spec_long.spec_passes(self, y, mask, st.n_fft, st.hop_length, L, end, st.win_length, st.window, max_batch, seeds)

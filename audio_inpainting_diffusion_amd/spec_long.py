@@ -10,7 +10,7 @@ over the frames t in [0, T_rec) that cover n (env: the overlap-added squared win
 masked window: within n_fft of a border the recording's frames read samples the window does not hold, and SpectralMask reflect-pads at its
 own ends.  So the grid of restore.py is used with the requested overlap end = int(overlap * L) widened to
 
-    end' = end + ((L - end) % hop)              so that every window start s is a multiple of hop (lowrate_long.aligned_end):
+    end' = end + ((L - end) % hop)              so that every window start s is a multiple of hop (restore.aligned_end):
 
 window frame j is then recording frame s // hop + j, and Tw = 1 + (L + n_fft) // hop covers every frame a window can compute.  Frame t is
 COMPUTABLE in the window when every position it reads, after the two reflections, is either >= N or inside [s, s + L) -- one rule for the
@@ -19,7 +19,7 @@ N % n_fft >= half (its lowest position is Np - half - 1).  A sample of a window 
 known (head / tail, taken from the result so far), 0 observed (every frame of the recording that covers s + i is computable: y = the
 recording's y), -1 unobserved (it exists and feeds frames, but its own y depends on samples outside the window).  At a state-0 sample the
 window operator performs the recording's arithmetic on the recording's numbers; nothing is subtracted or approximated.  Windows, heads, tails
-and owned ranges are bwe_long.bwe_windows(N, L, end', K = 2 n_fft - 1): the reach of A is n_fft - 1 to either side, so ownership is trimmed by
+and owned ranges are restore.trimmed_windows(N, L, end', K = 2 n_fft - 1): the reach of A is n_fft - 1 to either side, so ownership is trimmed by
 m = 2 (n_fft - 1), and more than one window needs end' >= 2 m.
 
 JOBS.  A frame is touched when a bin of its mask column differs from 1; a sample is affected when a touched frame covers it; a window is a job
@@ -38,9 +38,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from . import bwe_long
 from . import restore
-from .lowrate_long import aligned_end
+from .restore import aligned_end
 from .stft import stft_tables
 
 
@@ -70,9 +69,9 @@ def window_frames(L: int, n_fft: int, hop: int) -> int:
 
 
 def spec_windows(N: int, L: int, end: int, n_fft: int, hop: int):
-    """(start s, head, tail, lo, hi) of every window, as bwe_long.bwe_windows(N, L, end', 2 n_fft - 1) with the aligned overlap end': every
-    s is a multiple of hop."""
-    return bwe_long.bwe_windows(N, L, aligned_end(L, end, hop), 2 * int(n_fft) - 1)
+    """(start s, head, tail, lo, hi) of every window, as restore.trimmed_windows(N, L, end', 2 n_fft - 1) with the aligned overlap end':
+    every s is a multiple of hop."""
+    return restore.trimmed_windows(N, L, aligned_end(L, end, hop), 2 * int(n_fft) - 1)
 
 
 def computable(t, N: int, L: int, n_fft: int, hop: int, s: int) -> np.ndarray:
@@ -152,7 +151,7 @@ def spec_tables(N: int, n_fft: int, hop: int, win_length: Optional[int], device)
     return tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device) for a in (w, 1.0 / env, tw))
 
 
-class SpectralMaskObserved:
+class SpectralMaskObserved(restore.WindowOperator):
     """Observation of x[B, L] through the recording's STFT-domain masking operator: mask [1|R, F, T_rec] (float32 on the GPU, unit stride
     along T_rec; read in place), state [B, L + Tw] and items [B, 3] = (r, s, N) as ``spec_gather`` builds them, tables = spec_tables(N, ...).
     With kh the first L states, kf the rest, xin = 0 where kh is absent, x elsewhere, and c = the recording's operator over the frames with
@@ -162,11 +161,9 @@ class SpectralMaskObserved:
         adjoint(g)     with a = the transpose over the same frames of (g where observed, else 0): 0 where absent, a + g where known, a elsewhere
         project(x, y)  y where known, (-c + y) + x where observed (the order of SpectralMask.project), x where unobserved or absent
 
-    The operator protocol of degrade.py.  It holds per-item rows, so ``shared_mask`` is False; ``rows(lo, hi)`` is the operator of items
-    lo:hi, kept per range, which is what lets network.denoise_guided run sub-batches of it on concurrent streams.  The frame scratch is kept
-    per (B, stream).  Linear: it keeps nothing else between calls.  With N = L, s = 0 and every sample observed the three give
-    SpectralMask's bits."""
-    shared_mask = False
+    The operator protocol of degrade.py over restore.WindowOperator (``rows(lo, hi)``; the mask and the tables stay shared; the frame
+    scratch per (B, stream)).  Every item has its own (r, s, N), so the state has one row per item, never a shared one.  Linear: it keeps
+    nothing else between calls.  With N = L, s = 0 and every sample observed the three give SpectralMask's bits."""
 
     def __init__(self, mask: torch.Tensor, n_fft: int, hop: int, state: torch.Tensor, items: torch.Tensor, tables):
         self.N, self.hop = check_sizes(n_fft, hop)
@@ -175,8 +172,7 @@ class SpectralMaskObserved:
                 and mask.shape[2] >= 2 and mask.stride(2) == 1 and (mask.shape[2] - 1) * self.hop % self.N == 0):
             raise _lib.AidError(f"SpectralMaskObserved: mask must be a float32 GPU tensor [1|R, {self.F}, T_rec] with unit stride along T_rec and "
                                 "(T_rec - 1) hop a multiple of n_fft (no CPU fallback)")
-        if not (torch.is_tensor(state) and state.is_cuda and state.dtype == torch.float32 and state.dim() == 2 and state.stride(1) == 1):
-            raise _lib.AidError("SpectralMaskObserved: state must be a float32 GPU tensor [B, L + Tw] with contiguous rows")
+        super().__init__(state, "[B, L + Tw]")
         self.T_rec = mask.shape[2]
         self.Np = (self.T_rec - 1) * self.hop
         q, m = divmod(state.shape[1] - 1 - self.N // self.hop, self.hop + 1)     # L = q hop + m, m < hop  <=>  L + (L + n_fft) // hop = q (hop + 1) + m + n_fft / hop
@@ -191,30 +187,19 @@ class SpectralMaskObserved:
         self.window, self.inv_env, self.twiddle = tables
         if self.window.numel() != self.N or self.inv_env.numel() != self.Np:
             raise _lib.AidError(f"SpectralMaskObserved: the tables are not those of n_fft = {self.N} and a padded length of {self.Np} (spec_tables)")
-        self.mask, self.state, self.items, self.tables = mask, state, items, tables
-        self._sub, self._frames = {}, {}
+        self.mask, self.items, self.tables = mask, items, tables
 
-    def rows(self, lo: int, hi: int) -> "SpectralMaskObserved":
-        """The operator restricted to items lo:hi (views, no copy; the mask and the tables stay shared), kept per range."""
-        lo, hi = int(lo), int(hi)
-        rows = self.state.shape[0]
-        if not 0 <= lo < hi <= rows:
-            raise _lib.AidError(f"SpectralMaskObserved.rows: [{lo}, {hi}) is no range of {rows} items")
-        op = self._sub.get((lo, hi))
-        if op is None:
-            op = self._sub[(lo, hi)] = SpectralMaskObserved(self.mask, self.N, self.hop, self.state[lo:hi], self.items[lo:hi], self.tables)
-        return op
+    @property
+    def items_held(self) -> int:
+        return self.state.shape[0]
+
+    def _slice(self, lo: int, hi: int) -> "SpectralMaskObserved":
+        return SpectralMaskObserved(self.mask, self.N, self.hop, self.state[lo:hi], self.items[lo:hi], self.tables)
 
     def _run(self, mode, x, y=None):
-        x = x.reshape(x.shape[0], -1)
+        x = self._signal(x, self.L)
         B, L = x.shape[0], self.L
-        if not (x.is_cuda and x.dtype == torch.float32 and x.shape[1] == L and B == self.state.shape[0]):
-            raise _lib.AidError(f"SpectralMaskObserved: expected a float32 GPU tensor [{self.state.shape[0]}, {L}], got {tuple(x.shape)}")
-        x = x.contiguous()
-        key = (B, torch.cuda.current_stream().cuda_stream)          # (sub-batches on concurrent streams must not share the frame scratch)
-        fr = self._frames.get(key)
-        if fr is None:
-            fr = self._frames[key] = torch.empty(B, self.Tw, self.N, device=x.device, dtype=torch.float32)
+        fr = self._scratch(B, self.Tw, self.N, device=x.device)
         out = torch.empty_like(x)
         m = self.mask
         _lib.call("aid_stft_mask_observed", _lib.StftMaskObservedParams(
@@ -230,13 +215,7 @@ class SpectralMaskObserved:
         return self._run(1, g)
 
     def project(self, x, y):
-        y = y.reshape(y.shape[0], -1)
-        if not (y.is_cuda and y.dtype == torch.float32 and tuple(y.shape) == (x.shape[0], self.L)):
-            raise _lib.AidError(f"SpectralMaskObserved.project: the observation must be a float32 GPU tensor [{x.shape[0]}, {self.L}], got {tuple(y.shape)}")
-        return self._run(2, x, y=y.contiguous())
-
-    def __call__(self, x):
-        return self.apply(x)
+        return self._run(2, x, y=self._observation(x, y, self.L))
 
 
 def spec_gather(rec: torch.Tensor, out: torch.Tensor, jobs: torch.Tensor, L: int, n_fft: int, hop: int):
@@ -269,8 +248,7 @@ def check_spec_args(y: torch.Tensor, mask: torch.Tensor, n_fft, hop, win_length,
     n_fft, hop = check_sizes(n_fft, hop)
     if win_length is not None and (isinstance(win_length, bool) or not isinstance(win_length, int) or not 1 <= win_length <= n_fft):
         raise _lib.AidError(f"win_length must be an integer in [1, n_fft = {n_fft}], got {win_length!r}")
-    if not (torch.is_tensor(y) and y.dtype == torch.float32 and y.dim() == 2 and y.shape[0] >= 1 and y.shape[1] >= 1 and (y.shape[1] <= 1 or y.stride(1) == 1)):
-        raise _lib.AidError(f"y must be float32 recordings [R, N] with contiguous rows, got {tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
+    restore.check_rows(y, "recordings [R, N]", nonempty=True)
     R, N = y.shape
     F, T_rec = n_fft // 2 + 1, rec_frames(N, n_fft, hop)
     if torch.is_tensor(mask) and mask.dim() == 2:
@@ -280,12 +258,7 @@ def check_spec_args(y: torch.Tensor, mask: torch.Tensor, n_fft, hop, win_length,
                             f"T_rec = 1 + Np // hop_length with Np = {padded_length(N, n_fft)}: masks.spectral_mask(audio_len = {N})), "
                             f"got {tuple(mask.shape) if torch.is_tensor(mask) else type(mask).__name__}")
     spec_windows(N, L, end, n_fft, hop)                                    # (end' in [1, L/2); end' >= 4 (n_fft - 1) with more than one window)
-    if isinstance(max_batch, bool) or not isinstance(max_batch, int) or max_batch < 1:
-        raise _lib.AidError(f"max_batch must be an integer >= 1, got {max_batch!r}")
-    if seeds is not None and len(seeds) != R:
-        raise _lib.AidError(f"{len(seeds)} seeds for {R} recordings")
-    if not y.is_cuda:
-        raise _lib.AidError("spectrogram inpainting of whole recordings runs on the GPU only (no CPU fallback): y must be a float32 tensor on the GPU")
+    restore.check_batch(y, max_batch, seeds, "spectrogram inpainting of whole recordings")
     return n_fft, hop, mask
 
 
@@ -303,8 +276,7 @@ def spec_passes(sampler, y: torch.Tensor, mask: torch.Tensor, n_fft, hop, L: int
         dmask = dmask.contiguous()                                         # (one copy per call, never one per window)
     touched = touched_frames(dmask).cpu().numpy()                          # [1|R, T_rec]: reduced on the GPU; the one read-back, before pass A
     jobs_A, jobs_B = spec_plan(touched, R, N, L, end, n_fft, hop)
-    out = torch.empty((R, N), dtype=torch.float32, device=y.device)
-    out.copy_(y)
+    out = y.clone(memory_format=torch.contiguous_format)
     if not (jobs_A or jobs_B):
         return out
     tables = spec_tables(N, n_fft, hop, win_length, y.device)

@@ -277,7 +277,7 @@ class _Stub:
 @pytest.mark.parametrize("N,L,end,n_fft,hop", GATHER_CASES)
 @pytest.mark.parametrize("max_batch", [2, 8])
 def test_two_passes_stitch_the_stub_sampler_output(N, L, end, n_fft, hop, max_batch):
-    from audio_inpainting_diffusion_amd.lowrate_long import aligned_end
+    from audio_inpainting_diffusion_amd.restore import aligned_end
     from audio_inpainting_diffusion_amd.phase_long import default_length, frames_of, pr_passes, pr_plan
     R, F, T_rec = 3, n_fft // 2 + 1, frames_of(N, hop)
     end2 = aligned_end(L, end, hop)
@@ -420,7 +420,7 @@ def test_hip_network_pass_a_and_pass_b_shaped_windows_vs_oracle(norm):
     tests/test_gpu_phase.py::test_hip_network_predict_pr_vs_oracle; every other observed frame holds signal.  Bound: the documented 5e-4 of that
     test.
     Measured on one MI355X: rel-L2 = 4.47e-06 (norm 2) and 4.35e-06 ("smoothl1")."""
-    from audio_inpainting_diffusion_amd.lowrate_long import aligned_end
+    from audio_inpainting_diffusion_amd.restore import aligned_end
     from audio_inpainting_diffusion_amd.phase_long import STFTMagObserved
     from audio_inpainting_diffusion_amd.sampler import autoregressive_overlap
     smp, osmp, Ls = _small_net_pr()

@@ -294,7 +294,7 @@ class _Stub:
 def test_two_passes_stitch_the_stub_sampler_output_and_leave_the_rest_of_the_recording(N, L, end, n_fft, hop, max_batch):
     """Recording 0 has a rectangle over the border of windows 1 and 2 (a job in each pass), recording 1 one inside window 0, recording 2 none.
     Every owned sample of a job comes from its window; every other sample stays y."""
-    from audio_inpainting_diffusion_amd.lowrate_long import aligned_end
+    from audio_inpainting_diffusion_amd.restore import aligned_end
     from audio_inpainting_diffusion_amd.spec_long import rec_frames, spec_passes, spec_plan, spec_windows, touched_frames
     R, T_rec = 3, rec_frames(N, n_fft, hop)
     end2 = aligned_end(L, end, hop)

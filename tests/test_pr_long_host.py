@@ -65,7 +65,7 @@ def test_phase_long_exports_every_declared_symbol_and_shares_none():
 @pytest.mark.parametrize("N,L,end,n_fft,hop", PR_CASES)
 def test_window_starts_are_multiples_of_hop_and_owned_ranges_tile_the_recording(N, L, end, n_fft, hop):
     from audio_inpainting_diffusion_amd.bwe_long import bwe_windows
-    from audio_inpainting_diffusion_amd.lowrate_long import aligned_end
+    from audio_inpainting_diffusion_amd.restore import aligned_end
     from audio_inpainting_diffusion_amd.phase_long import frames_of, pr_plan, pr_windows, window_state
     end2 = aligned_end(L, end, hop)
     assert end2 == end + ((L - end) % hop) and end <= end2 < end + hop and (L - end2) % hop == 0

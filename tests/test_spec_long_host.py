@@ -202,7 +202,7 @@ def _brute_state(N, L, n_fft, hop, s, head, tail):
 @pytest.mark.parametrize("N,L,end,n_fft,hop", SPEC_CASES + TAIL_CASES)
 def test_window_state_is_the_brute_force_rule_and_owned_ranges_tile_the_recording_in_state_0(N, L, end, n_fft, hop):
     from audio_inpainting_diffusion_amd.bwe_long import bwe_windows
-    from audio_inpainting_diffusion_amd.lowrate_long import aligned_end
+    from audio_inpainting_diffusion_amd.restore import aligned_end
     from audio_inpainting_diffusion_amd.spec_long import padded_length, rec_frames, spec_windows, window_frames, window_state
     end2 = aligned_end(L, end, hop)
     Np, T_rec, Tw = padded_length(N, n_fft), rec_frames(N, n_fft, hop), window_frames(L, n_fft, hop)
@@ -343,7 +343,7 @@ def test_an_unaffected_sample_of_the_masked_recording_is_the_signal():
 # ---- the pass loop: seeds ----------------------------------------------------------------------------------------------------------------
 def test_the_seed_rule_of_run_passes_holds_with_the_aligned_step(monkeypatch):
     from audio_inpainting_diffusion_amd import restore, spec_long
-    from audio_inpainting_diffusion_amd.lowrate_long import aligned_end
+    from audio_inpainting_diffusion_amd.restore import aligned_end
     N, L, end, n_fft, hop = 5000, 1200, 300, 64, 16
     step = L - aligned_end(L, end, hop)
     wins = spec_long.spec_windows(N, L, end, n_fft, hop)

@@ -32,7 +32,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r17_bwe_lowrate_long_bench.json"))
     a = ap.parse_args()
     import torch
-    from audio_inpainting_diffusion_amd import lowrate_long
+    from audio_inpainting_diffusion_amd import lowrate_long, restore
     from audio_inpainting_diffusion_amd.config import make_args
     from audio_inpainting_diffusion_amd.degrade import resample_poly
     from audio_inpainting_diffusion_amd.edm import EDM
@@ -111,7 +111,7 @@ def main():
         outside = [r["wall_s"] - sum(r["call_s"]) for r in runs]
         rel_a, rel_b = max(pa) / max(ref), max(pb) / max(ref)
         return {"factor": factor, "ratio": f"{rate.orig}:{rate.new}", "kernel_taps": rate.K, "low_rate_samples_per_recording": M, "window_row": L + Mw,
-                "overlap_samples": lowrate_long.aligned_end(L, end, rate.orig), "windows_per_recording": (len(jobs_A) + len(jobs_B)) // R,
+                "overlap_samples": restore.aligned_end(L, end, rate.orig), "windows_per_recording": (len(jobs_A) + len(jobs_B)) // R,
                 "jobs_pass_A": len(jobs_A), "jobs_pass_B": len(jobs_B), "pass_batches": runs[0]["call_batch"],
                 "chunk_evals_per_s": [r2([b * per_item / c for b, c in zip(r["call_batch"], r["call_s"])]) for r in runs],
                 "bwe_first_complete_run": round(first["evals"] / first["call_s"][0], 2), "bwe_complete_run": r2(ref), "bwe_spread": round(spread, 4),

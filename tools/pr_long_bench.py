@@ -35,7 +35,7 @@ def main():
     from audio_inpainting_diffusion_amd.config import make_args
     from audio_inpainting_diffusion_amd.edm import EDM
     from audio_inpainting_diffusion_amd.init import seeded_init_, seeded_normal
-    from audio_inpainting_diffusion_amd.lowrate_long import aligned_end
+    from audio_inpainting_diffusion_amd.restore import aligned_end
     from audio_inpainting_diffusion_amd.network import Unet_CQT_oct_with_attention
     from audio_inpainting_diffusion_amd.phase import STFTMagnitude
     from audio_inpainting_diffusion_amd.sampler import Sampler, autoregressive_overlap, phase_retrieval_sizes
