@@ -5,6 +5,7 @@
 #include <utility>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));      // the accumulator of one 32 x 32 MFMA tile
+typedef float f32x4 __attribute__((ext_vector_type(4)));        // the accumulator of one 16 x 16 MFMA tile: lane l holds rows 4 (l / 16) + r, column l % 16
 
 // 16-byte direct-to-LDS load through the compiler builtin: the compiler tracks it and places the waits.
 #define AID_GLDS16(gptr, lptr) \

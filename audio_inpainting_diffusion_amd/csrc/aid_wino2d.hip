@@ -38,18 +38,27 @@ struct W2dGemmDev {
     int nchunks, ntn, ntm, ntiles, per_xcd;
 };
 
-template <int MT_, int NT_, int WGM_, int WGN_, int KC_, int NBUF_>
+// FR: the MFMA fragment -- 32: v_mfma_f32_32x32x2_f32 (16 accumulator registers, K = 2 per instruction, lane half h holds k = h); 16: v_mfma_f32_16x16x4_f32
+// (4 registers, K = 4, lane quarter q holds k = q; 32 cycles of issue instead of 64 at the same FLOP rate: more independent chains per accumulator register)
+template <int FR> struct W2dAcc;
+template <> struct W2dAcc<32> { typedef f32x16 type; };
+template <> struct W2dAcc<16> { typedef f32x4 type; };
+template <int MT_, int NT_, int WGM_, int WGN_, int KC_, int NBUF_, int FR_ = 32>
 struct W2dGemmShape {
-    static constexpr int MT = MT_, NT = NT_, WGM = WGM_, WGN = WGN_, KC = KC_, NBUF = NBUF_;
+    static constexpr int MT = MT_, NT = NT_, WGM = WGM_, WGN = WGN_, KC = KC_, NBUF = NBUF_, FR = FR_;
+    typedef typename W2dAcc<FR>::type Acc;
+    static constexpr int AR = FR == 32 ? 16 : 4, KS = FR == 32 ? 2 : 4;      // accumulator registers of a fragment; K per MFMA
     static constexpr int NW = WGM * WGN;
-    static constexpr int M_BLK = 32 * MT * WGM, N_BLK = 32 * NT * WGN;
+    static constexpr int M_BLK = FR * MT * WGM, N_BLK = FR * NT * WGN;
     static constexpr int XSZ = KC * N_BLK, WSZ = KC * M_BLK, BUFSZ = XSZ + WSZ;
     static constexpr int NXP = XSZ / 256, NWP = WSZ / 256, NP = NXP + NWP;
     static constexpr int PPW = (NP + NW - 1) / NW;
-    static constexpr int NSTEP = KC / 2;
+    static constexpr int NSTEP = KC / KS;
     static constexpr int AHEAD = NBUF - 1;                     // chunks in flight ahead of the one being multiplied
     static constexpr int LDS = NBUF * BUFSZ;
-    static_assert(XSZ % 256 == 0 && WSZ % 256 == 0 && NP % NW == 0, "whole 1-KiB pieces, the same number for every wave");
+    // whole 1-KiB pieces, PPW for every wave (the vmcnt waits count them): where NW does not divide NP the last waves load the LAST piece once more -- the same
+    // bytes to the same LDS addresses (w2d_piece_offsets)
+    static_assert(XSZ % 256 == 0 && WSZ % 256 == 0 && KC % KS == 0, "whole 1-KiB pieces, whole k-steps");
 };
 
 template <int N> struct W2dVec;
@@ -64,7 +73,7 @@ __device__ __forceinline__ float w2d_get(const float2& v, int i) { return i ? v.
 __device__ __forceinline__ float w2d_get(const float4& v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : (i == 2 ? v.z : v.w)); }
 
 // ---- the pieces the three kernels share ---------------------------------------------------------------------------------------------
-struct W2dWave { int lane, wave, wm, wn, half; };          // wave (wm, wn) of the WGM x WGN workgroup; half = which 32 lanes
+struct W2dWave { int lane, wave, wm, wn, half; };          // wave (wm, wn) of the WGM x WGN workgroup; half = which group of FR lanes (the k index of its fragments)
 template <class S>
 __device__ __forceinline__ W2dWave w2d_wave_of() {
     W2dWave w;
@@ -72,7 +81,7 @@ __device__ __forceinline__ W2dWave w2d_wave_of() {
     w.lane = tid & 63;
     w.wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     w.wm = w.wave / S::WGN; w.wn = w.wave % S::WGN;
-    w.half = w.lane >> 5;
+    w.half = w.lane / S::FR;
     return w;
 }
 
@@ -100,7 +109,8 @@ template <class S, bool CLAMP_M>
 __device__ __forceinline__ void w2d_piece_offsets(const W2dGemmDev& a, const int wave, const int lane, const int m0, const int n0, unsigned (&poff)[S::PPW], int (&plds)[S::PPW]) {
 #pragma unroll
     for (int i = 0; i < S::PPW; ++i) {
-        const int pc = wave + i * S::NW;
+        int pc = wave + i * S::NW;
+        if constexpr (S::NP % S::NW != 0) pc = min(pc, S::NP - 1);          // (the duplicate load of the last piece)
         plds[i] = pc * 256;
         if (pc < S::NXP) {
             const int e = pc * 256 + 4 * lane;
@@ -127,31 +137,31 @@ __device__ __forceinline__ void w2d_issue_piece(const unsigned (&poff)[S::PPW], 
 // float offsets within a buffer of this lane's B / A fragment row k = kh * half
 template <class S>
 __device__ __forceinline__ void w2d_frag_base(const W2dWave& w, int kh, int& vA, int& vB) {
-    vB = kh * w.half * S::N_BLK + w.wn * (32 * S::NT) + S::NT * (w.lane & 31);
-    vA = S::XSZ + kh * w.half * S::M_BLK + w.wm * (32 * S::MT) + S::MT * (w.lane & 31);
+    vB = kh * w.half * S::N_BLK + w.wn * (S::FR * S::NT) + S::NT * (w.lane % S::FR);
+    vA = S::XSZ + kh * w.half * S::M_BLK + w.wm * (S::FR * S::MT) + S::MT * (w.lane % S::FR);
 }
 
-template <int MT, int NT>
-__device__ __forceinline__ void w2d_zero(f32x16 (&acc)[MT][NT]) {
+template <class Acc, int MT, int NT>
+__device__ __forceinline__ void w2d_zero(Acc (&acc)[MT][NT]) {
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int j = 0; j < NT; ++j)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+            for (int r = 0; r < (int)(sizeof(Acc) / sizeof(float)); ++r) acc[i][j][r] = 0.f;
 }
 
 // the fp32 k-steps of one chunk in buffer Bf: fragment loads one step ahead, MFMAs, and -- while `more` -- the pieces of a later chunk, one group per
 // k-step (issue(ic) issues piece ic of it)
 template <class S, class Issue>
-__device__ __forceinline__ void w2d_ksteps(const float* Bf, int vA, int vB, f32x16 (&acc)[S::MT][S::NT], bool more, Issue&& issue) {
+__device__ __forceinline__ void w2d_ksteps(const float* Bf, int vA, int vB, typename S::Acc (&acc)[S::MT][S::NT], bool more, Issue&& issue) {
     constexpr int NSTEP = S::NSTEP;
     constexpr int ISTEPS = NSTEP < S::PPW ? NSTEP : S::PPW;          // k-steps of a chunk in which the pieces of a later chunk are issued
     typename W2dVec<S::NT>::type bv[2];
     typename W2dVec<S::MT>::type av[2];
     auto load_step = [&](int s, int q) {
-        bv[q] = *reinterpret_cast<const typename W2dVec<S::NT>::type*>(Bf + vB + 2 * s * S::N_BLK);
-        av[q] = *reinterpret_cast<const typename W2dVec<S::MT>::type*>(Bf + vA + 2 * s * S::M_BLK);
+        bv[q] = *reinterpret_cast<const typename W2dVec<S::NT>::type*>(Bf + vB + S::KS * s * S::N_BLK);
+        av[q] = *reinterpret_cast<const typename W2dVec<S::MT>::type*>(Bf + vA + S::KS * s * S::M_BLK);
     };
     load_step(0, 0);
     aid_static_for<NSTEP>([&](auto sc) {
@@ -165,7 +175,8 @@ __device__ __forceinline__ void w2d_ksteps(const float* Bf, int vA, int vB, f32x
         for (int i = 0; i < S::MT; ++i)
 #pragma unroll
             for (int j = 0; j < S::NT; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(w2d_get(av[q], i), w2d_get(bv[q], j), acc[i][j], 0, 0, 0);
+                if constexpr (S::FR == 32) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(w2d_get(av[q], i), w2d_get(bv[q], j), acc[i][j], 0, 0, 0);
+                else acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(w2d_get(av[q], i), w2d_get(bv[q], j), acc[i][j], 0, 0, 0);
     });
 }
 
@@ -190,15 +201,15 @@ __device__ __forceinline__ void w2d_for_chunks(int nct, Chunk&& chunk) {
         aid_static_for<NBUF>([&](auto qc) { if (ch + decltype(qc)::value < nct) chunk(qc, ch + decltype(qc)::value); });
 }
 
-// epilogue: the MT x 16 rows of this lane, NT consecutive columns per row, into the plane at cb (already at the lane's first column n < N)
+// epilogue: the MT x AR rows of this lane, NT consecutive columns per row, into the plane at cb (already at the lane's first column n < N)
 template <class S>
-__device__ __forceinline__ void w2d_store_tile(const W2dGemmDev& a, const W2dWave& w, const W2dTile& t, float* cb, const f32x16 (&acc)[S::MT][S::NT]) {
+__device__ __forceinline__ void w2d_store_tile(const W2dGemmDev& a, const W2dWave& w, const W2dTile& t, float* cb, const typename S::Acc (&acc)[S::MT][S::NT]) {
     constexpr int MT = S::MT, NT = S::NT;
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int m = t.m0 + w.wm * (32 * MT) + MT * (4 * w.half + (r & 3) + 8 * (r >> 2)) + i;
+        for (int r = 0; r < S::AR; ++r) {
+            const int m = t.m0 + w.wm * (S::FR * MT) + MT * (4 * w.half + (r & 3) + 8 * (r >> 2)) + i;          // (fragment row: 32 x 32 -- 8 (r / 4) + 4 half + r % 4; 16 x 16 -- 4 quarter + r)
             if (m >= a.Cout) continue;
             float* q = cb + (int64_t)m * a.N;
             if constexpr (NT == 4) *reinterpret_cast<float4*>(q) = make_float4(acc[i][0][r], acc[i][1][r], acc[i][2][r], acc[i][3][r]);
@@ -365,14 +376,17 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WPC * WGM * WGN + 3) / 4) void w2d
 // c % nch of plane c / nch); when a plane's K loop ends its accumulators are folded into the four output-row accumulators with the column of AF^T
 // (Y[j] += AF^T[j][xf] * acc) and cleared.  It writes M'[j * NTP + xt][co][n], 4 NTP planes instead of 8 NTP: the GEMM's writes and the output
 // pass's reads of M halve (these launches sit below the fp32 ridge at 24-32 FLOP/B), the output pass keeps only its T transform.
-// Five accumulator sets per tile: 64-column tiles (one 32 x 32 fragment column pair per wave), two workgroups per CU.
+// Five accumulator sets per tile: 64-column tiles (one 32 x 32 fragment column pair per wave), two workgroups per CU; the 96-channel panels take 16 x 16 fragments
+// (FR = 16: four waves x 3 x 2 fragments on the 96 x 64 tile, a quarter of the accumulator registers per fragment), three workgroups per CU (w2d_gemm_of).
 // =====================================================================================================================================
 __constant__ float w2d_atf[8][4] = {{1.f, 0.f, 0.f, 0.f}, {1.f, 1.f, 1.f, 1.f}, {1.f, -1.f, 1.f, -1.f}, {1.f, 2.f, 4.f, 8.f}, {1.f, -2.f, 4.f, -8.f},
                                     {1.f, 0.5f, 0.25f, 0.125f}, {1.f, -0.5f, 0.25f, -0.125f}, {0.f, 0.f, 0.f, 1.f}};      // [xf][j] = AF^T[j][xf] (aid_wino45.h)
 
-template <int MT, int NT, int WGM, int WGN, int KC, int NBUF, int WPC>
+template <int MT, int NT, int WGM, int WGN, int KC, int NBUF, int WPC, int FR = 32>
 __global__ __launch_bounds__(64 * WGM * WGN, (WPC * WGM * WGN + 3) / 4) void w2d_gemm_fold_kernel(const W2dGemmDev a, const int ntp) {
-    using S = W2dGemmShape<MT, NT, WGM, WGN, KC, NBUF>;
+    using S = W2dGemmShape<MT, NT, WGM, WGN, KC, NBUF, FR>;
+    using Acc = typename S::Acc;
+    constexpr int AR = S::AR;
     constexpr int BUFSZ = S::BUFSZ, PPW = S::PPW, AHEAD = S::AHEAD;
     __shared__ __attribute__((aligned(16))) float smem[S::LDS];
     const W2dWave w = w2d_wave_of<S>();
@@ -390,8 +404,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WPC * WGM * WGN + 3) / 4) void w2d
     const char* const wbase = reinterpret_cast<const char*>(a.U + (int64_t)xt * a.Cin_pad * a.Cout_pad);
     int vA, vB;
     w2d_frag_base<S>(w, 1, vA, vB);
-    f32x16 acc[MT][NT];
-    f32x16 Y[4][MT][NT];
+    Acc acc[MT][NT];
+    Acc Y[4][MT][NT];
     w2d_zero(acc); w2d_zero(Y[0]); w2d_zero(Y[1]); w2d_zero(Y[2]); w2d_zero(Y[3]);
 
     auto src_of = [&](int c, const char*& xs, const char*& ws) {      // (scalar) sources of stream chunk c
@@ -426,7 +440,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WPC * WGM * WGN + 3) / 4) void w2d
 #pragma unroll
                 for (int j = 0; j < NT; ++j)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) {
+                    for (int r = 0; r < AR; ++r) {
                         const float v = acc[i][j][r];
                         Y[0][i][j][r] += c0 * v; Y[1][i][j][r] += c1 * v; Y[2][i][j][r] += c2 * v; Y[3][i][j][r] += c3 * v;
                         acc[i][j][r] = 0.f;
@@ -435,7 +449,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WPC * WGM * WGN + 3) / 4) void w2d
     });
 
     // ---- epilogue: the four output-row planes j * ntp + xt ---------------------------------------------------------------------------------
-    const int n = t.n0 + w.wn * (32 * NT) + NT * (w.lane & 31);
+    const int n = t.n0 + w.wn * (FR * NT) + NT * (w.lane % FR);
     if (n >= a.N) return;
 #pragma unroll
     for (int jr = 0; jr < 4; ++jr) w2d_store_tile<S>(a, w, t, a.Mo + (int64_t)(jr * ntp + xt) * a.Cout * a.N + n, Y[jr]);
@@ -477,9 +491,9 @@ template <int MT, int NT, int WGM, int WGN, int NBUF, int WPC>
 static int w2d_launch_gemm_s6(const aid_wino2d_gemm_params* p, hipStream_t st, const char* name) {
     return w2d_launch<W2dGemmShape<MT, NT, WGM, WGN, 16, NBUF>, false>(w2d_gemm_s6_kernel<MT, NT, WGM, WGN, NBUF, WPC>, p, p->nxi, st, name);
 }
-template <int MT, int NT, int WGM, int WGN, int KC, int NBUF, int WPC>
+template <int MT, int NT, int WGM, int WGN, int KC, int NBUF, int WPC, int FR = 32>
 static int w2d_launch_gemm_fold(const aid_wino2d_gemm_params* p, int ntp, hipStream_t st, const char* name) {
-    return w2d_launch<W2dGemmShape<MT, NT, WGM, WGN, KC, NBUF>, true>(w2d_gemm_fold_kernel<MT, NT, WGM, WGN, KC, NBUF, WPC>, p, ntp, st, name);
+    return w2d_launch<W2dGemmShape<MT, NT, WGM, WGN, KC, NBUF, FR>, true>(w2d_gemm_fold_kernel<MT, NT, WGM, WGN, KC, NBUF, WPC, FR>, p, ntp, st, name);
 }
 
 // the split-precision variant as a process-wide switch of aid_conv2d(x_wino = 3) (0: the fp32-MFMA product kernel; 6: the six-product bf16 split): set
@@ -974,6 +988,12 @@ extern "C" int aid_conv2d_wino2d_tform(int B, int Cin, int Cout, int F, int T, i
 #ifndef W2D_FOLD96_NBUF
 #define W2D_FOLD96_NBUF 3
 #endif
+#ifndef W2D_FOLD96_FR          // 16: the 96 x 64 tile on FOUR waves x (48 x 32) of 16 x 16 x 4 MFMAs; 32: on three waves x (32 x 64) of 32 x 32 x 2
+#define W2D_FOLD96_FR 16
+#endif
+#ifndef W2D_FOLD96_WPC         // workgroups per CU of the four-wave 96 x 64 instance
+#define W2D_FOLD96_WPC 3
+#endif
 #define W2D_STR2(x) #x
 #define W2D_STR(x) W2D_STR2(x)
 static_assert(!(W2D_GP8_TWO > 0 && W2D_FOLD_M), "W2D_GP8_TWO and W2D_FOLD_M: the folded output pass takes one group per thread (build the two-group experiment with -DW2D_FOLD_M=0)");
@@ -1028,9 +1048,22 @@ static int w2d_gemm_of(const aid_conv2d_params* p, const W2dPlan& pl, hipStream_
         // (276 -> 264 us against chunks of 16: half the barriers; more buffers of 16 measured nothing, the loads are not what it waits for); 96-channel panels on THREE
         // waves with K chunks of 24 (exact 96 x 64 tiles, 15 one-KiB pieces per chunk = 5 per wave): 409 us against 437 on the four-wave instance with a quarter
         // of its columns clamped and 500 on two waves x (96 x 32).  Other Cin (multiples of 16) keep the four-wave instance with chunks of 16.
+        // Since profiles/r21_w2d_fold96_layer_ab.txt the 96 x 64 tile runs on FOUR waves x (48 x 32), 3 x 2 fragments of v_mfma_f32_16x16x4_f32 each: three waves
+        // at two workgroups per CU were six waves on four SIMDs (two SIMDs with two waves, two with one, two accumulator chains per wave); four waves with 24 + 96
+        // accumulator registers (152 in all) fit THREE workgroups per CU, three waves on every SIMD, six chains per wave.  Same tile, same chunks of 24 (the 15th piece
+        // is loaded by two waves); isolated GEMM, median of three alternations, three-wave -> four-wave: level 1 292 -> 250 us, level 2 234 -> 199, level 3d 157 -> 139
+        // at batch 4; 543 -> 461, 414 -> 357, 289 -> 248 at batch 8 (-11 .. -15 %; the parent's spread is 1 .. 8 us).  Both MFMA shapes accumulate an
+        // element's products as one fmaf chain in ascending k: M' is bit-identical to the three-wave instance's (sha256, tests/test_gpu_wino2d_fold_pipeline.py).
+        // The same fragments on the 128-channel tile (four waves x (64 x 32), or eight x (32 x 32) at four waves per SIMD) gained 0 .. 3 % and were dropped, and so was
+        // folding plane xf under the k-steps of plane xf + 1 from a second accumulator set (bit-identical, 0 +- 0.5 %: the other workgroup's waves already cover it).
         const bool p96 = (p->Cout_pad % 128) != 0;
+#if W2D_FOLD96_FR == 16
+        if (p96 && (p->Cin % W2D_FOLD96_KC) == 0)
+            return w2d_launch_gemm_fold<3, 2, 2, 2, W2D_FOLD96_KC, W2D_FOLD96_NBUF, W2D_FOLD96_WPC, 16>(&gp, pl.NTP, st, "w2d_gemm_kernel<96x64,foldM,kc" W2D_STR(W2D_FOLD96_KC) ",nb" W2D_STR(W2D_FOLD96_NBUF) ",4w16x16x4>+t8");
+#else
         if (p96 && (p->Cin % W2D_FOLD96_KC) == 0)
             return w2d_launch_gemm_fold<1, 2, 3, 1, W2D_FOLD96_KC, W2D_FOLD96_NBUF, W2D_FOLD_WPC>(&gp, pl.NTP, st, "w2d_gemm_kernel<96x64,foldM,kc" W2D_STR(W2D_FOLD96_KC) ",nb" W2D_STR(W2D_FOLD96_NBUF) ">+t8");
+#endif
         if ((p->Cin % 32) == 0)
             return w2d_launch_gemm_fold<1, 2, 4, 1, 32, 3, W2D_FOLD_WPC>(&gp, pl.NTP, st, p96 ? "w2d_gemm_kernel<128x64(96),foldM,kc32,nb3>+t8" : "w2d_gemm_kernel<128x64,foldM,kc32,nb3>+t8");
         return w2d_launch_gemm_fold<1, 2, 4, 1, 16, 3, W2D_FOLD_WPC>(&gp, pl.NTP, st, p96 ? "w2d_gemm_kernel<128x64(96),foldM,kc16,nb3>+t8" : "w2d_gemm_kernel<128x64,foldM,kc16,nb3>+t8");
