@@ -873,10 +873,10 @@ __global__ __launch_bounds__(256) void modulation_bwd_e_fold_kernel(const aid_mo
 
 extern "C" int aid_modulation_bwd(const aid_modulation_bwd_params* p, void* stream) {
     AID_REQUIRE(p && p->dmod && p->emb && p->W && p->dW && p->dbias && p->demb, "aid_modulation_bwd: null pointer");
+    const int nchunk = aid_cdiv(p->N, MODB_CH);          // (checked before the first launch: a refused call leaves dW / dbias as they were)
+    AID_REQUIRE(p->part && p->part_floats >= (int64_t)p->B * nchunk * p->E, "aid_modulation_bwd: `part` scratch must hold B * ceil(N/128) * E floats");
     hipLaunchKernelGGL(modulation_bwd_w_kernel, dim3((unsigned)(((int64_t)p->N * p->E + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *p);
     AID_CHECK_LAUNCH();
-    const int nchunk = aid_cdiv(p->N, MODB_CH);
-    AID_REQUIRE(p->part && p->part_floats >= (int64_t)p->B * nchunk * p->E, "aid_modulation_bwd: `part` scratch must hold B * ceil(N/128) * E floats");
     hipLaunchKernelGGL(modulation_bwd_e_kernel, dim3((unsigned)nchunk, (unsigned)p->B), dim3(256), 0, (hipStream_t)stream, *p, p->part, nchunk);
     AID_CHECK_LAUNCH();
     hipLaunchKernelGGL(modulation_bwd_e_fold_kernel, dim3((unsigned)aid_cdiv(p->E, 256), (unsigned)p->B), dim3(256), 0, (hipStream_t)stream, *p,
