@@ -125,6 +125,9 @@ __global__ __launch_bounds__(256) void cqt_gather_kernel(const aid_cqt_gather_pa
 
 static int cqt_check(const aid_cqt_params* p) {
     AID_REQUIRE(p && p->tab.n_oct > 0 && p->tab.n_oct <= AID_CQT_MAX_OCT, "aid_cqt: bad octave count");
+    AID_REQUIRE(p->B >= 1 && p->tab.bins >= 1 && p->Lh >= 1, "aid_cqt: B, bins and Lh must be positive");
+    AID_REQUIRE(p->tab.rc && p->tab.Lg && p->tab.goff && p->tab.g && p->tab.twiddle, "aid_cqt: null band table");
+    AID_REQUIRE((int64_t)p->B * p->tab.n_oct * p->tab.bins <= 2147483647LL, "aid_cqt: B * n_oct * bins exceeds the grid");
     for (int o = 0; o < p->tab.n_oct; ++o) {
         AID_REQUIRE(p->T_host[o] >= 2 && p->T_host[o] <= 8192 && (p->T_host[o] & (p->T_host[o] - 1)) == 0,
                     "aid_cqt: octave lengths must be powers of two in [2, 8192]");
@@ -167,6 +170,9 @@ extern "C" int aid_cqt_synthesis(const aid_cqt_params* p, void* stream) {
 
 extern "C" int aid_cqt_gather(const aid_cqt_gather_params* p, void* stream) {
     AID_REQUIRE(p && p->Y && (p->band_ws || p->X), "aid_cqt_gather: null pointer");
+    AID_REQUIRE(p->B >= 1 && p->B <= 65535 && p->Lh >= 1, "aid_cqt_gather: batch must be in [1, 65535] (grid y) and Lh positive");
+    AID_REQUIRE(!p->band_ws || (p->kfirst && p->kcount && p->rc && p->Lg && p->goff && p->woff && p->Tk && p->gdM),
+                "aid_cqt_gather: null band table");
     hipLaunchKernelGGL(cqt_gather_kernel, dim3(aid_cdiv(p->Lh, 256), p->B), dim3(256), 0, (hipStream_t)stream, *p);
     AID_CHECK_LAUNCH();
     return AID_OK;

@@ -69,6 +69,11 @@ extern "C" int aid_fft_pass(const aid_fft_pass_params* p, void* stream) {
     AID_REQUIRE(p && p->in && p->out && p->twiddle, "aid_fft_pass: null pointer");
     AID_REQUIRE(p->N > 0 && p->R >= 2 && p->N % p->R == 0 && p->Ns >= 1 && (p->N / p->R) % p->Ns == 0, "aid_fft_pass: bad factorisation");
     AID_REQUIRE(p->in != p->out, "aid_fft_pass: passes are out of place");
+    AID_REQUIRE(p->B >= 1 && p->B <= 65535, "aid_fft_pass: batch must be in [1, 65535] (grid y)");
+    AID_REQUIRE(p->in_mode >= 0 && p->in_mode <= 2 && p->out_mode >= 0 && p->out_mode <= 2, "aid_fft_pass: in_mode / out_mode must be 0, 1 or 2");
+    AID_REQUIRE(p->in_mode == 0 || p->Ns == 1, "aid_fft_pass: a real or half-spectrum input belongs to the first pass (Ns == 1)");
+    AID_REQUIRE(p->out_mode == 0 || (int64_t)p->Ns * p->R == p->N, "aid_fft_pass: a real or half-spectrum output belongs to the last pass (Ns * R == N)");
+    AID_REQUIRE(p->sign == 1.0f || p->sign == -1.0f, "aid_fft_pass: sign must be +1 or -1");
     switch (p->R) {
         case 2: return launch_fft<2>(p, st);   case 3: return launch_fft<3>(p, st);   case 4: return launch_fft<4>(p, st);
         case 5: return launch_fft<5>(p, st);   case 7: return launch_fft<7>(p, st);   case 8: return launch_fft<8>(p, st);
