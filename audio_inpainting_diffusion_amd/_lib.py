@@ -1,4 +1,5 @@
-"""ctypes binding of libaid_hip.so (the C ABI in include/aid_kernels.h, include/aid_degrade.h, include/aid_phase.h, include/aid_autoregressive.h, include/aid_restore.h, include/aid_declip.h, include/aid_resample_op.h, include/aid_bwe_long.h, include/aid_lowrate_long.h, include/aid_phase_long.h and include/aid_spec_long.h).
+"""ctypes binding of libaid_hip.so: the C ABI of the headers under include/, one entry of ``ABIS`` each (the table below the struct mirrors;
+``lib()`` binds from it and tests/test_abi_host.py holds it to the headers, field by field).
 
 There is deliberately NO fallback: if the shared library is missing or a launcher returns an error code,
 ``AidError`` is raised.  Tensors are passed as raw device pointers + element strides; the stream is torch's
@@ -8,9 +9,11 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional, Sequence
+from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
 import torch
+
+from . import winograd
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (AID_LIB_PATH selects another build of the library for kernel A/B experiments -- honoured only together with AID_EXPERIMENT=1, and announced on
@@ -20,9 +23,10 @@ if os.environ.get("AID_EXPERIMENT") == "1" and os.environ.get("AID_LIB_PATH"):
     LIB_PATH = os.environ["AID_LIB_PATH"]
     import sys as _sys
     print(f"[aid] AID_EXPERIMENT=1: loading {LIB_PATH} instead of the in-tree libaid_hip.so", file=_sys.stderr)
+# (the AID_* constants of this module that repeat a #define are listed per header in ABIS[...].macros and compared with it by tests/test_abi_host.py)
 AID_CQT_MAX_OCT = 12
 AID_STATS_SPLIT = 32
-AID_CONV2D_SPLIT_FLAG_BYTES = 4096     # include/aid_kernels.h: leading flag region of the split-K scratch (checked against the header in tests/test_host_logic.py)
+AID_CONV2D_SPLIT_FLAG_BYTES = 4096     # leading flag region of the split-K scratch
 AID_ATTN_MAX_T = 128          # aid_time_attention: one workgroup holds a whole [T, T] score tile
 
 
@@ -254,7 +258,7 @@ class SumsqParams(C.Structure):
 AID_SUMSQ_BLOCKS = 512
 
 
-# ---- include/aid_degrade.h (restoration degradations; a header and export list of their own) ----
+# ---- include/aid_degrade.h (restoration degradations) ----
 class FirParams(C.Structure):
     _fields_ = [("x", C.c_void_p), ("out", C.c_void_p), ("h", C.c_void_p), ("add1", C.c_void_p), ("add2", C.c_void_p), ("c0", C.c_float),
                 ("B", C.c_int), ("K", C.c_int), ("stride", C.c_int), ("pad_left", C.c_int), ("adjoint", C.c_int),
@@ -274,11 +278,9 @@ class ClipParams(C.Structure):
                 ("L", C.c_int64), ("x_ld", C.c_int64), ("out_ld", C.c_int64)]
 
 
-AID_DEGRADE_ABI_VERSION = 1
-DEGRADE_EXPORTS = ["aid_degrade_abi_version", "aid_fir", "aid_iir", "aid_clip"]
 
 
-# ---- include/aid_phase.h (phase retrieval: STFT magnitude and the induced-matrix-norm seed; a header and export list of their own) ----
+# ---- include/aid_phase.h (phase retrieval: STFT magnitude and the induced-matrix-norm seed) ----
 class StftMagParams(C.Structure):
     _fields_ = [("x", C.c_void_p), ("g", C.c_void_p), ("out", C.c_void_p), ("frames", C.c_void_p), ("window", C.c_void_p), ("twiddle", C.c_void_p),
                 ("B", C.c_int), ("n_fft", C.c_int), ("hop", C.c_int), ("n_frames", C.c_int), ("adjoint", C.c_int),
@@ -290,20 +292,16 @@ class MatrixNormParams(C.Structure):
                 ("B", C.c_int), ("F", C.c_int), ("T", C.c_int), ("ord", C.c_int), ("max_iter", C.c_int), ("tol", C.c_double)]
 
 
-AID_PHASE_ABI_VERSION = 1
-PHASE_EXPORTS = ["aid_phase_abi_version", "aid_stft_mag", "aid_matrix_norm_seed"]
 
-# ---- include/aid_autoregressive.h (the window carry of autoregressive generation; a header and export list of their own) ----
+# ---- include/aid_autoregressive.h (the window carry of autoregressive generation) ----
 class ArCarryParams(C.Structure):
     _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("out", C.c_void_p), ("B", C.c_int), ("first", C.c_int),
                 ("L", C.c_int64), ("end", C.c_int64), ("off", C.c_int64), ("out_ld", C.c_int64)]
 
 
-AID_AR_ABI_VERSION = 1
-AR_EXPORTS = ["aid_ar_abi_version", "aid_ar_carry"]
 
 
-# ---- include/aid_restore.h (window gather / scatter of whole-recording restoration; a header and export list of their own) ----
+# ---- include/aid_restore.h (window gather / scatter of whole-recording restoration) ----
 class WindowGatherParams(C.Structure):
     _fields_ = [("rec", C.c_void_p), ("out", C.c_void_p), ("mask", C.c_void_p), ("y", C.c_void_p), ("m", C.c_void_p), ("jobs", C.c_void_p),
                 ("J", C.c_int), ("R", C.c_int), ("L", C.c_int64), ("N", C.c_int64), ("rec_ld", C.c_int64), ("out_ld", C.c_int64), ("mask_ld", C.c_int64)]
@@ -314,11 +312,9 @@ class WindowScatterParams(C.Structure):
                 ("L", C.c_int64), ("N", C.c_int64), ("out_ld", C.c_int64)]
 
 
-AID_RESTORE_ABI_VERSION = 1
 AID_RESTORE_JOB_FIELDS = 6             # r, s, head, tail, lo, hi (int64 each)
-RESTORE_EXPORTS = ["aid_restore_abi_version", "aid_window_gather", "aid_window_scatter"]
 
-# ---- include/aid_declip.h (declipping whole recordings: the clipped / known / absent operator and its gather; a header and export list of their own) ----
+# ---- include/aid_declip.h (declipping whole recordings: the clipped / known / absent operator and its gather) ----
 class ClipKnownParams(C.Structure):
     _fields_ = [("x", C.c_void_p), ("xref", C.c_void_p), ("y", C.c_void_p), ("state", C.c_void_p), ("clip", C.c_void_p), ("out", C.c_void_p),
                 ("B", C.c_int), ("mode", C.c_int), ("L", C.c_int64), ("x_ld", C.c_int64), ("xref_ld", C.c_int64), ("y_ld", C.c_int64),
@@ -330,20 +326,16 @@ class DeclipGatherParams(C.Structure):
                 ("J", C.c_int), ("R", C.c_int), ("L", C.c_int64), ("N", C.c_int64), ("rec_ld", C.c_int64), ("out_ld", C.c_int64)]
 
 
-AID_DECLIP_ABI_VERSION = 1
-DECLIP_EXPORTS = ["aid_declip_abi_version", "aid_clip_known", "aid_declip_gather"]
 
-# ---- include/aid_resample_op.h (the resampling degradation of bandwidth extension: the adjoint of aid_resample_poly; a header and export list of their own) ----
+# ---- include/aid_resample_op.h (the resampling degradation of bandwidth extension: the adjoint of aid_resample_poly) ----
 class ResamplePolyAdjParams(C.Structure):
     _fields_ = [("g", C.c_void_p), ("gx", C.c_void_p), ("kT", C.c_void_p), ("j_lo", C.c_void_p), ("j_hi", C.c_void_p),
                 ("g_ld", C.c_int64), ("gx_ld", C.c_int64), ("L", C.c_int64), ("Lout", C.c_int64),
                 ("B", C.c_int), ("orig_freq", C.c_int), ("new_freq", C.c_int), ("width", C.c_int), ("K", C.c_int)]
 
 
-AID_RESAMPLE_OP_ABI_VERSION = 1
-RESAMPLE_OP_EXPORTS = ["aid_resample_op_abi_version", "aid_resample_poly_adj"]
 
-# ---- include/aid_bwe_long.h (bandwidth extension of whole recordings: the filtered / known / unobserved / absent FIR operator and its gather; a header and export list of their own) ----
+# ---- include/aid_bwe_long.h (bandwidth extension of whole recordings: the filtered / known / unobserved / absent FIR operator and its gather) ----
 class FirObservedParams(C.Structure):
     _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("state", C.c_void_p), ("h", C.c_void_p), ("out", C.c_void_p),
                 ("B", C.c_int), ("K", C.c_int), ("mode", C.c_int), ("L", C.c_int64), ("x_ld", C.c_int64), ("y_ld", C.c_int64),
@@ -355,10 +347,8 @@ class BweGatherParams(C.Structure):
                 ("J", C.c_int), ("R", C.c_int), ("K", C.c_int), ("L", C.c_int64), ("N", C.c_int64), ("rec_ld", C.c_int64), ("out_ld", C.c_int64)]
 
 
-AID_BWE_LONG_ABI_VERSION = 1
-BWE_LONG_EXPORTS = ["aid_bwe_long_abi_version", "aid_fir_observed", "aid_bwe_gather"]
 
-# ---- include/aid_lowrate_long.h (bandwidth extension of whole low-sample-rate recordings: the known / observed / unobserved / absent resampling operator and its gather; a header and export list of their own) ----
+# ---- include/aid_lowrate_long.h (bandwidth extension of whole low-sample-rate recordings: the known / observed / unobserved / absent resampling operator and its gather) ----
 class RateObservedParams(C.Structure):
     _fields_ = [("x", C.c_void_p), ("state", C.c_void_p), ("k", C.c_void_p), ("kT", C.c_void_p), ("j_lo", C.c_void_p), ("j_hi", C.c_void_p), ("out", C.c_void_p),
                 ("L", C.c_int64), ("Mw", C.c_int64), ("x_ld", C.c_int64), ("state_ld", C.c_int64), ("out_ld", C.c_int64),
@@ -371,10 +361,8 @@ class LowrateGatherParams(C.Structure):
                 ("J", C.c_int), ("R", C.c_int), ("orig_freq", C.c_int), ("new_freq", C.c_int), ("width", C.c_int), ("K", C.c_int)]
 
 
-AID_LOWRATE_LONG_ABI_VERSION = 1
-LOWRATE_LONG_EXPORTS = ["aid_lowrate_long_abi_version", "aid_rate_observed", "aid_lowrate_gather"]
 
-# ---- include/aid_phase_long.h (phase retrieval of whole recordings: the known / observed / unobserved / absent STFT-magnitude operator and its gather; a header and export list of their own) ----
+# ---- include/aid_phase_long.h (phase retrieval of whole recordings: the known / observed / unobserved / absent STFT-magnitude operator and its gather) ----
 class StftMagObservedParams(C.Structure):
     _fields_ = [("x", C.c_void_p), ("g", C.c_void_p), ("state", C.c_void_p), ("window", C.c_void_p), ("twiddle", C.c_void_p), ("frames", C.c_void_p), ("out", C.c_void_p),
                 ("L", C.c_int64), ("x_ld", C.c_int64), ("g_ld", C.c_int64), ("state_ld", C.c_int64), ("out_ld", C.c_int64),
@@ -387,10 +375,8 @@ class PrGatherParams(C.Structure):
                 ("J", C.c_int), ("R", C.c_int), ("n_fft", C.c_int), ("hop", C.c_int), ("n_frames", C.c_int)]
 
 
-AID_PHASE_LONG_ABI_VERSION = 1
-PHASE_LONG_EXPORTS = ["aid_phase_long_abi_version", "aid_stft_mag_observed", "aid_pr_gather"]
 
-# ---- include/aid_spec_long.h (spectrogram inpainting of whole recordings: the known / observed / unobserved / absent STFT-masking operator and its gather; a header and export list of their own) ----
+# ---- include/aid_spec_long.h (spectrogram inpainting of whole recordings: the known / observed / unobserved / absent STFT-masking operator and its gather) ----
 class StftMaskObservedParams(C.Structure):
     _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("state", C.c_void_p), ("items", C.c_void_p),
                 ("window", C.c_void_p), ("twiddle", C.c_void_p), ("inv_env", C.c_void_p), ("mask", C.c_void_p),
@@ -406,97 +392,119 @@ class SpecGatherParams(C.Structure):
                 ("J", C.c_int), ("R", C.c_int), ("n_fft", C.c_int), ("hop", C.c_int), ("n_frames", C.c_int)]
 
 
-AID_SPEC_LONG_ABI_VERSION = 1
 AID_SPEC_ITEM_FIELDS = 3
-SPEC_LONG_EXPORTS = ["aid_spec_long_abi_version", "aid_stft_mask_observed", "aid_spec_gather"]
 
-EXPORTS = ["aid_abi_version", "aid_last_error", "aid_last_kernel", "aid_group_stats", "aid_conv2d", "aid_conv2d_pack_dims", "aid_conv2d_stat_partials", "aid_pack_conv_weight", "aid_wino_gy", "aid_conv2d_wgrad_tiles", "aid_resample",
-           "aid_time_attention", "aid_embed", "aid_modulation", "aid_cqt_analysis", "aid_cqt_synthesis",
-           "aid_cqt_gather", "aid_axpby", "aid_score_step", "aid_add2", "aid_group_dot", "aid_norm_bwd",
-           "aid_time_attention_bwd", "aid_guidance_seed", "aid_guidance_step", "aid_set_rows", "aid_row_norm", "aid_scale_act", "aid_fft_pass",
-           "aid_stft_frames", "aid_stft_ola", "aid_resample_poly", "aid_conv2d_wino_input_supported", "aid_conv2d_dot_partials", "aid_conv2d_x2_supported", "aid_conv2d_dot_partials_1x1", "aid_conv2d_wino_input_ok", "aid_conv2d_wino_form", "aid_conv2d_wino8_supported", "aid_conv2d_wino_split_ws_bytes", "aid_conv2d_fin_supported",
-           "aid_conv2d_wgrad", "aid_wgrad_reduce", "aid_channel_dot", "aid_relpos_bwd", "aid_scale_bwd", "aid_modulation_bwd", "aid_embed_bwd",
-           "aid_adam", "aid_ema", "aid_sumsq", "aid_wino2d_gemm", "aid_wino2d_set_split", "aid_conv2d_wino2d_gemm", "aid_conv2d_wino2d_output", "aid_conv2d_wino2d_supported", "aid_conv2d_wino2d_positions", "aid_conv2d_wino2d_wanted", "aid_conv2d_wino2d_tform"]
 
-# the sub-ABIs, each with a header and a version of its own: (exports, version symbol, version, header under include/)
-SUB_ABIS = [(DEGRADE_EXPORTS, "aid_degrade_abi_version", AID_DEGRADE_ABI_VERSION, "aid_degrade.h"),
-            (PHASE_EXPORTS, "aid_phase_abi_version", AID_PHASE_ABI_VERSION, "aid_phase.h"),
-            (AR_EXPORTS, "aid_ar_abi_version", AID_AR_ABI_VERSION, "aid_autoregressive.h"),
-            (RESTORE_EXPORTS, "aid_restore_abi_version", AID_RESTORE_ABI_VERSION, "aid_restore.h"),
-            (DECLIP_EXPORTS, "aid_declip_abi_version", AID_DECLIP_ABI_VERSION, "aid_declip.h"),
-            (RESAMPLE_OP_EXPORTS, "aid_resample_op_abi_version", AID_RESAMPLE_OP_ABI_VERSION, "aid_resample_op.h"),
-            (BWE_LONG_EXPORTS, "aid_bwe_long_abi_version", AID_BWE_LONG_ABI_VERSION, "aid_bwe_long.h"),
-            (LOWRATE_LONG_EXPORTS, "aid_lowrate_long_abi_version", AID_LOWRATE_LONG_ABI_VERSION, "aid_lowrate_long.h"),
-            (PHASE_LONG_EXPORTS, "aid_phase_long_abi_version", AID_PHASE_LONG_ABI_VERSION, "aid_phase_long.h"),
-            (SPEC_LONG_EXPORTS, "aid_spec_long_abi_version", AID_SPEC_LONG_ABI_VERSION, "aid_spec_long.h")]
+class Abi(NamedTuple):
+    """One header under include/ as the binding sees it.  Adding a header, a struct or an export is one edit here: ``lib()`` binds from this table and
+    tests/test_abi_host.py compares every entry with the header (struct set, field order, sizes and offsets, prototypes, version, macros)."""
+    header: str                                   # file under include/
+    version_fn: str                               # int f(void); its upper-cased name is the header's version #define
+    version: int                                  # the version this binding was written against
+    structs: Dict[str, type]                      # C typedef name -> ctypes mirror
+    launches: Dict[str, type]                     # entry point int f(const params*, void* stream) -> the mirror of its params
+    queries: Dict[str, Tuple] = {}                # host functions with signatures of their own: name -> (restype, argtypes)
+    macros: Tuple[str, ...] = ()                  # #defines whose value a module constant of the same name repeats
+
+    @property
+    def exports(self):
+        return [self.version_fn, *self.queries, *self.launches]
+
+
+def _ints(n):
+    return [C.c_int] * n
+
+
+ABIS = (
+    Abi("aid_kernels.h", "aid_abi_version", 14,
+        structs={"aid_view": View, "aid_group_stats_params": GroupStatsParams, "aid_conv2d_params": Conv2dParams, "aid_wino2d_gemm_params": Wino2dGemmParams,
+                 "aid_resample_params": ResampleParams, "aid_attention_params": AttentionParams, "aid_embed_params": EmbedParams,
+                 "aid_modulation_params": ModulationParams, "aid_cqt_tables": CqtTables, "aid_cqt_params": CqtParams, "aid_cqt_gather_params": CqtGatherParams,
+                 "aid_fft_pass_params": FftPassParams, "aid_axpby_params": AxpbyParams, "aid_score_step_params": ScoreStepParams,
+                 "aid_group_dot_params": GroupDotParams, "aid_norm_bwd_params": NormBwdParams, "aid_attention_bwd_params": AttentionBwdParams,
+                 "aid_guidance_seed_params": GuidanceSeedParams, "aid_guidance_step_params": GuidanceStepParams, "aid_set_rows_params": SetRowsParams,
+                 "aid_row_norm_params": RowNormParams, "aid_resample_poly_params": ResamplePolyParams, "aid_stft_params": StftParams,
+                 "aid_scale_act_params": ScaleActParams, "aid_add2_params": Add2Params, "aid_conv2d_wgrad_params": WgradParams,
+                 "aid_wino_gy_params": WinoGyParams, "aid_pack_conv_weight_params": PackConvWeightParams, "aid_wgrad_reduce_params": WgradReduceParams,
+                 "aid_channel_dot_params": ChannelDotParams, "aid_relpos_bwd_params": RelposBwdParams, "aid_scale_bwd_params": ScaleBwdParams,
+                 "aid_modulation_bwd_params": ModulationBwdParams, "aid_embed_bwd_params": EmbedBwdParams, "aid_adam_params": AdamParams,
+                 "aid_ema_params": EmaParams, "aid_sumsq_params": SumsqParams},
+        launches={"aid_group_stats": GroupStatsParams, "aid_conv2d": Conv2dParams, "aid_wino2d_gemm": Wino2dGemmParams,
+                  "aid_conv2d_wino2d_gemm": Conv2dParams, "aid_conv2d_wino2d_output": Conv2dParams, "aid_resample": ResampleParams,
+                  "aid_time_attention": AttentionParams, "aid_embed": EmbedParams, "aid_modulation": ModulationParams,
+                  "aid_cqt_analysis": CqtParams, "aid_cqt_synthesis": CqtParams, "aid_cqt_gather": CqtGatherParams, "aid_fft_pass": FftPassParams,
+                  "aid_axpby": AxpbyParams, "aid_score_step": ScoreStepParams, "aid_group_dot": GroupDotParams, "aid_norm_bwd": NormBwdParams,
+                  "aid_time_attention_bwd": AttentionBwdParams, "aid_guidance_seed": GuidanceSeedParams, "aid_guidance_step": GuidanceStepParams,
+                  "aid_set_rows": SetRowsParams, "aid_row_norm": RowNormParams, "aid_resample_poly": ResamplePolyParams,
+                  "aid_stft_frames": StftParams, "aid_stft_ola": StftParams, "aid_scale_act": ScaleActParams, "aid_add2": Add2Params,
+                  "aid_conv2d_wgrad": WgradParams, "aid_wino_gy": WinoGyParams, "aid_pack_conv_weight": PackConvWeightParams,
+                  "aid_wgrad_reduce": WgradReduceParams, "aid_channel_dot": ChannelDotParams, "aid_relpos_bwd": RelposBwdParams,
+                  "aid_scale_bwd": ScaleBwdParams, "aid_modulation_bwd": ModulationBwdParams, "aid_embed_bwd": EmbedBwdParams,
+                  "aid_adam": AdamParams, "aid_ema": EmaParams, "aid_sumsq": SumsqParams},
+        queries={"aid_last_error": (C.c_char_p, []), "aid_last_kernel": (C.c_char_p, []),
+                 "aid_conv2d_pack_dims": (None, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+                 "aid_conv2d_wino_input_supported": (C.c_int, _ints(3)), "aid_conv2d_wino_input_ok": (C.c_int, _ints(6)),
+                 "aid_conv2d_wino_form": (C.c_int, _ints(6)), "aid_conv2d_wino8_supported": (C.c_int, _ints(5)),
+                 "aid_conv2d_wino_split_ws_bytes": (C.c_int64, _ints(6)), "aid_conv2d_fin_supported": (C.c_int, _ints(7)),
+                 "aid_conv2d_dot_partials": (C.c_int, _ints(7)), "aid_conv2d_dot_partials_1x1": (C.c_int, _ints(5)),
+                 "aid_conv2d_stat_partials": (C.c_int, _ints(7)), "aid_conv2d_x2_supported": (C.c_int, _ints(5)),
+                 "aid_conv2d_wgrad_tiles": (C.c_int, _ints(5)), "aid_conv2d_wino2d_supported": (C.c_int, _ints(5)),
+                 "aid_conv2d_wino2d_positions": (C.c_int64, _ints(4)), "aid_conv2d_wino2d_wanted": (C.c_int, _ints(6)),
+                 "aid_conv2d_wino2d_tform": (C.c_int, _ints(6)), "aid_wino2d_set_split": (C.c_int, _ints(1))},
+        macros=("AID_CQT_MAX_OCT", "AID_STATS_SPLIT", "AID_CONV2D_SPLIT_FLAG_BYTES", "AID_SUMSQ_BLOCKS")),
+    Abi("aid_degrade.h", "aid_degrade_abi_version", 1,
+        structs={"aid_fir_params": FirParams, "aid_iir_params": IirParams, "aid_clip_params": ClipParams},
+        launches={"aid_fir": FirParams, "aid_iir": IirParams, "aid_clip": ClipParams}),
+    Abi("aid_phase.h", "aid_phase_abi_version", 1,
+        structs={"aid_stft_mag_params": StftMagParams, "aid_matrix_norm_params": MatrixNormParams},
+        launches={"aid_stft_mag": StftMagParams, "aid_matrix_norm_seed": MatrixNormParams}),
+    Abi("aid_autoregressive.h", "aid_ar_abi_version", 1,
+        structs={"aid_ar_carry_params": ArCarryParams}, launches={"aid_ar_carry": ArCarryParams}),
+    Abi("aid_restore.h", "aid_restore_abi_version", 1,
+        structs={"aid_window_gather_params": WindowGatherParams, "aid_window_scatter_params": WindowScatterParams},
+        launches={"aid_window_gather": WindowGatherParams, "aid_window_scatter": WindowScatterParams}, macros=("AID_RESTORE_JOB_FIELDS",)),
+    Abi("aid_declip.h", "aid_declip_abi_version", 1,
+        structs={"aid_clip_known_params": ClipKnownParams, "aid_declip_gather_params": DeclipGatherParams},
+        launches={"aid_clip_known": ClipKnownParams, "aid_declip_gather": DeclipGatherParams}),
+    Abi("aid_resample_op.h", "aid_resample_op_abi_version", 1,
+        structs={"aid_resample_poly_adj_params": ResamplePolyAdjParams}, launches={"aid_resample_poly_adj": ResamplePolyAdjParams}),
+    Abi("aid_bwe_long.h", "aid_bwe_long_abi_version", 1,
+        structs={"aid_fir_observed_params": FirObservedParams, "aid_bwe_gather_params": BweGatherParams},
+        launches={"aid_fir_observed": FirObservedParams, "aid_bwe_gather": BweGatherParams}),
+    Abi("aid_lowrate_long.h", "aid_lowrate_long_abi_version", 1,
+        structs={"aid_rate_observed_params": RateObservedParams, "aid_lowrate_gather_params": LowrateGatherParams},
+        launches={"aid_rate_observed": RateObservedParams, "aid_lowrate_gather": LowrateGatherParams}),
+    Abi("aid_phase_long.h", "aid_phase_long_abi_version", 1,
+        structs={"aid_stft_mag_observed_params": StftMagObservedParams, "aid_pr_gather_params": PrGatherParams},
+        launches={"aid_stft_mag_observed": StftMagObservedParams, "aid_pr_gather": PrGatherParams}),
+    Abi("aid_spec_long.h", "aid_spec_long_abi_version", 1,
+        structs={"aid_stft_mask_observed_params": StftMaskObservedParams, "aid_spec_gather_params": SpecGatherParams},
+        launches={"aid_stft_mask_observed": StftMaskObservedParams, "aid_spec_gather": SpecGatherParams}, macros=("AID_SPEC_ITEM_FIELDS",)),
+)
 
 _lib = None
 
 
 def lib():
-    """Load libaid_hip.so (built by ``__graft_entry__.build()`` / ``build.py``).  Raises if it is absent."""
+    """Load libaid_hip.so (built by ``__graft_entry__.build()`` / ``build.py``) and bind every entry of ``ABIS``.  Raises if it is absent, if an export
+    is missing or if a header's version is not the one this binding was written against."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise AidError(f"{LIB_PATH} not found: build the HIP extension first (python __graft_entry__.py). "
                            "There is no CPU / eager fallback on the product path.")
         L = C.CDLL(LIB_PATH)
-        L.aid_last_error.restype = C.c_char_p
-        L.aid_abi_version.restype = C.c_int
-        L.aid_last_kernel.restype = C.c_char_p
-        for name in EXPORTS:
-            if not hasattr(L, name):
-                raise AidError(f"libaid_hip.so does not export {name}")
-        L.aid_conv2d_pack_dims.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        L.aid_conv2d_pack_dims.restype = None
-        L.aid_conv2d_wino_input_supported.argtypes = [C.c_int, C.c_int, C.c_int]
-        L.aid_conv2d_wino_input_supported.restype = C.c_int
-        L.aid_conv2d_dot_partials.argtypes = [C.c_int] * 7
-        L.aid_conv2d_dot_partials.restype = C.c_int
-        L.aid_conv2d_x2_supported.argtypes = [C.c_int] * 5
-        L.aid_conv2d_x2_supported.restype = C.c_int
-        L.aid_conv2d_dot_partials_1x1.argtypes = [C.c_int] * 5
-        L.aid_conv2d_dot_partials_1x1.restype = C.c_int
-        L.aid_conv2d_wino_input_ok.argtypes = [C.c_int] * 6
-        L.aid_conv2d_wino_input_ok.restype = C.c_int
-        L.aid_conv2d_wino8_supported.argtypes = [C.c_int] * 5
-        L.aid_conv2d_wino8_supported.restype = C.c_int
-        L.aid_conv2d_fin_supported.argtypes = [C.c_int] * 7
-        L.aid_conv2d_fin_supported.restype = C.c_int
-        L.aid_conv2d_wino_form.argtypes = [C.c_int] * 6
-        L.aid_conv2d_wino_form.restype = C.c_int
-        L.aid_conv2d_wino_split_ws_bytes.argtypes = [C.c_int] * 6
-        L.aid_conv2d_wino_split_ws_bytes.restype = C.c_int64
-        L.aid_conv2d_stat_partials.argtypes = [C.c_int] * 7
-        L.aid_conv2d_stat_partials.restype = C.c_int
-        L.aid_conv2d_wgrad_tiles.argtypes = [C.c_int] * 5
-        L.aid_conv2d_wgrad_tiles.restype = C.c_int
-        L.aid_conv2d_wino2d_supported.argtypes = [C.c_int] * 5
-        L.aid_conv2d_wino2d_supported.restype = C.c_int
-        L.aid_conv2d_wino2d_wanted.argtypes = [C.c_int] * 6
-        L.aid_conv2d_wino2d_wanted.restype = C.c_int
-        L.aid_conv2d_wino2d_tform.argtypes = [C.c_int] * 6
-        L.aid_conv2d_wino2d_tform.restype = C.c_int
-        L.aid_conv2d_wino2d_positions.argtypes = [C.c_int] * 4
-        L.aid_conv2d_wino2d_positions.restype = C.c_int64
-        L.aid_wino2d_set_split.argtypes = [C.c_int]
-        L.aid_wino2d_set_split.restype = C.c_int
-        for name in EXPORTS[3:]:
-            if name not in ("aid_conv2d_pack_dims", "aid_conv2d_wino_input_supported", "aid_conv2d_dot_partials", "aid_conv2d_x2_supported", "aid_conv2d_dot_partials_1x1", "aid_conv2d_wino_input_ok", "aid_conv2d_wino_form", "aid_conv2d_wino8_supported", "aid_conv2d_wino_split_ws_bytes", "aid_conv2d_fin_supported",
-                            "aid_conv2d_stat_partials", "aid_conv2d_wgrad_tiles", "aid_conv2d_wino2d_supported", "aid_conv2d_wino2d_positions", "aid_conv2d_wino2d_wanted", "aid_conv2d_wino2d_tform", "aid_wino2d_set_split"):
-                getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
-                getattr(L, name).restype = C.c_int
-        if L.aid_abi_version() != 14:
-            raise AidError("ABI version mismatch")
-        for exports, version_fn, version, header in SUB_ABIS:
-            for name in exports:
+        for abi in ABIS:
+            for name in abi.exports:
                 if not hasattr(L, name):
                     raise AidError(f"libaid_hip.so does not export {name}")
-                getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
-                getattr(L, name).restype = C.c_int
-            getattr(L, version_fn).argtypes = []
-            if getattr(L, version_fn)() != version:
-                raise AidError(f"include/{header} ABI version mismatch")
+            for name in abi.launches:
+                # (raw addresses, not POINTER(struct): cached launch plans call these with the integer address of a parameter block, see call_on)
+                getattr(L, name).restype, getattr(L, name).argtypes = C.c_int, [C.c_void_p, C.c_void_p]
+            for name, (restype, argtypes) in {abi.version_fn: (C.c_int, []), **abi.queries}.items():
+                getattr(L, name).restype, getattr(L, name).argtypes = restype, argtypes
+            if getattr(L, abi.version_fn)() != abi.version:
+                raise AidError(f"include/{abi.header} ABI version mismatch")
         _lib = L
     return _lib
 
@@ -541,133 +549,80 @@ def pack_dims(cin: int, cout: int):
     return a.value, b.value
 
 
-def pack_conv_weight(w: torch.Tensor, transpose: bool = False) -> torch.Tensor:
-    """[Cout,Cin,KH,KW] (or [Cout,Cin,1] / [Cout,Cin]) -> packed [KH*KW, Cin_pad, Cout_pad] (cout contiguous).
+def wino8_matrices():
+    """(A^T [8,10], G [10,3], B^T [10,10]) of F(8,3) as the kernels use them, float64 (tools/gen_wino8.py writes csrc/aid_wino8.h from the same call)."""
+    return winograd.cook_toom(winograd.W8_POINTS, 8, 3)
 
-    transpose=True packs the input-gradient operator instead: taps flipped, roles of Cin/Cout swapped."""
+
+def wino45_matrices():
+    """(AF^T [4,8], GF [8,5], BF^T [8,8], AT^T [4,6], GT [6,3], BT^T [6,6]) of the 2-D form F(4,5) x F(4,3) as the kernels use them, float64
+    (tools/gen_wino45.py writes csrc/aid_wino45.h from the same calls)."""
+    return winograd.cook_toom(winograd.W45_F_POINTS, 4, 5) + winograd.cook_toom(winograd.W45_T_POINTS, 4, 3)
+
+
+# The fused 1-D F(4,3) kernels use the classic unscaled matrices over {0, +-1, +-2, inf}, not cook_toom((1, 2), 4, 3) (include/aid_kernels.h, aid_conv2d)
+_G43 = torch.tensor([[1 / 4, 0, 0], [-1 / 6, -1 / 6, -1 / 6], [-1 / 6, 1 / 6, -1 / 6], [1 / 24, 1 / 12, 1 / 6], [1 / 24, -1 / 12, 1 / 6], [0, 0, 1]],
+                    dtype=torch.float64)
+_G8, _GF, _GT = (torch.from_numpy(g) for g in (wino8_matrices()[1], wino45_matrices()[1], wino45_matrices()[4]))
+# Weight packs of a conv layer by the form number the builder speaks (network._FORMS): (G along kh or None, G along kw or None)
+PACK_FORMS = {0: (None, None), 4: (None, _G43), 8: (None, _G8), 45: (_GF, _GT), 85: (_GF, _G8)}
+
+
+def pack_planes(form: int, kh: int = 5, kw: int = 3) -> int:
+    """leading dimension of the pack of a [.., .., kh, kw] weight in this form"""
+    gh, gw = PACK_FORMS[form]
+    return (kh if gh is None else gh.shape[0]) * (kw if gw is None else gw.shape[0])
+
+
+def pack_conv_weight_form(w: torch.Tensor, form: int, transpose: bool = False) -> torch.Tensor:
+    """[Cout,Cin,KH,KW] (form 0 also [Cout,Cin,k] / [Cout,Cin]) -> the pack [planes, Cin_pad, Cout_pad] (cout contiguous, zero padded) that
+    aid_pack_conv_weight writes for this form: U = G_kh w G_kw^T in float64, stored fp32.  Plane order: kh*KW + kw (form 0), xi*5 + kh (1-D forms:
+    G along kw only), xf*NT + xt (2-D forms).  transpose=True packs the input-gradient operator instead: taps flipped, roles of Cin/Cout swapped."""
+    gh, gw = PACK_FORMS[form]
     if w.dim() == 2:
         w = w[:, :, None, None]
     elif w.dim() == 3:
         w = w[:, :, None, :]  # Conv1d [O,I,k] -> [O,I,1,k]
-    w = w.detach().float()
+    w = w.detach().double()
     if transpose:
         w = w.flip(2, 3).permute(1, 0, 2, 3)
     co, ci, kh, kw = w.shape
+    assert form == 0 or (kh, kw) == (5, 3)
+    if gw is None:
+        U = w.permute(2, 3, 1, 0)                                                         # [kh, kw, ci, co]
+    elif gh is None and form == 4:
+        # (_G43 row by row with each division done once, as aid_pack_conv_weight does it: the device pack is bit-identical)
+        w0, w1, w2 = w[..., 0], w[..., 1], w[..., 2]
+        U = torch.stack((w0 / 4, -(w0 + w1 + w2) / 6, -(w0 - w1 + w2) / 6, (w0 + 2 * w1 + 4 * w2) / 24,
+                         (w0 - 2 * w1 + 4 * w2) / 24, w2), dim=0).permute(0, 3, 2, 1)     # [xi, kh, ci, co]
+    elif gh is None:
+        U = torch.einsum("xk,oihk->xoih", gw.to(w.device), w).permute(0, 3, 2, 1)         # [xi, kh, ci, co]
+    else:
+        U = torch.einsum("fh,tk,oihk->ftio", gh.to(w.device), gw.to(w.device), w)         # [xf, xt, ci, co]
     cip, cop = pack_dims(ci, co)
-    out = torch.zeros(kh * kw, cip, cop, device=w.device, dtype=torch.float32)
-    out[:, :ci, :co] = w.permute(2, 3, 1, 0).reshape(kh * kw, ci, co)
+    out = torch.zeros(pack_planes(form, kh, kw), cip, cop, device=w.device, dtype=torch.float32)
+    out[:, :ci, :co] = U.reshape(-1, ci, co).float()
     return out
+
+
+def pack_conv_weight(w: torch.Tensor, transpose: bool = False) -> torch.Tensor:
+    return pack_conv_weight_form(w, 0, transpose)
 
 
 def pack_conv_weight_wino(w: torch.Tensor, transpose: bool = False) -> torch.Tensor:
-    """[Cout,Cin,5,3] -> Winograd F(4,3) pack [6*5, Cin_pad, Cout_pad]: U = G w along kw, "tap" index xi*5+kh
-    (computed in float64, stored fp32)."""
-    w = w.detach().double()
-    if transpose:
-        w = w.flip(2, 3).permute(1, 0, 2, 3)
-    co, ci, kh, kw = w.shape
-    assert (kh, kw) == (5, 3)
-    w0, w1, w2 = w[..., 0], w[..., 1], w[..., 2]
-    U = torch.stack((w0 / 4, -(w0 + w1 + w2) / 6, -(w0 - w1 + w2) / 6, (w0 + 2 * w1 + 4 * w2) / 24,
-                     (w0 - 2 * w1 + 4 * w2) / 24, w2), dim=0)                              # [NXI, co, ci, kh]
-    nxi = U.shape[0]
-    cip, cop = pack_dims(ci, co)
-    out = torch.zeros(nxi * kh, cip, cop, device=w.device, dtype=torch.float32)
-    out[:, :ci, :co] = U.permute(0, 3, 2, 1).reshape(nxi * kh, ci, co).float()
-    return out
-
-
-W8_POINTS = (0.4, 0.8, 1.25, 2.5)
-
-
-def wino8_matrices():
-    """(A^T [8,10], G [10,3], B^T [10,10]) of F(8,3) as the kernels use them (float64; same construction as tools/gen_wino8.py, which
-    writes csrc/aid_wino8.h): points {0, +-0.4, +-0.8, +-1.25, +-2.5, inf}, rows of B^T scaled to max |entry| = 1 and G by the inverse."""
-    import numpy as np
-    n = 10
-    pts = np.array([0.0] + [sg * a for a in W8_POINTS for sg in (1, -1)], dtype=np.float64)
-
-    def vander(cols):
-        V = np.zeros((n, cols))
-        for j in range(n - 1):
-            V[j] = pts[j] ** np.arange(cols)
-        V[n - 1, cols - 1] = 1.0
-        return V
-    AT, G, BT = vander(8).T, vander(3), np.linalg.inv(vander(n)).T
-    sc = np.abs(BT).max(axis=1)
-    BT = BT / sc[:, None]
-    BT[np.abs(BT) < 1e-13] = 0.0
-    return AT, G * sc[:, None], BT
-
-
-def wino45_matrices():
-    """(AF^T [4,8], GF [8,5], BF^T [8,8], AT^T [4,6], GT [6,3], BT^T [6,6]) of the 2-D form F(4,5) x F(4,3) as the kernels use them (float64; same
-    construction as tools/gen_wino45.py, which writes csrc/aid_wino45.h): row-axis points {0, +-1, +-2, +-1/2, inf}, T-axis {0, +-1, +-2, inf}."""
-    import numpy as np
-
-    def toom(points, m, r):
-        n = m + r - 1
-        pts = np.array([0.0] + [sg * a for a in points for sg in (1, -1)], dtype=np.float64)
-
-        def vander(cols):
-            V = np.zeros((n, cols))
-            for j in range(n - 1):
-                V[j] = pts[j] ** np.arange(cols)
-            V[n - 1, cols - 1] = 1.0
-            return V
-        AT, G, BT = vander(m).T, vander(r), np.linalg.inv(vander(n)).T
-        sc = np.abs(BT).max(axis=1)
-        BT = BT / sc[:, None]
-        BT[np.abs(BT) < 1e-13] = 0.0
-        return AT, G * sc[:, None], BT
-    return toom((1.0, 2.0, 0.5), 4, 5) + toom((1.0, 2.0), 4, 3)
-
-
-def pack_conv_weight_wino2d(w: torch.Tensor, transpose: bool = False) -> torch.Tensor:
-    """[Cout,Cin,5,3] -> 2-D Winograd pack [48, Cin_pad, Cout_pad]: U[xf*6 + xt] = GF w GT^T (float64, stored fp32)."""
-    w = w.detach().double()
-    if transpose:
-        w = w.flip(2, 3).permute(1, 0, 2, 3)
-    co, ci, kh, kw = w.shape
-    assert (kh, kw) == (5, 3)
-    m = wino45_matrices()
-    GF, GT = torch.from_numpy(m[1]).to(w.device), torch.from_numpy(m[4]).to(w.device)
-    U = torch.einsum("fh,tk,oihk->ftio", GF, GT, w).reshape(48, ci, co)
-    cip, cop = pack_dims(ci, co)
-    out = torch.zeros(48, cip, cop, device=w.device, dtype=torch.float32)
-    out[:, :ci, :co] = U.float()
-    return out
-
-
-def pack_conv_weight_wino2d8(w: torch.Tensor, transpose: bool = False) -> torch.Tensor:
-    """[Cout,Cin,5,3] -> pack of the 2-D form with F(8,3) along T [80, Cin_pad, Cout_pad]: U[xf*10 + xt] = GF w G8^T (float64, stored fp32)."""
-    w = w.detach().double()
-    if transpose:
-        w = w.flip(2, 3).permute(1, 0, 2, 3)
-    co, ci, kh, kw = w.shape
-    assert (kh, kw) == (5, 3)
-    GF = torch.from_numpy(wino45_matrices()[1]).to(w.device)
-    G8 = torch.from_numpy(wino8_matrices()[1]).to(w.device)
-    U = torch.einsum("fh,tk,oihk->ftio", GF, G8, w).reshape(80, ci, co)
-    cip, cop = pack_dims(ci, co)
-    out = torch.zeros(80, cip, cop, device=w.device, dtype=torch.float32)
-    out[:, :ci, :co] = U.float()
-    return out
+    return pack_conv_weight_form(w, 4, transpose)
 
 
 def pack_conv_weight_wino8(w: torch.Tensor, transpose: bool = False) -> torch.Tensor:
-    """[Cout,Cin,5,3] -> Winograd F(8,3) pack [10*5, Cin_pad, Cout_pad]: U = G w along kw, "tap" index xi*5+kh (float64, stored fp32)."""
-    w = w.detach().double()
-    if transpose:
-        w = w.flip(2, 3).permute(1, 0, 2, 3)
-    co, ci, kh, kw = w.shape
-    assert (kh, kw) == (5, 3)
-    G = torch.from_numpy(wino8_matrices()[1]).to(w.device)
-    U = torch.einsum("xk,oihk->xoih", G, w)                                               # [NXI, co, ci, kh]
-    cip, cop = pack_dims(ci, co)
-    out = torch.zeros(10 * kh, cip, cop, device=w.device, dtype=torch.float32)
-    out[:, :ci, :co] = U.permute(0, 3, 2, 1).reshape(10 * kh, ci, co).float()
-    return out
+    return pack_conv_weight_form(w, 8, transpose)
+
+
+def pack_conv_weight_wino2d(w: torch.Tensor, transpose: bool = False) -> torch.Tensor:
+    return pack_conv_weight_form(w, 45, transpose)
+
+
+def pack_conv_weight_wino2d8(w: torch.Tensor, transpose: bool = False) -> torch.Tensor:
+    return pack_conv_weight_form(w, 85, transpose)
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -915,7 +915,7 @@ class Unet_CQT_oct_with_attention(nn.Module):
                     rec.fwd[f], rec.dgrad[f] = ensure(old.fwd.get(f), (taps, cip, cop)), ensure(old.dgrad.get(f), (taps, cipT, copT))
                 pk = [_lib.ptr(packs.get(f)) for f in _FORMS for packs in (rec.fwd, rec.dgrad)]      # (the struct's order: form by form, forward first)
                 pp = _lib.PackConvWeightParams(wd.data_ptr(), *pk[:4], co, ci, kh, kw, cip, cop, cipT, copT, *pk[4:])
-                _lib.call("aid_pack_conv_weight", pp)       # all layouts of this weight in one launch (same values as _lib.pack_conv_weight*)
+                _lib.call("aid_pack_conv_weight", pp)       # all layouts of this weight in one launch (same values as _lib.pack_conv_weight_form, the tests' reference)
             elif leaf == "gamma":
                 put(name, w.detach().reshape(-1).float())
         # ResnetBlocks that project their input twice (proj_in and res_conv on the same tensor): one stacked pack [W_pi^T ; W_rc^T / sqrt2] for the

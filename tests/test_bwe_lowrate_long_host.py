@@ -1,18 +1,12 @@
 """CPU tests (no GPU) of bandwidth extension of whole low-sample-rate recordings (lowrate_long.py, include/aid_lowrate_long.h,
-Sampler.predict_bwe_lowrate_long, harness.bwe_lowrate_long): the C ABI and its ctypes mirror, the aligned window grid (every start a multiple
+Sampler.predict_bwe_lowrate_long, harness.bwe_lowrate_long): the aligned window grid (every start a multiple
 of the input period; ownership tiles the recording), the exactness of the observed low-rate samples of a window in float64, the lengths, and
 the refusals, all raised before anything touches a GPU."""
-import ctypes
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
 
 # (factor, filt_type) -> (orig, new): 2:1, 3:2, 147:100, decimation by 3 and by 4
 RATES = [(2, "resample", (2, 1)), (1.5, "resample", (3, 2)), (1.47, "resample", (147, 100)), (3, "decimate", (3, 1)), (4, "decimate", (4, 1))]
@@ -25,48 +19,6 @@ def _refused(ratio, L):
 
 
 LOWRATE_CASES = [(f, t, ratio, L, end, N) for f, t, ratio in RATES for L, end in GRIDS for N in LENGTHS if not _refused(ratio, L)]
-
-
-# ---- C ABI ---------------------------------------------------------------------------------------------------------------------------
-def test_lowrate_long_header_compiles_as_c_and_struct_sizes_match_the_binding(tmp_path):
-    from audio_inpainting_diffusion_amd import _lib
-    gcc = shutil.which("gcc")
-    if gcc is None:
-        pytest.skip("no gcc")
-    pairs = {"aid_rate_observed_params": "RateObservedParams", "aid_lowrate_gather_params": "LowrateGatherParams"}
-    hdr = open(os.path.join(ROOT, "include", "aid_lowrate_long.h")).read()
-    assert set(re.findall(r"\}\s*(aid_\w+)\s*;", hdr)) == set(pairs)
-    assert int(re.search(r"#define AID_LOWRATE_LONG_ABI_VERSION (\d+)", hdr).group(1)) == _lib.AID_LOWRATE_LONG_ABI_VERSION == 1
-    fields = {"aid_rate_observed_params": ("out", "L", "out_ld", "B", "K"), "aid_lowrate_gather_params": ("jobs", "L", "out_ld", "J", "K")}
-    src = tmp_path / "sizes.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "aid_lowrate_long.h"\nint main(void) {\n' +
-                   "".join(f'    printf("{c} %zu\\n", sizeof({c}));\n' for c in pairs) +
-                   "".join(f'    printf("{c}.{f} %zu\\n", offsetof({c}, {f}));\n' for c, fs in fields.items() for f in fs) + "    return 0;\n}\n")
-    exe = tmp_path / "sizes"
-    subprocess.check_call([gcc, "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    out = dict(line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())
-    for c, py in pairs.items():
-        assert int(out[c]) == ctypes.sizeof(getattr(_lib, py)), (c, out[c], ctypes.sizeof(getattr(_lib, py)))
-        for f in fields[c]:
-            assert int(out[f"{c}.{f}"]) == getattr(getattr(_lib, py), f).offset, (c, f)
-
-
-def test_lowrate_long_exports_every_declared_symbol_and_shares_none():
-    from audio_inpainting_diffusion_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "aid_lowrate_long.h")).read()
-    declared = set(re.findall(r"^\s*(?:int|void)\s+(aid_\w+)\s*\(", hdr, flags=re.M))
-    assert declared == set(_lib.LOWRATE_LONG_EXPORTS) == {"aid_lowrate_long_abi_version", "aid_rate_observed", "aid_lowrate_gather"}
-    assert not declared & (set(_lib.EXPORTS) | set(_lib.DEGRADE_EXPORTS) | set(_lib.PHASE_EXPORTS) | set(_lib.AR_EXPORTS) | set(_lib.RESTORE_EXPORTS)
-                           | set(_lib.DECLIP_EXPORTS) | set(_lib.RESAMPLE_OP_EXPORTS) | set(_lib.BWE_LONG_EXPORTS))
-    so = os.path.join(ROOT, "audio_inpainting_diffusion_amd", "libaid_hip.so")
-    if not os.path.exists(so):
-        import build
-        build.build()
-    lib = ctypes.CDLL(so)
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in aid_lowrate_long.h but not exported"
-    assert _lib.lib().aid_lowrate_long_abi_version() == _lib.AID_LOWRATE_LONG_ABI_VERSION
-    assert _lib.lib().aid_abi_version() == 14 and _lib.lib().aid_bwe_long_abi_version() == 1
 
 
 # ---- the grid ------------------------------------------------------------------------------------------------------------------------

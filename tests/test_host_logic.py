@@ -1,6 +1,6 @@
 """CPU tests (no GPU): host-side logic of the product package and the C-ABI surface.
 
- * libaid_hip.so loads here and exports every symbol include/aid_kernels.h declares (no compute calls);
+ * libaid_hip.so loads here and answers its host queries (no compute calls; the C ABI itself: tests/test_abi_host.py);
  * the product's vectorised CQT plan equals the oracle's band-by-band design, and a numpy emulation of the
    device algorithm (gather * window -> power-of-two inverse FFT; FFT * dual window -> overlap-add) built
    from the plan's tables reproduces the oracle transform;
@@ -20,22 +20,8 @@ import torch
 from conftest import GOLDEN, ROOT, rel_l2
 
 
-def test_c_abi_exports_every_declared_symbol():
-    import ctypes
-    hdr = open(os.path.join(ROOT, "include", "aid_kernels.h")).read()
-    declared = set(re.findall(r"^\s*(?:int|int64_t|void|const char\*)\s+(aid_\w+)\s*\(", hdr, flags=re.M))
-    assert len(declared) >= 15
-    so = os.path.join(ROOT, "audio_inpainting_diffusion_amd", "libaid_hip.so")
-    if not os.path.exists(so):
-        import build
-        build.build()
-    lib = ctypes.CDLL(so)
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in aid_kernels.h but not exported"
-    lib.aid_abi_version.restype = ctypes.c_int
-    assert lib.aid_abi_version() == int(re.search(r"#define AID_ABI_VERSION (\d+)", hdr).group(1)) == 14
+def test_pack_dims_of_the_library():
     from audio_inpainting_diffusion_amd import _lib
-    assert set(_lib.EXPORTS) == declared
     a, b = _lib.pack_dims(2, 96)
     assert (a, b) == (32, 96)
     assert _lib.pack_dims(256, 256) == (256, 256) and _lib.pack_dims(40, 5120) == (64, 5120) and _lib.pack_dims(64, 192) == (64, 192)
@@ -347,39 +333,6 @@ def test_graft_entry_build_checks_the_header_abi_version():
     g.build()
 
 
-def test_header_compiles_as_c_and_struct_sizes_match_the_binding(tmp_path):
-    """include/aid_kernels.h is the C ABI: it must compile as plain C99, and every parameter struct must have the size the ctypes mirror in
-    _lib.py gives it (a drifted field list would shift every later field silently)."""
-    import ctypes
-    import shutil
-    import subprocess
-    from audio_inpainting_diffusion_amd import _lib
-    gcc = shutil.which("gcc")
-    if gcc is None:
-        pytest.skip("no gcc")
-    pairs = {"aid_view": "View", "aid_group_stats_params": "GroupStatsParams", "aid_conv2d_params": "Conv2dParams", "aid_resample_params": "ResampleParams",
-             "aid_attention_params": "AttentionParams", "aid_embed_params": "EmbedParams", "aid_modulation_params": "ModulationParams",
-             "aid_cqt_tables": "CqtTables", "aid_cqt_params": "CqtParams", "aid_cqt_gather_params": "CqtGatherParams", "aid_fft_pass_params": "FftPassParams",
-             "aid_axpby_params": "AxpbyParams", "aid_score_step_params": "ScoreStepParams", "aid_group_dot_params": "GroupDotParams",
-             "aid_norm_bwd_params": "NormBwdParams", "aid_attention_bwd_params": "AttentionBwdParams", "aid_guidance_seed_params": "GuidanceSeedParams",
-             "aid_row_norm_params": "RowNormParams", "aid_guidance_step_params": "GuidanceStepParams", "aid_set_rows_params": "SetRowsParams", "aid_resample_poly_params": "ResamplePolyParams", "aid_stft_params": "StftParams",
-             "aid_scale_act_params": "ScaleActParams", "aid_add2_params": "Add2Params", "aid_conv2d_wgrad_params": "WgradParams",
-             "aid_wino_gy_params": "WinoGyParams", "aid_pack_conv_weight_params": "PackConvWeightParams", "aid_wgrad_reduce_params": "WgradReduceParams",
-             "aid_channel_dot_params": "ChannelDotParams", "aid_relpos_bwd_params": "RelposBwdParams", "aid_scale_bwd_params": "ScaleBwdParams", "aid_modulation_bwd_params": "ModulationBwdParams",
-             "aid_embed_bwd_params": "EmbedBwdParams", "aid_wino2d_gemm_params": "Wino2dGemmParams", "aid_adam_params": "AdamParams", "aid_ema_params": "EmaParams", "aid_sumsq_params": "SumsqParams"}
-    hdr = open(os.path.join(ROOT, "include", "aid_kernels.h")).read()
-    declared = set(re.findall(r"\}\s*(aid_\w+)\s*;", hdr))
-    assert declared == set(pairs), declared ^ set(pairs)
-    src = tmp_path / "sizes.c"
-    src.write_text('#include <stdio.h>\n#include "aid_kernels.h"\nint main(void) {\n' +
-                   "".join(f'    printf("{c} %zu\\n", sizeof({c}));\n' for c in pairs) + "    return 0;\n}\n")
-    exe = tmp_path / "sizes"
-    subprocess.check_call([gcc, "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    out = dict(line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())
-    for c, py in pairs.items():
-        assert int(out[c]) == ctypes.sizeof(getattr(_lib, py)), (c, out[c], ctypes.sizeof(getattr(_lib, py)))
-
-
 def test_a_weighting_taps_match_the_reference_filter():
     """training.a_weighting_taps restates FIRFilter("aw") (utils/training_utils.py:94-120); golden from the imported reference (make_golden.py --only aweighting)."""
     from audio_inpainting_diffusion_amd.training import a_weighting_taps
@@ -434,6 +387,61 @@ def test_cpu_thread_placements_and_numa_binding_are_well_formed():
         torch.set_num_threads(threads0)
 
 
+def _c_tables(header):
+    """name -> the brace-initialiser table a ``#define`` of csrc/<header> holds, as a float64 array"""
+    hdr = open(os.path.join(ROOT, "audio_inpainting_diffusion_amd", "csrc", header)).read()
+
+    def macro(name):
+        body = re.search(r"#define %s (\{.*\})" % name, hdr).group(1)
+        return np.array(ast.literal_eval(body.replace("{", "[").replace("}", "]").replace("f,", ",").replace("f]", "]")), dtype=np.float64)
+    return macro
+
+
+@pytest.mark.parametrize("gen", ["gen_wino8", "gen_wino45"])
+def test_generators_reproduce_the_committed_winograd_headers(gen, tmp_path):
+    """tools/gen_wino8.py and tools/gen_wino45.py write csrc/aid_wino8.h and csrc/aid_wino45.h from winograd.cook_toom, the construction the weight
+    packs use: run on this tree they give the committed headers byte for byte."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(gen, os.path.join(ROOT, "tools", gen + ".py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    out = tmp_path / os.path.basename(mod.HEADER)
+    mod.main(str(out))
+    assert out.read_bytes() == open(mod.HEADER, "rb").read()
+
+
+def test_f45xf43_matrices_header_and_python_twin_agree():
+    """csrc/aid_wino45.h and _lib.wino45_matrices(): each axis reproduces its correlation in fp64; the header's G tables are the doubles themselves
+    (%.17g round-trips) and its B^T / A^T tables are the matrices rounded to float32 (%.9g round-trips)."""
+    from audio_inpainting_diffusion_amd import _lib
+    AFT, GF, BFT, ATT, GT, BTT = _lib.wino45_matrices()
+    rng = np.random.default_rng(5)
+    for AT, G, BT, m, r in ((AFT, GF, BFT, 4, 5), (ATT, GT, BTT, 4, 3)):
+        assert AT.shape == (m, m + r - 1) and G.shape == (m + r - 1, r) and BT.shape == (m + r - 1, m + r - 1)
+        d, w = rng.standard_normal(m + r - 1), rng.standard_normal(r)
+        ref = np.array([sum(w[k] * d[o + k] for k in range(r)) for o in range(m)])
+        assert np.abs(AT @ ((G @ w) * (BT @ d)) - ref).max() < 1e-10
+    macro = _c_tables("aid_wino45.h")
+    assert np.array_equal(macro("AID_W45_GF"), GF) and np.array_equal(macro("AID_W45_GT"), GT)
+    for name, M in (("AID_W45_BTF", BFT), ("AID_W45_BTT", BTT), ("AID_W45_ATF", AFT), ("AID_W45_ATT", ATT)):
+        assert np.array_equal(macro(name).astype(np.float32), M.astype(np.float32)), name
+
+
+def test_pack_forms_are_the_builders_forms_and_the_f43_pack_is_its_g():
+    """_lib.PACK_FORMS and network._FORMS speak of the same forms with the same number of planes; the F(4,3) pack, which applies its G row by row with
+    one division each as the device kernel does, is the product with the explicit _G43 up to the float32 rounding of the stored value."""
+    from audio_inpainting_diffusion_amd import _lib, network
+    assert set(network._FORMS) == set(_lib.PACK_FORMS)
+    for f, fm in network._FORMS.items():
+        assert (fm.taps or 5 * 3) == _lib.pack_planes(f), f
+    w = torch.randn(3, 7, 5, 3, generator=torch.Generator().manual_seed(43), dtype=torch.float64)
+    cip, cop = _lib.pack_dims(7, 3)
+    U = _lib.pack_conv_weight_form(w, 4)
+    ref = torch.einsum("xk,oihk->xhio", _lib._G43, w).reshape(30, 7, 3)
+    assert U.shape == (30, cip, cop) and U.dtype == torch.float32 and not U[:, 7:].any() and not U[:, :, 3:].any()
+    assert bool(((U[:, :7, :3].double() - ref).abs() <= 2.0 ** -24 * ref.abs() + 1e-15).all())
+
+
 def test_f83_matrices_header_and_python_twin_agree():
     """csrc/aid_wino8.h (generated by tools/gen_wino8.py, compiled into the kernels) and _lib.wino8_matrices() (weight packs, tests) describe the same
     F(8,3): y = A^T [(G w) * (B^T d)] reproduces the 3-tap correlation of 10 samples exactly in fp64, the header's fp32 constants are the rounded
@@ -449,11 +457,7 @@ def test_f83_matrices_header_and_python_twin_agree():
     sg = np.array([(-1.0) ** k for k in range(10)])
     for j in range(4):
         assert np.abs(BT[2 + 2 * j] - sg * BT[1 + 2 * j]).max() < 1e-12 and BT[1 + 2 * j][0] == 0 and BT[1 + 2 * j][9] == 0
-    hdr = open(os.path.join(ROOT, "audio_inpainting_diffusion_amd", "csrc", "aid_wino8.h")).read()
-
-    def macro(name):
-        body = re.search(r"#define %s (\{.*\})" % name, hdr).group(1)
-        return np.array(ast.literal_eval(body.replace("{", "[").replace("}", "]").replace("f,", ",").replace("f]", "]")), dtype=np.float64)
+    macro = _c_tables("aid_wino8.h")
     assert np.abs(macro("AID_W8_G") - G).max() < 1e-12
     assert np.abs(macro("AID_W8_BT0") - BT[0][0::2]).max() < 1e-7
     assert np.abs(macro("AID_W8_BTE") - np.stack([BT[1 + 2 * j][2::2] for j in range(4)])).max() < 1e-7

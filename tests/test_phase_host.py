@@ -1,55 +1,9 @@
-"""CPU tests (no GPU) of phase retrieval (include/aid_phase.h, audio_inpainting_diffusion_amd/phase.py, Sampler.predict_pr): the C ABI and
-its ctypes mirrors, the config lookup and the refusals that happen before any kernel runs."""
-import ctypes
-import os
-import re
-import shutil
-import subprocess
+"""CPU tests (no GPU) of phase retrieval (include/aid_phase.h, audio_inpainting_diffusion_amd/phase.py, Sampler.predict_pr):
+the config lookup and the refusals that happen before any kernel runs."""
 
 import pytest
 import torch
 
-from conftest import ROOT
-
-
-def test_phase_header_compiles_as_c_and_struct_sizes_match_the_binding(tmp_path):
-    from audio_inpainting_diffusion_amd import _lib
-    gcc = shutil.which("gcc")
-    if gcc is None:
-        pytest.skip("no gcc")
-    pairs = {"aid_stft_mag_params": "StftMagParams", "aid_matrix_norm_params": "MatrixNormParams"}
-    hdr = open(os.path.join(ROOT, "include", "aid_phase.h")).read()
-    assert set(re.findall(r"\}\s*(aid_\w+)\s*;", hdr)) == set(pairs)
-    assert int(re.search(r"#define AID_PHASE_ABI_VERSION (\d+)", hdr).group(1)) == _lib.AID_PHASE_ABI_VERSION
-    src = tmp_path / "sizes.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "aid_phase.h"\nint main(void) {\n' +
-                   "".join(f'    printf("{c} %zu\\n", sizeof({c}));\n' for c in pairs) +
-                   "".join(f'    printf("{c}.{f} %zu\\n", offsetof({c}, {f}));\n' for c, py in pairs.items() for f, _ in getattr(_lib, py)._fields_) +
-                   "    return 0;\n}\n")
-    exe = tmp_path / "sizes"
-    subprocess.check_call([gcc, "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    out = dict(line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())
-    for c, py in pairs.items():
-        cls = getattr(_lib, py)
-        assert int(out[c]) == ctypes.sizeof(cls), (c, out[c], ctypes.sizeof(cls))
-        for f, _ in cls._fields_:
-            assert int(out[f"{c}.{f}"]) == getattr(cls, f).offset, (c, f)
-
-
-def test_phase_exports_every_declared_symbol_and_the_lists_are_disjoint():
-    from audio_inpainting_diffusion_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "aid_phase.h")).read()
-    declared = set(re.findall(r"^\s*(?:int|void)\s+(aid_\w+)\s*\(", hdr, flags=re.M))
-    assert declared == set(_lib.PHASE_EXPORTS)
-    assert not declared & set(_lib.EXPORTS) and not declared & set(_lib.DEGRADE_EXPORTS)
-    so = os.path.join(ROOT, "audio_inpainting_diffusion_amd", "libaid_hip.so")
-    if not os.path.exists(so):
-        import build
-        build.build()
-    lib = ctypes.CDLL(so)
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in aid_phase.h but not exported"
-    assert _lib.lib().aid_phase_abi_version() == _lib.AID_PHASE_ABI_VERSION
 
 
 def test_hamming_window_and_observation_shape_match_torch():

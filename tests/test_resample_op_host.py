@@ -1,18 +1,12 @@
 """CPU tests (no GPU) of the resampling degradation of bandwidth extension (include/aid_resample_op.h, degrade.SincResample,
 Sampler.predict_bwe(..., "resample")): the ratio rule, the host tables and their support ranges, the adjoint gather over them
-against autograd through the oracle's resampler, the C ABI and its ctypes mirror, and the refusals."""
-import ctypes
+against autograd through the oracle's resampler, and the refusals."""
 import math
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
 
 RATIOS = [(2, 1), (5, 2), (3, 2), (57, 50), (1, 2), (147, 100), (160, 147), (320, 147)]
 ADJOINT_CASES = [(2, 1, 37), (5, 2, 41), (147, 100, 300), (147, 100, 146), (3, 1, 2), (2, 1, 1)]
@@ -94,46 +88,6 @@ def test_gather_over_the_ranges_is_the_adjoint_of_the_oracle_resampler(o, n, L):
     err = float(np.linalg.norm(got - ref.numpy()) / np.linalg.norm(ref.numpy()))
     print(f"adjoint gather {o}:{n} L = {L}: rel-L2 vs autograd through the oracle = {err:.2e}")
     assert err <= 1e-6                                          # the project's bound for these operators; the table's float32 rounding is 6e-8
-
-
-# ---- C ABI ---------------------------------------------------------------------------------------------------------------------------
-def test_resample_op_header_compiles_as_c_and_struct_size_matches_the_binding(tmp_path):
-    from audio_inpainting_diffusion_amd import _lib
-    gcc = shutil.which("gcc")
-    if gcc is None:
-        pytest.skip("no gcc")
-    pairs = {"aid_resample_poly_adj_params": "ResamplePolyAdjParams"}
-    hdr = open(os.path.join(ROOT, "include", "aid_resample_op.h")).read()
-    assert set(re.findall(r"\}\s*(aid_\w+)\s*;", hdr)) == set(pairs)
-    assert int(re.search(r"#define AID_RESAMPLE_OP_ABI_VERSION (\d+)", hdr).group(1)) == _lib.AID_RESAMPLE_OP_ABI_VERSION
-    src = tmp_path / "sizes.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "aid_resample_op.h"\nint main(void) {\n' +
-                   "".join(f'    printf("{c} %zu\\n", sizeof({c}));\n' for c in pairs) +
-                   '    printf("g_ld %zu\\n", offsetof(aid_resample_poly_adj_params, g_ld));\n'
-                   '    printf("K %zu\\n", offsetof(aid_resample_poly_adj_params, K));\n    return 0;\n}\n')
-    exe = tmp_path / "sizes"
-    subprocess.check_call([gcc, "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    out = dict(line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())
-    for c, py in pairs.items():
-        assert int(out[c]) == ctypes.sizeof(getattr(_lib, py)), (c, out[c], ctypes.sizeof(getattr(_lib, py)))
-    assert int(out["g_ld"]) == _lib.ResamplePolyAdjParams.g_ld.offset and int(out["K"]) == _lib.ResamplePolyAdjParams.K.offset
-
-
-def test_resample_op_exports_every_declared_symbol():
-    from audio_inpainting_diffusion_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "aid_resample_op.h")).read()
-    declared = set(re.findall(r"^\s*(?:int|void)\s+(aid_\w+)\s*\(", hdr, flags=re.M))
-    assert declared == set(_lib.RESAMPLE_OP_EXPORTS) and "aid_resample_poly_adj" in declared
-    assert not declared & (set(_lib.EXPORTS) | set(_lib.DEGRADE_EXPORTS) | set(_lib.PHASE_EXPORTS) | set(_lib.AR_EXPORTS) |
-                           set(_lib.RESTORE_EXPORTS) | set(_lib.DECLIP_EXPORTS))
-    so = os.path.join(ROOT, "audio_inpainting_diffusion_amd", "libaid_hip.so")
-    if not os.path.exists(so):
-        import build
-        build.build()
-    lib = ctypes.CDLL(so)
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in aid_resample_op.h but not exported"
-    assert _lib.lib().aid_resample_op_abi_version() == _lib.AID_RESAMPLE_OP_ABI_VERSION
 
 
 # ---- the operator's geometry and the refusals (all raised before anything touches a GPU) -----------------------------------------------

@@ -1,17 +1,11 @@
 """CPU tests (no GPU) of whole-recording restoration (restore.py, include/aid_restore.h, Sampler.predict_inpainting_long,
-harness.restore_long): the window plan against the ownership rule restated here, the C ABI and its ctypes mirror, the refusals (all
+harness.restore_long): the window plan against the ownership rule restated here, the refusals (all
 raised before anything touches a GPU) and the smoothed mask of a window whose gap touches an end of the window."""
-import ctypes
 import math
-import os
-import re
-import shutil
-import subprocess
 
 import pytest
 import torch
 
-from conftest import ROOT
 
 CASES = [(1000, 256, 64), (1001, 256, 1), (2500, 256, 127), (100, 256, 64), (256, 256, 64)]
 
@@ -108,46 +102,6 @@ def test_plan_refuses_an_overlap_outside_its_range():
         restore_plan(torch.zeros(2, 1000), 256, 64, R=3)
     with pytest.raises(_lib.AidError):
         restore_plan(torch.zeros(2, 3, 1000), 256, 64)
-
-
-# ---- C ABI ---------------------------------------------------------------------------------------------------------------------------
-def test_restore_header_compiles_as_c_and_struct_sizes_match_the_binding(tmp_path):
-    from audio_inpainting_diffusion_amd import _lib
-    gcc = shutil.which("gcc")
-    if gcc is None:
-        pytest.skip("no gcc")
-    pairs = {"aid_window_gather_params": "WindowGatherParams", "aid_window_scatter_params": "WindowScatterParams"}
-    hdr = open(os.path.join(ROOT, "include", "aid_restore.h")).read()
-    assert set(re.findall(r"\}\s*(aid_\w+)\s*;", hdr)) == set(pairs)
-    assert int(re.search(r"#define AID_RESTORE_ABI_VERSION (\d+)", hdr).group(1)) == _lib.AID_RESTORE_ABI_VERSION
-    assert int(re.search(r"#define AID_RESTORE_JOB_FIELDS (\d+)", hdr).group(1)) == _lib.AID_RESTORE_JOB_FIELDS
-    src = tmp_path / "sizes.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "aid_restore.h"\nint main(void) {\n' +
-                   "".join(f'    printf("{c} %zu\\n", sizeof({c}));\n' for c in pairs) +
-                   '    printf("mask_ld %zu\\n", offsetof(aid_window_gather_params, mask_ld));\n'
-                   '    printf("out_ld %zu\\n", offsetof(aid_window_scatter_params, out_ld));\n    return 0;\n}\n')
-    exe = tmp_path / "sizes"
-    subprocess.check_call([gcc, "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    out = dict(line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())
-    for c, py in pairs.items():
-        assert int(out[c]) == ctypes.sizeof(getattr(_lib, py)), (c, out[c], ctypes.sizeof(getattr(_lib, py)))
-    assert int(out["mask_ld"]) == _lib.WindowGatherParams.mask_ld.offset and int(out["out_ld"]) == _lib.WindowScatterParams.out_ld.offset
-
-
-def test_restore_exports_every_declared_symbol():
-    from audio_inpainting_diffusion_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "aid_restore.h")).read()
-    declared = set(re.findall(r"^\s*(?:int|void)\s+(aid_\w+)\s*\(", hdr, flags=re.M))
-    assert declared == set(_lib.RESTORE_EXPORTS) and {"aid_window_gather", "aid_window_scatter"} <= declared
-    assert not declared & (set(_lib.EXPORTS) | set(_lib.DEGRADE_EXPORTS) | set(_lib.PHASE_EXPORTS) | set(_lib.AR_EXPORTS))
-    so = os.path.join(ROOT, "audio_inpainting_diffusion_amd", "libaid_hip.so")
-    if not os.path.exists(so):
-        import build
-        build.build()
-    lib = ctypes.CDLL(so)
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in aid_restore.h but not exported"
-    assert _lib.lib().aid_restore_abi_version() == _lib.AID_RESTORE_ABI_VERSION
 
 
 # ---- refusals that need no GPU, the harness wrapper, the smoothed mask of a window -----------------------------------------------------

@@ -1,21 +1,15 @@
 """CPU tests (no GPU) of spectrogram inpainting of whole recordings (spec_long.py, include/aid_spec_long.h,
-Sampler.predict_spectrogram_inpainting_long, harness.spectrogram_inpainting_long): the C ABI and its ctypes mirror, the computable-frame
+Sampler.predict_spectrogram_inpainting_long, harness.spectrogram_inpainting_long): the computable-frame
 rule and the sample states against brute force, the hop-aligned grid and its ownership, the exactness of the computable frames and of the
 state-0 samples of a window in float64, the job rule, the seed rule, and the refusals, all raised before anything touches a GPU.
 
 The float64 reference of the recording's operator (``rec_operator64``) and of the window's (``window_c64``, ``window_apply64``) is the formula
 of include/aid_spec_long.h written with torch, so autograd gives the exact VJP; tests/test_gpu_spec_long.py imports them."""
-import ctypes
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
 
 # (N, L, end, n_fft, hop)
 SPEC_CASES = [(5000, 1200, 300, 64, 16), (3777, 1000, 260, 64, 16), (2048, 1024, 260, 64, 16), (4000, 1100, 150, 32, 8), (900, 1000, 300, 64, 16),
@@ -117,53 +111,6 @@ def rect_mask(N, n_fft, hop, t_lo, t_hi, f_lo=3, f_hi=None):
     m = torch.ones(n_fft // 2 + 1, 1 + Np // hop)
     m[f_lo:(n_fft // 4 if f_hi is None else f_hi), t_lo:t_hi] = 0
     return m
-
-
-# ---- C ABI ---------------------------------------------------------------------------------------------------------------------------
-def test_spec_long_header_compiles_as_c_and_struct_sizes_match_the_binding(tmp_path):
-    from audio_inpainting_diffusion_amd import _lib
-    gcc = shutil.which("gcc")
-    if gcc is None:
-        pytest.skip("no gcc")
-    pairs = {"aid_stft_mask_observed_params": "StftMaskObservedParams", "aid_spec_gather_params": "SpecGatherParams"}
-    hdr = open(os.path.join(ROOT, "include", "aid_spec_long.h")).read()
-    assert set(re.findall(r"\}\s*(aid_\w+)\s*;", hdr)) == set(pairs)
-    assert int(re.search(r"#define AID_SPEC_LONG_ABI_VERSION (\d+)", hdr).group(1)) == _lib.AID_SPEC_LONG_ABI_VERSION == 1
-    assert int(re.search(r"#define AID_SPEC_ITEM_FIELDS (\d+)", hdr).group(1)) == _lib.AID_SPEC_ITEM_FIELDS == 3
-    fields = {"aid_stft_mask_observed_params": ("x", "y", "state", "items", "window", "twiddle", "inv_env", "mask", "frames", "out", "L", "Np", "x_ld", "y_ld",
-                                                "state_ld", "out_ld", "mask_sB", "mask_ld", "B", "Rm", "n_fft", "hop", "n_frames", "mode"),
-              "aid_spec_gather_params": ("rec", "out", "y", "state", "items", "jobs", "L", "N", "Np", "rec_ld", "out_ld", "J", "R", "n_fft", "hop", "n_frames")}
-    assert all(tuple(n for n, _ in getattr(_lib, py)._fields_) == fields[c] for c, py in pairs.items())
-    src = tmp_path / "sizes.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "aid_spec_long.h"\nint main(void) {\n' +
-                   "".join(f'    printf("{c} %zu\\n", sizeof({c}));\n' for c in pairs) +
-                   "".join(f'    printf("{c}.{f} %zu\\n", offsetof({c}, {f}));\n' for c, fs in fields.items() for f in fs) + "    return 0;\n}\n")
-    exe = tmp_path / "sizes"
-    subprocess.check_call([gcc, "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    out = dict(line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())
-    for c, py in pairs.items():
-        assert int(out[c]) == ctypes.sizeof(getattr(_lib, py)), (c, out[c], ctypes.sizeof(getattr(_lib, py)))
-        for f in fields[c]:
-            assert int(out[f"{c}.{f}"]) == getattr(getattr(_lib, py), f).offset, (c, f)
-
-
-def test_spec_long_exports_every_declared_symbol_and_shares_none():
-    from audio_inpainting_diffusion_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "aid_spec_long.h")).read()
-    declared = set(re.findall(r"^\s*(?:int|void)\s+(aid_\w+)\s*\(", hdr, flags=re.M))
-    assert declared == set(_lib.SPEC_LONG_EXPORTS) == {"aid_spec_long_abi_version", "aid_stft_mask_observed", "aid_spec_gather"}
-    assert not declared & (set(_lib.EXPORTS) | set(_lib.DEGRADE_EXPORTS) | set(_lib.PHASE_EXPORTS) | set(_lib.AR_EXPORTS) | set(_lib.RESTORE_EXPORTS)
-                           | set(_lib.DECLIP_EXPORTS) | set(_lib.RESAMPLE_OP_EXPORTS) | set(_lib.BWE_LONG_EXPORTS) | set(_lib.LOWRATE_LONG_EXPORTS)
-                           | set(_lib.PHASE_LONG_EXPORTS))
-    so = os.path.join(ROOT, "audio_inpainting_diffusion_amd", "libaid_hip.so")
-    if not os.path.exists(so):
-        import build
-        build.build()
-    lib = ctypes.CDLL(so)
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in aid_spec_long.h but not exported"
-    assert _lib.lib().aid_spec_long_abi_version() == _lib.AID_SPEC_LONG_ABI_VERSION
-    assert _lib.lib().aid_abi_version() == 14 and _lib.lib().aid_phase_long_abi_version() == 1
 
 
 # ---- the computable-frame rule and the states ----------------------------------------------------------------------------------------
