@@ -161,5 +161,5 @@ def bwe_passes(sampler, y: torch.Tensor, filt, filt_type: str, L: int, end: int,
     def predict(win, c0, c1):
         yw, kw = (t[c0:c1] for t in win)
         return sampler.predict_resample(yw, (c1 - c0, L), FIRObserved(dtaps, kw))
-    restore.run_passes(sampler, out, (jobs_A, jobs_B), L - end, max_batch, seeds, lambda table: bwe_gather(y, out, table, L, K), predict)
+    restore.run_passes(sampler, out, (jobs_A, jobs_B), L - end, max_batch, seeds, lambda table: bwe_gather(y, out, table, L, K), predict, L=L)
     return out

@@ -132,12 +132,12 @@ def declip_passes(sampler, y: torch.Tensor, clip, L: int, end: int, max_batch: i
     levels = check_declip_args(y, clip, L, end, max_batch, seeds)
     jobs_A, jobs_B, _ = declip_plan(y, levels, L, end)
     out = y.clone(memory_format=torch.contiguous_format)
-    if not (jobs_A or jobs_B):
+    if restore.no_jobs(jobs_A, jobs_B):
         return out
     dclip = torch.from_numpy(levels).to(y.device)
 
     def predict(win, c0, c1):
         yw, kw, cw = (t[c0:c1] for t in win)
         return sampler.predict_resample(yw, (c1 - c0, L), ClipObserved(kw, cw))
-    restore.run_passes(sampler, out, (jobs_A, jobs_B), L - end, max_batch, seeds, lambda table: declip_gather(y, out, dclip, table, L), predict)
+    restore.run_passes(sampler, out, (jobs_A, jobs_B), L - end, max_batch, seeds, lambda table: declip_gather(y, out, dclip, table, L), predict, L=L)
     return out

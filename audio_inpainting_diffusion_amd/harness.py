@@ -143,9 +143,14 @@ def generate_long(sampler, n_items: int, n_windows: int, seeds: Optional[Sequenc
 
 def _long_groups(who: str, files, seeds, device, key, call, flat: bool = True) -> List[torch.Tensor]:
     """The loop the *_long functions below share: the files with equal ``key(i)`` are stacked on ``device`` (``flat``: each as a 1-D waveform)
-    and go through ONE ``call(y, idx, key, seeds of idx)`` -> [len(idx), ...]; its rows come back in the order of ``files``."""
+    and go through ONE ``call(y, idx, key, seeds of idx)`` -> [len(idx), ...]; its rows come back in the order of ``files``.
+    Under an active process group ``seeds`` = None becomes dist.item_seeds(0, 0, len(files)), as in generate_long: the ranks share the windows
+    of every call (restore.run_passes), and a file's result must not depend on the world size."""
+    from . import dist as D
     if seeds is not None and len(seeds) != len(files):
         raise ValueError(f"{who}: {len(seeds)} seeds for {len(files)} files")
+    if seeds is None and D._active():
+        seeds = D.item_seeds(0, 0, len(files))
     groups = {}
     for i in range(len(files)):
         groups.setdefault(key(i), []).append(i)
@@ -163,7 +168,10 @@ def restore_long(sampler, files: Sequence[torch.Tensor], masks: Sequence[torch.T
     """Restore every 1-D waveform of ``files`` (any lengths) where its mask (same length; 1 = observed, 0 = gap, gaps anywhere) is 0 and return the
     full-length results on ``device``, in the order of ``files``.  Files of equal length go through ONE Sampler.predict_inpainting_long call, so
     their windows share the two batched passes; every other length is a call of its own.  ``seeds``: one RNG seed per file (file i's result then
-    depends on seeds[i] alone, not on the grouping)."""
+    depends on seeds[i] alone, not on the grouping).
+    Under an active process group (dist.init_distributed; weights made equal with dist.broadcast_parameters first) every rank passes the same
+    files and gets the full results: the windows of each pass are shared out over the ranks and exchanged once per pass, ``max_batch`` is
+    per rank, and ``seeds`` = None means dist.item_seeds(0, 0, len(files))."""
     if len(masks) != len(files):
         raise ValueError(f"restore_long: {len(masks)} masks for {len(files)} files")
 
@@ -180,7 +188,10 @@ def declip_long(sampler, files: Sequence[torch.Tensor], clip_values, seeds: Opti
     """Declip every 1-D waveform of ``files`` (any lengths), clipped at +-clip_values (one float for all files, or one per file), and return the
     full-length results on ``device``, in the order of ``files``.  Files of equal length go through ONE Sampler.predict_declipping_long call, so
     their windows share the two batched passes; every other length is a call of its own.  ``seeds``: one RNG seed per file (file i's result then
-    depends on seeds[i] alone, not on the grouping)."""
+    depends on seeds[i] alone, not on the grouping).
+    Under an active process group (dist.init_distributed; weights made equal with dist.broadcast_parameters first) every rank passes the same
+    files and gets the full results: the windows of each pass are shared out over the ranks and exchanged once per pass, ``max_batch`` is
+    per rank, and ``seeds`` = None means dist.item_seeds(0, 0, len(files))."""
     levels = [float(v) for v in (clip_values.reshape(-1).tolist() if torch.is_tensor(clip_values) else
                                  (list(clip_values) if hasattr(clip_values, "__len__") else [clip_values]))]
     if len(levels) not in (1, len(files)):
@@ -196,7 +207,10 @@ def bwe_long(sampler, files: Sequence[torch.Tensor], filt, filt_type: str = "fir
     """Bandwidth-extend every 1-D waveform of ``files`` (any lengths), each low-passed as a whole with the FIR taps ``filt`` (one filter for all
     files), and return the full-length results on ``device``, in the order of ``files``.  Files of equal length go through ONE
     Sampler.predict_bwe_long call, so their windows share the two batched passes; every other length is a call of its own.  ``seeds``: one RNG
-    seed per file (file i's result then depends on seeds[i] alone, not on the grouping)."""
+    seed per file (file i's result then depends on seeds[i] alone, not on the grouping).
+    Under an active process group (dist.init_distributed; weights made equal with dist.broadcast_parameters first) every rank passes the same
+    files and gets the full results: the windows of each pass are shared out over the ranks and exchanged once per pass, ``max_batch`` is
+    per rank, and ``seeds`` = None means dist.item_seeds(0, 0, len(files))."""
     return _long_groups("bwe_long", files, seeds, device, lambda i: files[i].numel(), lambda y, idx, _, sd: sampler.predict_bwe_long(
         y, filt, filt_type, max_batch=max_batch, seeds=sd))
 
@@ -207,7 +221,10 @@ def bwe_lowrate_long(sampler, files: Sequence[torch.Tensor], factor, filt_type: 
     high-rate results on ``device``, in the order of ``files``.  ``lengths``: the number of high-rate samples per file (None, for all files or for
     one: the largest consistent with the file).  Files of equal (low-rate length, length) go through ONE Sampler.predict_bwe_lowrate_long call, so
     their windows share the two batched passes; every other pair is a call of its own.  ``seeds``: one RNG seed per file (file i's result then
-    depends on seeds[i] alone, not on the grouping)."""
+    depends on seeds[i] alone, not on the grouping).
+    Under an active process group (dist.init_distributed; weights made equal with dist.broadcast_parameters first) every rank passes the same
+    files and gets the full results: the windows of each pass are shared out over the ranks and exchanged once per pass, ``max_batch`` is
+    per rank, and ``seeds`` = None means dist.item_seeds(0, 0, len(files))."""
     if lengths is not None and len(lengths) != len(files):
         raise ValueError(f"bwe_lowrate_long: {len(lengths)} lengths for {len(files)} files")
     return _long_groups("bwe_lowrate_long", files, seeds, device,
@@ -221,7 +238,10 @@ def pr_long(sampler, spectrograms: Sequence[torch.Tensor], lengths: Optional[Seq
     ``device``, in the order of ``spectrograms``.  ``lengths``: the number of samples per file (None, for all files or for one: the largest
     consistent with the file's frames).  Files of equal (T_rec, length) go through ONE Sampler.predict_pr_long call, so their windows share the
     two batched passes; every other pair is a call of its own.  ``seeds``: one RNG seed per file (file i's result then depends on seeds[i] alone,
-    not on the grouping)."""
+    not on the grouping).
+    Under an active process group (dist.init_distributed; weights made equal with dist.broadcast_parameters first) every rank passes the same
+    files and gets the full results: the windows of each pass are shared out over the ranks and exchanged once per pass, ``max_batch`` is
+    per rank, and ``seeds`` = None means dist.item_seeds(0, 0, len(files))."""
     if lengths is not None and len(lengths) != len(spectrograms):
         raise ValueError(f"pr_long: {len(lengths)} lengths for {len(spectrograms)} files")
 
@@ -238,7 +258,10 @@ def spectrogram_inpainting_long(sampler, files: Sequence[torch.Tensor], masks: S
     """Restore every waveform of ``files`` (any lengths; each masked as a whole in the STFT domain) under its mask [F, T_rec] of ``masks``
     (masks.spectral_mask(audio_len=len(file), ...)) and return the waveforms on ``device``, in the order of ``files``.  Files of equal length
     go through ONE Sampler.predict_spectrogram_inpainting_long call, so their windows share the two batched passes; every other length is a
-    call of its own.  ``seeds``: one RNG seed per file (file i's result then depends on seeds[i] alone, not on the grouping)."""
+    call of its own.  ``seeds``: one RNG seed per file (file i's result then depends on seeds[i] alone, not on the grouping).
+    Under an active process group (dist.init_distributed; weights made equal with dist.broadcast_parameters first) every rank passes the same
+    files and gets the full results: the windows of each pass are shared out over the ranks and exchanged once per pass, ``max_batch`` is
+    per rank, and ``seeds`` = None means dist.item_seeds(0, 0, len(files))."""
     if len(masks) != len(files):
         raise ValueError(f"spectrogram_inpainting_long: {len(masks)} masks for {len(files)} files")
 

@@ -232,5 +232,5 @@ def lowrate_passes(sampler, y: torch.Tensor, factor, filt_type: str, L: int, end
         yw, kw = (t[c0:c1] for t in win)
         return sampler.predict_resample(yw, (c1 - c0, L), RateObserved(tables, kw))
     restore.run_passes(sampler, out, (jobs_A, jobs_B), L - aligned_end(L, end, rate.orig), max_batch, seeds,
-                       lambda table: lowrate_gather(y, out, table, L, rate), predict)
+                       lambda table: lowrate_gather(y, out, table, L, rate), predict, L=L)
     return out

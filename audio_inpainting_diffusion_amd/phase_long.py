@@ -207,5 +207,5 @@ def pr_passes(sampler, y: torch.Tensor, win_size, hop_size, L: int, end: int, le
         yw, kw = (t[c0:c1] for t in win)
         return sampler.predict_resample(yw, (c1 - c0, L), STFTMagObserved(n_fft, hop, kw))
     restore.run_passes(sampler, out, (jobs_A, jobs_B), L - aligned_end(L, end, hop), max_batch, seeds,
-                       lambda table: pr_gather(y, out, table, L, n_fft, hop), predict)
+                       lambda table: pr_gather(y, out, table, L, n_fft, hop), predict, L=L)
     return out

@@ -21,6 +21,10 @@ This module is also the one home of what the other whole-recording modes share (
 spec_long.py; DESIGN.md, "The window scheme of whole recordings"): ``aligned_end`` / ``trimmed_windows`` / ``every_window_plan`` (the grid
 aligned to a period, the ownership trimmed by an operator's reach, every window a job), ``check_rows`` / ``check_batch`` (the refusals
 every mode raises), ``WindowOperator`` (the base of the five window operators) and ``run_passes`` (the pass loop).
+
+Under an active process group (dist.py) ``run_passes`` shares every pass out over the ranks -- contiguous shares, the unchanged seed rule,
+one all-gather of the windows per pass, the whole pass scattered on every rank -- after ``guard_ranks`` has compared what the ranks were
+given (``pass_digest``); host code only, the kernels and the sampler rounds are the same.
 """
 from __future__ import annotations
 
@@ -30,9 +34,11 @@ import torch
 
 from . import _lib
 from . import degrade
+from . import dist as _dist
 
 Job = Tuple[int, int, int, int, int, int]            # (recording r, start s, head, tail, lo, hi)
 SEED_STRIDE = 65536                                  # the job of window w of recording r runs with seed seeds[r] * SEED_STRIDE + w
+SCATTER_JOBS = 65535                                 # the most jobs one aid_window_scatter launch takes (csrc/aid_restore.hip)
 
 
 def restore_windows(N: int, L: int, end: int) -> List[Tuple[int, int, int, int, int]]:
@@ -198,12 +204,17 @@ def check_rows(y, what: str, nonempty: bool = False) -> None:
 
 
 def check_batch(y: torch.Tensor, max_batch, seeds, task: str) -> None:
-    """The last refusals of a whole-recording mode, after the mode's own: max_batch, one seed per recording and, judged last so that a host
-    tensor with any other fault is refused for that fault, the device of y.  All before anything is launched."""
+    """The last refusals of a whole-recording mode, after the mode's own: max_batch, one seed per recording -- under an active process group
+    (dist._active()) ``seeds`` = None is refused too: run_passes shares the windows out over the ranks, and only seeded jobs give a result
+    that does not depend on the world size -- and, judged last so that a host tensor with any other fault is refused for that fault, the
+    device of y.  All before anything is launched."""
     if isinstance(max_batch, bool) or not isinstance(max_batch, int) or max_batch < 1:
         raise _lib.AidError(f"max_batch must be an integer >= 1, got {max_batch!r}")
     if seeds is not None and len(seeds) != y.shape[0]:
         raise _lib.AidError(f"{len(seeds)} seeds for {y.shape[0]} recordings")
+    if seeds is None and _dist._active():
+        raise _lib.AidError(f"{task} under a process group needs seeds, one per recording: without them every rank would draw from its own global "
+                            "generator and the result would depend on the world size")
     if not y.is_cuda:
         raise _lib.AidError(f"{task} runs on the GPU only (no CPU fallback): y must be a float32 tensor on the GPU")
 
@@ -279,11 +290,85 @@ class WindowOperator(degrade._Operator):
         return fr
 
 
-def run_passes(sampler, out: torch.Tensor, passes: Sequence[Sequence[Job]], step: int, max_batch: int, seeds, gather, predict) -> None:
+def no_jobs(*passes) -> bool:
+    """True when no pass has a job and no process group is active: the recordings are returned as they are.  Under a group run_passes is
+    entered even without a job, for its guard: a rank that alone found no job must not leave the others waiting."""
+    return not any(passes) and not _dist._active()
+
+
+def _job_seeds(seeds, jobs: Sequence[Job], step: int):
+    """the seed rule: the job of window w = s // step of recording r runs with seeds[r] * SEED_STRIDE + w (None without seeds)"""
+    return None if seeds is None else [int(seeds[r]) * SEED_STRIDE + s // step for r, s, *_ in jobs]
+
+
+def pass_digest(out: torch.Tensor, passes: Sequence[Sequence[Job]], step: int, seeds, L) -> dict:
+    """What every rank of a process group must agree on before a sharded run_passes: the number of passes, the job count and a hash of the
+    job tuples per pass (tuples of ints hash identically in every process), the shape of ``out``, step, L, the seeds, and one float64
+    checksum of ``out`` -- a single reduction, read once (as hex text, so that a NaN compares equal to itself)."""
+    return {"passes": len(passes), "jobs": tuple(len(jobs) for jobs in passes),
+            "plan": tuple(hash(tuple(tuple(int(v) for v in job) for job in jobs)) for jobs in passes),
+            "shape": tuple(out.shape), "step": int(step), "L": int(L), "seeds": None if seeds is None else tuple(int(s) for s in seeds),
+            "recordings": float(out.sum(dtype=torch.float64)).hex()}
+
+
+def guard_ranks(digest: dict) -> None:
+    """One all_gather_object of ``digest``; unless all are equal, EVERY rank raises AidError naming the ranks that differ from rank 0 and the
+    fields they differ in -- a rank that was handed other files fails here, not in an all-gather of mismatched size."""
+    every = [None] * torch.distributed.get_world_size()
+    torch.distributed.all_gather_object(every, digest)
+    bad = [(r, sorted(k for k in every[0] if d.get(k) != every[0][k])) for r, d in enumerate(every) if d != every[0]]
+    if bad:
+        raise _lib.AidError("run_passes: the ranks of the process group were not given the same work: "
+                            + ", ".join(f"rank {r} differs from rank 0 in {', '.join(ks)}" for r, ks in bad)
+                            + " (every rank passes the same recordings, arguments and seeds)")
+
+
+def _sharded_passes(sampler, out, passes, step, max_batch, seeds, gather, predict, L) -> None:
+    """run_passes under an active process group (its docstring states the rule)."""
+    if L is None:
+        raise _lib.AidError("run_passes under a process group needs L, the length of a window: a rank without a job in a pass contributes [0, L]")
+    rank, world = torch.distributed.get_rank(), torch.distributed.get_world_size()
+    guard_ranks(pass_digest(out, passes, step, seeds, L))
+    keep = getattr(sampler, "seeds", None)
+    try:
+        for jobs in passes:
+            if not jobs:
+                continue
+            J = len(jobs)
+            table = job_table(jobs, out.device)
+            lo, hi = _dist.shard_range(J, rank, world)
+            parts = []
+            if hi > lo:
+                win = gather(table[lo:hi])                                   # (the closures index win relative to the table they were given)
+                for c0 in range(lo, hi, max_batch):
+                    c1 = min(hi, c0 + max_batch)
+                    sampler.seeds = _job_seeds(seeds, jobs[c0:c1], step)
+                    parts.append(predict(win, c0 - lo, c1 - lo))
+            local = parts[0] if len(parts) == 1 else torch.cat(parts) if parts else torch.zeros((0, int(L)), dtype=out.dtype, device=out.device)
+            allx = _dist.gather_outputs(local, J).contiguous()              # [J, L] in job order, the same on every rank
+            for j0 in range(0, J, SCATTER_JOBS):
+                window_scatter(allx[j0:j0 + SCATTER_JOBS], out, table[j0:j0 + SCATTER_JOBS])
+    finally:
+        sampler.seeds = keep
+
+
+def run_passes(sampler, out: torch.Tensor, passes: Sequence[Sequence[Job]], step: int, max_batch: int, seeds, gather, predict, L: Optional[int] = None) -> None:
     """The pass loop every whole-recording restoration shares.  Per non-empty job list of ``passes``: ``win = gather(table)`` (one launch for
     the whole pass), then per chunk [c0, c1) of at most ``max_batch`` jobs ``x = predict(win, c0, c1)`` -> [c1 - c0, L] and one
     aid_window_scatter launch of x into ``out``.  A later pass gathers what an earlier one scattered: same stream, in order.
-    ``sampler.seeds`` is set per chunk by the seed rule (None without seeds) and put back at the end."""
+    ``sampler.seeds`` is set per chunk by the seed rule (None without seeds) and put back at the end.
+
+    Under an active process group (dist._active()) of ``world`` ranks a pass is shared out; every rank calls with the same recordings, plan
+    and seeds, and with the same weights (call dist.broadcast_parameters first).  Before anything is launched one all_gather_object
+    compares pass_digest of every rank and all ranks raise if one differs (guard_ranks).  Then per pass of J jobs: rank k takes
+    [lo, hi) = dist.shard_range(J, k, world), gathers ``win = gather(table[lo:hi])`` (nothing when its share is empty) and calls
+    ``predict(win, c0 - lo, c1 - lo)`` per chunk of at most ``max_batch`` jobs of its share (max_batch is per rank), under the unchanged seed
+    rule, so a job's result does not depend on the rank or chunk it ran in; ONE dist.gather_outputs per pass returns [J, L] in job order on
+    every rank (a rank without a job contributes [0, L]: ``L`` is required here), and the whole pass is scattered, in launches of at most
+    65535 jobs.  After a pass ``out`` is identical on every rank, and the next pass gathers from it as before.  No collective inside
+    ``predict``, the sampler or the network."""
+    if _dist._active():
+        return _sharded_passes(sampler, out, passes, step, max_batch, seeds, gather, predict, L)
     tables = [(jobs, job_table(jobs, out.device)) for jobs in passes if jobs]
     keep = getattr(sampler, "seeds", None)
     try:
@@ -291,7 +376,7 @@ def run_passes(sampler, out: torch.Tensor, passes: Sequence[Sequence[Job]], step
             win = gather(table)
             for c0 in range(0, len(jobs), max_batch):
                 c1 = min(len(jobs), c0 + max_batch)
-                sampler.seeds = None if seeds is None else [int(seeds[r]) * SEED_STRIDE + s // step for r, s, *_ in jobs[c0:c1]]
+                sampler.seeds = _job_seeds(seeds, jobs[c0:c1], step)
                 window_scatter(predict(win, c0, c1).contiguous(), out, table[c0:c1])
     finally:
         sampler.seeds = keep
@@ -306,10 +391,10 @@ def restore_passes(sampler, y: torch.Tensor, mask: torch.Tensor, L: int, end: in
     R, N = y.shape
     jobs_A, jobs_B, _ = restore_plan(mask, L, end, R)
     out = y.clone(memory_format=torch.contiguous_format)
-    if not (jobs_A or jobs_B):
+    if no_jobs(jobs_A, jobs_B):
         return out
     dmask = mask.to(y.device, torch.float32).contiguous()
     run_passes(sampler, out, (jobs_A, jobs_B), L - end, max_batch, seeds,
                lambda table: window_gather(y, out, dmask, table, L),         # (pass B reads what pass A scattered)
-               lambda win, c0, c1: sampler.predict_inpainting(win[0][c0:c1], win[1][c0:c1]))
+               lambda win, c0, c1: sampler.predict_inpainting(win[0][c0:c1], win[1][c0:c1]), L=L)
     return out

@@ -512,7 +512,11 @@ class Sampler:
         hold a gap are inpainted as one batch, then the odd ones, conditioned on their neighbours' restored overlaps: two rounds of
         predict_inpainting in chunks of at most ``max_batch`` windows, one aid_window_gather launch per round and one aid_window_scatter launch per
         chunk.  Windows without a gap cost nothing; samples outside every gap's window stay the recording's.  ``seeds`` [R]: window w of recording
-        r runs with seed seeds[r] * 65536 + w, so a recording's result depends neither on the other recordings nor on max_batch."""
+        r runs with seed seeds[r] * 65536 + w, so a recording's result depends neither on the other recordings nor on max_batch.
+        Under an active process group (dist._active(); call dist.broadcast_parameters first, so that the ranks hold the same weights) every rank
+        calls with the same y, mask and seeds and gets the full [R, N]: rank k runs dist.shard_range of each round's windows in chunks of at most
+        ``max_batch`` (per rank), one dist.gather_outputs per round brings all windows to every rank, and each rank scatters the whole round
+        (restore.run_passes).  ``seeds`` = None is then refused, and ranks that were given different work raise before anything is launched."""
         from . import restore
         L, end = self._long_grid("predict_inpainting_long")
         mask = restore.check_restore_args(y, mask, L, end, max_batch, seeds)
@@ -526,7 +530,9 @@ class Sampler:
         is one predict_resample through declip_long.ClipObserved, which sees the recording through the clipper and takes the overlaps its
         neighbours restored as known.  tester.data_consistency off: guidance only, as the reference's declipping; "always" / "end": the
         projection onto the signals consistent with the clipped recording at every evaluation / once on the final state.  Windows without a
-        clipped sample cost nothing and keep the recording's samples."""
+        clipped sample cost nothing and keep the recording's samples.
+        Under an active process group the windows of each pass are shared out over the ranks as predict_inpainting_long states: the same
+        arguments and weights (dist.broadcast_parameters) on every rank, ``seeds`` required, ``max_batch`` per rank, the full result on every rank."""
         from . import declip_long
         L, end = self._long_grid("predict_declipping_long", "declipped")
         self._check_model()
@@ -541,7 +547,9 @@ class Sampler:
         end = int(overlap * L) >= 2 (K - 1)).  Each chunk of at most ``max_batch`` windows is one predict_resample through bwe_long.FIRObserved,
         which uses a filtered sample as an observation only where the window holds its whole filter support and takes the overlaps its
         neighbours restored as known.  tester.data_consistency off / "end" / "always" mean what they mean for predict_bwe.  A recording that
-        exists only at a low sample rate ("decimate", "resample") goes through predict_bwe_lowrate_long, whose grid is aligned to the input period."""
+        exists only at a low sample rate ("decimate", "resample") goes through predict_bwe_lowrate_long, whose grid is aligned to the input period.
+        Under an active process group the windows of each pass are shared out over the ranks as predict_inpainting_long states: the same
+        arguments and weights (dist.broadcast_parameters) on every rank, ``seeds`` required, ``max_batch`` per rank, the full result on every rank."""
         from . import bwe_long
         L, end = self._long_grid("predict_bwe_long")
         bwe_long.check_bwe_args(y, filt, filt_type, L, end, max_batch, seeds)
@@ -559,7 +567,9 @@ class Sampler:
         ``max_batch`` windows is one predict_resample through lowrate_long.RateObserved, which observes [B, L + ceil(new * L / orig)] entries
         per window: the overlaps its neighbours restored as known, and the low-rate samples whose whole kernel support the window holds.
         Guidance only: an identity ratio, rid and tester.data_consistency in use are refused (the reference's y + x - A(x) is undefined for an
-        operator that changes the length)."""
+        operator that changes the length).
+        Under an active process group the windows of each pass are shared out over the ranks as predict_inpainting_long states: the same
+        arguments and weights (dist.broadcast_parameters) on every rank, ``seeds`` required, ``max_batch`` per rank, the full result on every rank."""
         from . import lowrate_long
         L, end = self._long_grid("predict_bwe_lowrate_long", consistency="y + x - A(x) is undefined for an operator that changes the length")
         lowrate_long.check_lowrate_args(y, factor, filt_type, length, L, end, max_batch, seeds)
@@ -579,7 +589,9 @@ class Sampler:
         THE NORM DIFFERS FROM predict_pr: the operator declares no matrix_obs, so tester.posterior_sampling.norm = 2 / 1 is the element-wise norm
         over the whole observation row, not the induced matrix norm of one segment's spectrogram that the reference's dim=(1, 2) gives predict_pr --
         an induced matrix norm has no meaning across windows, and known samples do not fit in the matrix.
-        Guidance only: xi <= 0, rid and tester.data_consistency in use are refused."""
+        Guidance only: xi <= 0, rid and tester.data_consistency in use are refused.
+        Under an active process group the windows of each pass are shared out over the ranks as predict_inpainting_long states: the same
+        arguments and weights (dist.broadcast_parameters) on every rank, ``seeds`` required, ``max_batch`` per rank, the full result on every rank."""
         from . import phase_long
         L, end = self._long_grid("predict_pr_long", consistency="no data-consistency step exists for phase retrieval")
         if not self.xi > 0:
@@ -600,7 +612,9 @@ class Sampler:
         ``max_batch`` windows is one predict_resample through spec_long.SpectralMaskObserved, which uses a sample of y as an observation only
         where the window can compute every frame that covers it, and takes the overlaps its neighbours restored as known.
         tester.data_consistency off / "end" / "always" mean what they mean for predict_spectrogram_inpainting.  A window other than "hann", a
-        hop_length that does not divide n_fft and rid are refused."""
+        hop_length that does not divide n_fft and rid are refused.
+        Under an active process group the windows of each pass are shared out over the ranks as predict_inpainting_long states: the same
+        arguments and weights (dist.broadcast_parameters) on every rank, ``seeds`` required, ``max_batch`` per rank, the full result on every rank."""
         from . import spec_long
         L, end = self._long_grid("predict_spectrogram_inpainting_long")
         st = self.args.tester.spectrogram_inpainting.stft

@@ -277,7 +277,7 @@ def spec_passes(sampler, y: torch.Tensor, mask: torch.Tensor, n_fft, hop, L: int
     touched = touched_frames(dmask).cpu().numpy()                          # [1|R, T_rec]: reduced on the GPU; the one read-back, before pass A
     jobs_A, jobs_B = spec_plan(touched, R, N, L, end, n_fft, hop)
     out = y.clone(memory_format=torch.contiguous_format)
-    if not (jobs_A or jobs_B):
+    if restore.no_jobs(jobs_A, jobs_B):
         return out
     tables = spec_tables(N, n_fft, hop, win_length, y.device)
 
@@ -285,5 +285,5 @@ def spec_passes(sampler, y: torch.Tensor, mask: torch.Tensor, n_fft, hop, L: int
         yw, kw, iw = (t[c0:c1] for t in win)
         return sampler.predict_resample(yw, (c1 - c0, L), SpectralMaskObserved(dmask, n_fft, hop, kw, iw, tables))
     restore.run_passes(sampler, out, (jobs_A, jobs_B), L - aligned_end(L, end, hop), max_batch, seeds,
-                       lambda table: spec_gather(y, out, table, L, n_fft, hop), predict)
+                       lambda table: spec_gather(y, out, table, L, n_fft, hop), predict, L=L)
     return out
