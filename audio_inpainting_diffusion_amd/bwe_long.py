@@ -146,20 +146,32 @@ def check_bwe_args(y: torch.Tensor, filt, filt_type: str, L: int, end: int, max_
     return taps
 
 
+def bwe_group(y: torch.Tensor, filt, filt_type: str, L: int, end: int, max_batch: int = 8, seeds: Optional[Sequence[int]] = None) -> restore.Group:
+    """The part of a bandwidth extension that checks, plans and builds: y [R, N] recordings filtered with ``filt`` on the GPU ->
+    restore.Group(out = a copy of y, (jobs_A, jobs_B) of bwe_plan, the aid_bwe_gather closure).  The taps are shared by every group of a
+    call (``bwe_predict``); the states of a job travel in the gathered rows."""
+    K = check_bwe_args(y, filt, filt_type, L, end, max_batch, seeds).numel()
+    R, N = y.shape
+    out = y.clone(memory_format=torch.contiguous_format)
+    return restore.Group(out, bwe_plan(R, N, L, end, K), lambda table: bwe_gather(y, out, table, L, K))
+
+
+def bwe_predict(sampler, filt, L: int, device):
+    """predict(win, c0, c1) of a bandwidth extension: ``sampler.predict_resample`` through FIRObserved(taps on ``device``) over rows c0:c1 of the
+    gathered (y, k)"""
+    dtaps = fir_taps(filt).to(device)
+
+    def predict(win, c0, c1):
+        yw, kw = (t[c0:c1] for t in win)
+        return sampler.predict_resample(yw, (c1 - c0, L), FIRObserved(dtaps, kw))
+    return predict
+
+
 def bwe_passes(sampler, y: torch.Tensor, filt, filt_type: str, L: int, end: int, max_batch: int = 8, seeds: Optional[Sequence[int]] = None) -> torch.Tensor:
     """The two passes over ``sampler.predict_resample(yw [B, L], (B, L), FIRObserved(taps, kw [B, L])) -> [B, L]`` with B <= max_batch:
     y [R, N] recordings filtered with ``filt`` on the GPU (rows contiguous, any row stride) -> restored [R, N].  Per pass: one aid_bwe_gather
     launch, the sampler calls, one aid_window_scatter launch per call (restore.run_passes).  Recordings and result stay on the GPU.  Seeds
     as restore.restore_passes."""
-    taps = check_bwe_args(y, filt, filt_type, L, end, max_batch, seeds)
-    R, N = y.shape
-    K = taps.numel()
-    jobs_A, jobs_B = bwe_plan(R, N, L, end, K)
-    out = y.clone(memory_format=torch.contiguous_format)
-    dtaps = taps.to(y.device)
-
-    def predict(win, c0, c1):
-        yw, kw = (t[c0:c1] for t in win)
-        return sampler.predict_resample(yw, (c1 - c0, L), FIRObserved(dtaps, kw))
-    restore.run_passes(sampler, out, (jobs_A, jobs_B), L - end, max_batch, seeds, lambda table: bwe_gather(y, out, table, L, K), predict, L=L)
-    return out
+    group = bwe_group(y, filt, filt_type, L, end, max_batch, seeds)
+    restore.run_passes(sampler, group.out, group.passes, L - end, max_batch, seeds, group.gather, bwe_predict(sampler, filt, L, y.device), L=L)
+    return group.out

@@ -124,20 +124,31 @@ def declip_plan(y: torch.Tensor, levels, L: int, end: int):
     return restore.restore_plan(y.abs() < c[:, None], L, end, y.shape[0])
 
 
+def declip_group(y: torch.Tensor, clip, L: int, end: int, max_batch: int = 8, seeds: Optional[Sequence[int]] = None) -> restore.Group:
+    """The part of a declipping run that checks, plans and builds: y [R, N] clipped recordings on the GPU, clip a level or R levels ->
+    restore.Group(out = a copy of y, (jobs_A, jobs_B) of declip_plan, the aid_declip_gather closure).  The clip level of a job travels in
+    the gathered rows, so groups of other lengths and levels can share ``declip_predict``."""
+    levels = check_declip_args(y, clip, L, end, max_batch, seeds)
+    jobs_A, jobs_B, _ = declip_plan(y, levels, L, end)
+    out = y.clone(memory_format=torch.contiguous_format)
+    dclip = torch.from_numpy(levels).to(y.device) if jobs_A or jobs_B else None
+    return restore.Group(out, (jobs_A, jobs_B), lambda table: declip_gather(y, out, dclip, table, L))
+
+
+def declip_predict(sampler, L: int):
+    """predict(win, c0, c1) of a declipping run: ``sampler.predict_resample`` through ClipObserved over rows c0:c1 of the gathered (y, k, c)"""
+    def predict(win, c0, c1):
+        yw, kw, cw = (t[c0:c1] for t in win)
+        return sampler.predict_resample(yw, (c1 - c0, L), ClipObserved(kw, cw))
+    return predict
+
+
 def declip_passes(sampler, y: torch.Tensor, clip, L: int, end: int, max_batch: int = 8, seeds: Optional[Sequence[int]] = None) -> torch.Tensor:
     """The two passes over ``sampler.predict_resample(yw [B, L], (B, L), ClipObserved(kw [B, L], cw [B])) -> [B, L]`` with B <= max_batch:
     y [R, N] clipped recordings on the GPU (rows contiguous, any row stride), clip a level or R levels -> declipped [R, N].  Per pass: one
     aid_declip_gather launch, the sampler calls, one aid_window_scatter launch per call (restore.run_passes).  Recordings and result stay on
     the GPU; the plan is made on the host from |y| < c before pass A.  Seeds as restore.restore_passes."""
-    levels = check_declip_args(y, clip, L, end, max_batch, seeds)
-    jobs_A, jobs_B, _ = declip_plan(y, levels, L, end)
-    out = y.clone(memory_format=torch.contiguous_format)
-    if restore.no_jobs(jobs_A, jobs_B):
-        return out
-    dclip = torch.from_numpy(levels).to(y.device)
-
-    def predict(win, c0, c1):
-        yw, kw, cw = (t[c0:c1] for t in win)
-        return sampler.predict_resample(yw, (c1 - c0, L), ClipObserved(kw, cw))
-    restore.run_passes(sampler, out, (jobs_A, jobs_B), L - end, max_batch, seeds, lambda table: declip_gather(y, out, dclip, table, L), predict, L=L)
-    return out
+    group = declip_group(y, clip, L, end, max_batch, seeds)
+    if not restore.no_jobs(*group.passes):
+        restore.run_passes(sampler, group.out, group.passes, L - end, max_batch, seeds, group.gather, declip_predict(sampler, L), L=L)
+    return group.out

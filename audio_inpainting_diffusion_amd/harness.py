@@ -141,9 +141,11 @@ def generate_long(sampler, n_items: int, n_windows: int, seeds: Optional[Sequenc
     return D.gather_outputs(local, n_items)
 
 
-def _long_groups(who: str, files, seeds, device, key, call, flat: bool = True) -> List[torch.Tensor]:
+def _long_groups(who: str, files, seeds, device, key, call, flat: bool = True, pooled=None) -> List[torch.Tensor]:
     """The loop the *_long functions below share: the files with equal ``key(i)`` are stacked on ``device`` (``flat``: each as a 1-D waveform)
     and go through ONE ``call(y, idx, key, seeds of idx)`` -> [len(idx), ...]; its rows come back in the order of ``files``.
+    With ``pooled`` (pool=True) all stacks go through ONE ``pooled([(y, idx, key), ...], the seeds in that order)`` -> [one [len(idx), ...]
+    per stack] instead: Sampler.predict_long_pooled, where the windows of all lengths share the two batched passes.
     Under an active process group ``seeds`` = None becomes dist.item_seeds(0, 0, len(files)), as in generate_long: the ranks share the windows
     of every call (restore.run_passes), and a file's result must not depend on the world size."""
     from . import dist as D
@@ -155,8 +157,16 @@ def _long_groups(who: str, files, seeds, device, key, call, flat: bool = True) -
     for i in range(len(files)):
         groups.setdefault(key(i), []).append(i)
     out: List[Optional[torch.Tensor]] = [None] * len(files)
+    stack = lambda idx: torch.stack([(files[i].reshape(-1) if flat else files[i]).float() for i in idx]).to(device)      # noqa: E731
+    if pooled is not None:
+        every = pooled([(stack(idx), idx, k) for k, idx in groups.items()],
+                       None if seeds is None else [int(seeds[i]) for idx in groups.values() for i in idx])
+        for res, idx in zip(every, groups.values()):
+            for j, i in enumerate(idx):
+                out[i] = res[j]
+        return out
     for k, idx in groups.items():
-        y = torch.stack([(files[i].reshape(-1) if flat else files[i]).float() for i in idx]).to(device)
+        y = stack(idx)
         res = call(y, idx, k, None if seeds is None else [int(seeds[i]) for i in idx])
         for j, i in enumerate(idx):
             out[i] = res[j]
@@ -164,14 +174,17 @@ def _long_groups(who: str, files, seeds, device, key, call, flat: bool = True) -
 
 
 def restore_long(sampler, files: Sequence[torch.Tensor], masks: Sequence[torch.Tensor], seeds: Optional[Sequence[int]] = None, max_batch: int = 8,
-                 device="cuda") -> List[torch.Tensor]:
+                 device="cuda", pool: bool = False) -> List[torch.Tensor]:
     """Restore every 1-D waveform of ``files`` (any lengths) where its mask (same length; 1 = observed, 0 = gap, gaps anywhere) is 0 and return the
     full-length results on ``device``, in the order of ``files``.  Files of equal length go through ONE Sampler.predict_inpainting_long call, so
     their windows share the two batched passes; every other length is a call of its own.  ``seeds``: one RNG seed per file (file i's result then
     depends on seeds[i] alone, not on the grouping).
     Under an active process group (dist.init_distributed; weights made equal with dist.broadcast_parameters first) every rank passes the same
     files and gets the full results: the windows of each pass are shared out over the ranks and exchanged once per pass, ``max_batch`` is
-    per rank, and ``seeds`` = None means dist.item_seeds(0, 0, len(files))."""
+    per rank, and ``seeds`` = None means dist.item_seeds(0, 0, len(files)).
+    ``pool`` = True: the windows of ALL files, whatever their lengths, share the two batched passes (Sampler.predict_long_pooled): a chunk of
+    ``max_batch`` windows may span files, so a folder of short files of different lengths runs full batches; with seeds the results are
+    those of ``pool`` = False."""
     if len(masks) != len(files):
         raise ValueError(f"restore_long: {len(masks)} masks for {len(files)} files")
 
@@ -179,19 +192,24 @@ def restore_long(sampler, files: Sequence[torch.Tensor], masks: Sequence[torch.T
         if files[i].numel() != masks[i].numel():
             raise ValueError(f"restore_long: file {i} has {files[i].numel()} samples, its mask {masks[i].numel()}")
         return files[i].numel()
+    mask_of = lambda idx: torch.stack([masks[i].reshape(-1).float() for i in idx])                                     # noqa: E731
     return _long_groups("restore_long", files, seeds, device, key, lambda y, idx, _, sd: sampler.predict_inpainting_long(
-        y, torch.stack([masks[i].reshape(-1).float() for i in idx]), max_batch=max_batch, seeds=sd))
+        y, mask_of(idx), max_batch=max_batch, seeds=sd),
+        pooled=None if not pool else lambda gs, sd: sampler.predict_long_pooled("inpainting", [(y, mask_of(idx)) for y, idx, _ in gs], max_batch=max_batch, seeds=sd))
 
 
 def declip_long(sampler, files: Sequence[torch.Tensor], clip_values, seeds: Optional[Sequence[int]] = None, max_batch: int = 8,
-                device="cuda") -> List[torch.Tensor]:
+                device="cuda", pool: bool = False) -> List[torch.Tensor]:
     """Declip every 1-D waveform of ``files`` (any lengths), clipped at +-clip_values (one float for all files, or one per file), and return the
     full-length results on ``device``, in the order of ``files``.  Files of equal length go through ONE Sampler.predict_declipping_long call, so
     their windows share the two batched passes; every other length is a call of its own.  ``seeds``: one RNG seed per file (file i's result then
     depends on seeds[i] alone, not on the grouping).
     Under an active process group (dist.init_distributed; weights made equal with dist.broadcast_parameters first) every rank passes the same
     files and gets the full results: the windows of each pass are shared out over the ranks and exchanged once per pass, ``max_batch`` is
-    per rank, and ``seeds`` = None means dist.item_seeds(0, 0, len(files))."""
+    per rank, and ``seeds`` = None means dist.item_seeds(0, 0, len(files)).
+    ``pool`` = True: the windows of ALL files, whatever their lengths, share the two batched passes (Sampler.predict_long_pooled): a chunk of
+    ``max_batch`` windows may span files, so a folder of short files of different lengths runs full batches; with seeds the results are
+    those of ``pool`` = False."""
     levels = [float(v) for v in (clip_values.reshape(-1).tolist() if torch.is_tensor(clip_values) else
                                  (list(clip_values) if hasattr(clip_values, "__len__") else [clip_values]))]
     if len(levels) not in (1, len(files)):
@@ -199,24 +217,29 @@ def declip_long(sampler, files: Sequence[torch.Tensor], clip_values, seeds: Opti
     if len(levels) == 1:
         levels = levels * len(files)
     return _long_groups("declip_long", files, seeds, device, lambda i: files[i].numel(), lambda y, idx, _, sd: sampler.predict_declipping_long(
-        y, [levels[i] for i in idx], max_batch=max_batch, seeds=sd))
+        y, [levels[i] for i in idx], max_batch=max_batch, seeds=sd),
+        pooled=None if not pool else lambda gs, sd: sampler.predict_long_pooled("declipping", [(y, [levels[i] for i in idx]) for y, idx, _ in gs], max_batch=max_batch, seeds=sd))
 
 
 def bwe_long(sampler, files: Sequence[torch.Tensor], filt, filt_type: str = "firwin", seeds: Optional[Sequence[int]] = None, max_batch: int = 8,
-             device="cuda") -> List[torch.Tensor]:
+             device="cuda", pool: bool = False) -> List[torch.Tensor]:
     """Bandwidth-extend every 1-D waveform of ``files`` (any lengths), each low-passed as a whole with the FIR taps ``filt`` (one filter for all
     files), and return the full-length results on ``device``, in the order of ``files``.  Files of equal length go through ONE
     Sampler.predict_bwe_long call, so their windows share the two batched passes; every other length is a call of its own.  ``seeds``: one RNG
     seed per file (file i's result then depends on seeds[i] alone, not on the grouping).
     Under an active process group (dist.init_distributed; weights made equal with dist.broadcast_parameters first) every rank passes the same
     files and gets the full results: the windows of each pass are shared out over the ranks and exchanged once per pass, ``max_batch`` is
-    per rank, and ``seeds`` = None means dist.item_seeds(0, 0, len(files))."""
+    per rank, and ``seeds`` = None means dist.item_seeds(0, 0, len(files)).
+    ``pool`` = True: the windows of ALL files, whatever their lengths, share the two batched passes (Sampler.predict_long_pooled): a chunk of
+    ``max_batch`` windows may span files, so a folder of short files of different lengths runs full batches; with seeds the results are
+    those of ``pool`` = False."""
     return _long_groups("bwe_long", files, seeds, device, lambda i: files[i].numel(), lambda y, idx, _, sd: sampler.predict_bwe_long(
-        y, filt, filt_type, max_batch=max_batch, seeds=sd))
+        y, filt, filt_type, max_batch=max_batch, seeds=sd),
+        pooled=None if not pool else lambda gs, sd: sampler.predict_long_pooled("bwe", [y for y, _, _ in gs], max_batch=max_batch, seeds=sd, filt=filt, filt_type=filt_type))
 
 
 def bwe_lowrate_long(sampler, files: Sequence[torch.Tensor], factor, filt_type: str = "resample", lengths: Optional[Sequence[Optional[int]]] = None,
-                     seeds: Optional[Sequence[int]] = None, max_batch: int = 8, device="cuda") -> List[torch.Tensor]:
+                     seeds: Optional[Sequence[int]] = None, max_batch: int = 8, device="cuda", pool: bool = False) -> List[torch.Tensor]:
     """Bandwidth-extend every 1-D low-sample-rate waveform of ``files`` (any lengths; one ``factor`` and ``filt_type`` for all files) and return the
     high-rate results on ``device``, in the order of ``files``.  ``lengths``: the number of high-rate samples per file (None, for all files or for
     one: the largest consistent with the file).  Files of equal (low-rate length, length) go through ONE Sampler.predict_bwe_lowrate_long call, so
@@ -224,16 +247,21 @@ def bwe_lowrate_long(sampler, files: Sequence[torch.Tensor], factor, filt_type: 
     depends on seeds[i] alone, not on the grouping).
     Under an active process group (dist.init_distributed; weights made equal with dist.broadcast_parameters first) every rank passes the same
     files and gets the full results: the windows of each pass are shared out over the ranks and exchanged once per pass, ``max_batch`` is
-    per rank, and ``seeds`` = None means dist.item_seeds(0, 0, len(files))."""
+    per rank, and ``seeds`` = None means dist.item_seeds(0, 0, len(files)).
+    ``pool`` = True: the windows of ALL files, whatever their lengths, share the two batched passes (Sampler.predict_long_pooled): a chunk of
+    ``max_batch`` windows may span files, so a folder of short files of different lengths runs full batches; with seeds the results are
+    those of ``pool`` = False."""
     if lengths is not None and len(lengths) != len(files):
         raise ValueError(f"bwe_lowrate_long: {len(lengths)} lengths for {len(files)} files")
     return _long_groups("bwe_lowrate_long", files, seeds, device,
                         lambda i: (files[i].numel(), None if lengths is None or lengths[i] is None else int(lengths[i])),
-                        lambda y, idx, k, sd: sampler.predict_bwe_lowrate_long(y, factor, filt_type, length=k[1], max_batch=max_batch, seeds=sd))
+                        lambda y, idx, k, sd: sampler.predict_bwe_lowrate_long(y, factor, filt_type, length=k[1], max_batch=max_batch, seeds=sd),
+                        pooled=None if not pool else lambda gs, sd: sampler.predict_long_pooled("bwe_lowrate", [(y, k[1]) for y, _, k in gs], max_batch=max_batch, seeds=sd,
+                                                                                        factor=factor, filt_type=filt_type))
 
 
 def pr_long(sampler, spectrograms: Sequence[torch.Tensor], lengths: Optional[Sequence[Optional[int]]] = None, seeds: Optional[Sequence[int]] = None,
-            max_batch: int = 8, device="cuda") -> List[torch.Tensor]:
+            max_batch: int = 8, device="cuda", pool: bool = False) -> List[torch.Tensor]:
     """Retrieve the phase of every 2-D magnitude spectrogram [F, T_rec] of ``spectrograms`` (any numbers of frames) and return the waveforms on
     ``device``, in the order of ``spectrograms``.  ``lengths``: the number of samples per file (None, for all files or for one: the largest
     consistent with the file's frames).  Files of equal (T_rec, length) go through ONE Sampler.predict_pr_long call, so their windows share the
@@ -241,7 +269,10 @@ def pr_long(sampler, spectrograms: Sequence[torch.Tensor], lengths: Optional[Seq
     not on the grouping).
     Under an active process group (dist.init_distributed; weights made equal with dist.broadcast_parameters first) every rank passes the same
     files and gets the full results: the windows of each pass are shared out over the ranks and exchanged once per pass, ``max_batch`` is
-    per rank, and ``seeds`` = None means dist.item_seeds(0, 0, len(files))."""
+    per rank, and ``seeds`` = None means dist.item_seeds(0, 0, len(files)).
+    ``pool`` = True: the windows of ALL files, whatever their lengths, share the two batched passes (Sampler.predict_long_pooled): a chunk of
+    ``max_batch`` windows may span files, so a folder of short files of different lengths runs full batches; with seeds the results are
+    those of ``pool`` = False."""
     if lengths is not None and len(lengths) != len(spectrograms):
         raise ValueError(f"pr_long: {len(lengths)} lengths for {len(spectrograms)} files")
 
@@ -250,18 +281,23 @@ def pr_long(sampler, spectrograms: Sequence[torch.Tensor], lengths: Optional[Seq
             raise ValueError(f"pr_long: file {i} must be a magnitude spectrogram [F, T_rec], got {tuple(spectrograms[i].shape)}")
         return tuple(spectrograms[i].shape), None if lengths is None or lengths[i] is None else int(lengths[i])
     return _long_groups("pr_long", spectrograms, seeds, device, key,
-                        lambda y, idx, k, sd: sampler.predict_pr_long(y, length=k[1], max_batch=max_batch, seeds=sd), flat=False)
+                        lambda y, idx, k, sd: sampler.predict_pr_long(y, length=k[1], max_batch=max_batch, seeds=sd), flat=False,
+                        pooled=None if not pool else lambda gs, sd: sampler.predict_long_pooled("pr", [(y, k[1]) for y, _, k in gs], max_batch=max_batch, seeds=sd))
 
 
 def spectrogram_inpainting_long(sampler, files: Sequence[torch.Tensor], masks: Sequence[torch.Tensor], seeds: Optional[Sequence[int]] = None,
-                                max_batch: int = 8, device="cuda") -> List[torch.Tensor]:
+                                max_batch: int = 8, device="cuda", pool: bool = False) -> List[torch.Tensor]:
     """Restore every waveform of ``files`` (any lengths; each masked as a whole in the STFT domain) under its mask [F, T_rec] of ``masks``
     (masks.spectral_mask(audio_len=len(file), ...)) and return the waveforms on ``device``, in the order of ``files``.  Files of equal length
     go through ONE Sampler.predict_spectrogram_inpainting_long call, so their windows share the two batched passes; every other length is a
     call of its own.  ``seeds``: one RNG seed per file (file i's result then depends on seeds[i] alone, not on the grouping).
     Under an active process group (dist.init_distributed; weights made equal with dist.broadcast_parameters first) every rank passes the same
     files and gets the full results: the windows of each pass are shared out over the ranks and exchanged once per pass, ``max_batch`` is
-    per rank, and ``seeds`` = None means dist.item_seeds(0, 0, len(files))."""
+    per rank, and ``seeds`` = None means dist.item_seeds(0, 0, len(files)).
+    ``pool`` = True is refused: aid_stft_mask_observed reads one recording-shaped mask in place, so the windows of files with different
+    T_rec cannot share a launch (Sampler.predict_long_pooled says the same)."""
+    if pool:
+        return sampler.predict_long_pooled("spectrogram_inpainting", [])                   # (raises, with the reason)
     if len(masks) != len(files):
         raise ValueError(f"spectrogram_inpainting_long: {len(masks)} masks for {len(files)} files")
 

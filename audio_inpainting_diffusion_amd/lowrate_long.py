@@ -216,21 +216,40 @@ def check_lowrate_args(y: torch.Tensor, factor, filt_type: str, length, L: int, 
     return rate, N
 
 
+def lowrate_group(y: torch.Tensor, factor, filt_type: str, L: int, end: int, length=None, max_batch: int = 8,
+                  seeds: Optional[Sequence[int]] = None) -> restore.Group:
+    """The part of a bandwidth extension of low-rate recordings that checks, plans and builds: y [R, M] low-rate recordings on the GPU ->
+    restore.Group(out = zeros [R, N], (jobs_A, jobs_B) of lowrate_plan, the aid_lowrate_gather closure).  The ratio is shared by every group
+    of a call (``lowrate_step``, ``lowrate_predict``); the states of a job travel in the gathered rows."""
+    rate, N = check_lowrate_args(y, factor, filt_type, length, L, end, max_batch, seeds)
+    R = y.shape[0]
+    out = torch.zeros((R, N), dtype=torch.float32, device=y.device)          # (every sample is owned; pass B's heads and tails lie in ranges pass A owns)
+    return restore.Group(out, lowrate_plan(R, N, L, end, rate), lambda table: lowrate_gather(y, out, table, L, rate))
+
+
+def lowrate_step(factor, filt_type: str, L: int, end: int) -> int:
+    """the aligned step L - end' of the grid at this ratio"""
+    return L - aligned_end(L, end, rate_of(factor, filt_type).orig)
+
+
+def lowrate_predict(sampler, factor, filt_type: str, L: int, device):
+    """predict(win, c0, c1) of a bandwidth extension of low-rate recordings: ``sampler.predict_resample`` through RateObserved(the ratio's
+    tables on ``device``) over rows c0:c1 of the gathered (y, k)"""
+    tables = rate_tables(rate_of(factor, filt_type), device)
+
+    def predict(win, c0, c1):
+        yw, kw = (t[c0:c1] for t in win)
+        return sampler.predict_resample(yw, (c1 - c0, L), RateObserved(tables, kw))
+    return predict
+
+
 def lowrate_passes(sampler, y: torch.Tensor, factor, filt_type: str, L: int, end: int, length=None, max_batch: int = 8,
                    seeds: Optional[Sequence[int]] = None) -> torch.Tensor:
     """The two passes over ``sampler.predict_resample(yw [B, L + Mw], (B, L), RateObserved(tables, kw [B, L + Mw])) -> [B, L]`` with
     B <= max_batch: y [R, M] low-rate recordings on the GPU (rows contiguous, any row stride) -> restored [R, N] at the high rate.  Per pass:
     one aid_lowrate_gather launch, the sampler calls, one aid_window_scatter launch per call (restore.run_passes, with the aligned step
     L - end').  Recordings and result stay on the GPU.  Seeds as restore.restore_passes."""
-    rate, N = check_lowrate_args(y, factor, filt_type, length, L, end, max_batch, seeds)
-    R = y.shape[0]
-    jobs_A, jobs_B = lowrate_plan(R, N, L, end, rate)
-    out = torch.zeros((R, N), dtype=torch.float32, device=y.device)          # (every sample is owned; pass B's heads and tails lie in ranges pass A owns)
-    tables = rate_tables(rate, y.device)
-
-    def predict(win, c0, c1):
-        yw, kw = (t[c0:c1] for t in win)
-        return sampler.predict_resample(yw, (c1 - c0, L), RateObserved(tables, kw))
-    restore.run_passes(sampler, out, (jobs_A, jobs_B), L - aligned_end(L, end, rate.orig), max_batch, seeds,
-                       lambda table: lowrate_gather(y, out, table, L, rate), predict, L=L)
-    return out
+    group = lowrate_group(y, factor, filt_type, L, end, length, max_batch, seeds)
+    restore.run_passes(sampler, group.out, group.passes, lowrate_step(factor, filt_type, L, end), max_batch, seeds,
+                       group.gather, lowrate_predict(sampler, factor, filt_type, L, y.device), L=L)
+    return group.out

@@ -189,6 +189,27 @@ def check_pr_args(y: torch.Tensor, win_size, hop_size, length, L: int, end: int,
     return n_fft, hop, N
 
 
+def pr_group(y: torch.Tensor, win_size, hop_size, L: int, end: int, length=None, max_batch: int = 8,
+             seeds: Optional[Sequence[int]] = None) -> restore.Group:
+    """The part of a phase retrieval that checks, plans and builds: y [R, F, T_rec] magnitude spectrograms on the GPU (any strides; one copy
+    unless T_rec has unit stride) -> restore.Group(out = zeros [R, N], (jobs_A, jobs_B) of pr_plan, the aid_pr_gather closure).  win_size
+    and hop_size are shared by every group of a call (``pr_predict``); the states of a job travel in the gathered rows."""
+    n_fft, hop, N = check_pr_args(y, win_size, hop_size, length, L, end, max_batch, seeds)
+    R, F, T_rec = y.shape
+    if (T_rec > 1 and y.stride(2) != 1) or y.stride(1) < T_rec or y.stride(0) < (F - 1) * y.stride(1) + T_rec:
+        y = y.contiguous()                                                   # (torch.stft hands out [R, F, T] with frames strided: one copy, before pass A)
+    out = torch.zeros((R, N), dtype=torch.float32, device=y.device)          # (every sample is owned; pass B's heads and tails lie in ranges pass A owns)
+    return restore.Group(out, pr_plan(R, N, L, end, n_fft, hop), lambda table: pr_gather(y, out, table, L, n_fft, hop))
+
+
+def pr_predict(sampler, n_fft: int, hop: int, L: int):
+    """predict(win, c0, c1) of a phase retrieval: ``sampler.predict_resample`` through STFTMagObserved over rows c0:c1 of the gathered (y, k)"""
+    def predict(win, c0, c1):
+        yw, kw = (t[c0:c1] for t in win)
+        return sampler.predict_resample(yw, (c1 - c0, L), STFTMagObserved(n_fft, hop, kw))
+    return predict
+
+
 def pr_passes(sampler, y: torch.Tensor, win_size, hop_size, L: int, end: int, length=None, max_batch: int = 8,
               seeds: Optional[Sequence[int]] = None) -> torch.Tensor:
     """The two passes over ``sampler.predict_resample(yw [B, L + F*Tw], (B, L), STFTMagObserved(win_size, hop_size, kw [B, L + Tw])) -> [B, L]``
@@ -196,16 +217,8 @@ def pr_passes(sampler, y: torch.Tensor, win_size, hop_size, L: int, end: int, le
     stride) -> restored [R, N].  Per pass: one aid_pr_gather launch, the sampler
     calls, one aid_window_scatter launch per call (restore.run_passes, with the aligned step L - end').  Spectrograms and result stay on the
     GPU.  Seeds as restore.restore_passes."""
-    n_fft, hop, N = check_pr_args(y, win_size, hop_size, length, L, end, max_batch, seeds)
-    R, F, T_rec = y.shape
-    if (T_rec > 1 and y.stride(2) != 1) or y.stride(1) < T_rec or y.stride(0) < (F - 1) * y.stride(1) + T_rec:
-        y = y.contiguous()                                                   # (torch.stft hands out [R, F, T] with frames strided: one copy, before pass A)
-    jobs_A, jobs_B = pr_plan(R, N, L, end, n_fft, hop)
-    out = torch.zeros((R, N), dtype=torch.float32, device=y.device)          # (every sample is owned; pass B's heads and tails lie in ranges pass A owns)
-
-    def predict(win, c0, c1):
-        yw, kw = (t[c0:c1] for t in win)
-        return sampler.predict_resample(yw, (c1 - c0, L), STFTMagObserved(n_fft, hop, kw))
-    restore.run_passes(sampler, out, (jobs_A, jobs_B), L - aligned_end(L, end, hop), max_batch, seeds,
-                       lambda table: pr_gather(y, out, table, L, n_fft, hop), predict, L=L)
-    return out
+    group = pr_group(y, win_size, hop_size, L, end, length, max_batch, seeds)
+    n_fft, hop = phase.check_sizes(win_size, hop_size)
+    restore.run_passes(sampler, group.out, group.passes, L - aligned_end(L, end, hop), max_batch, seeds,
+                       group.gather, pr_predict(sampler, n_fft, hop, L), L=L)
+    return group.out

@@ -20,7 +20,9 @@ two HIP kernels of csrc/aid_restore.hip; ``restore_passes`` is the pass code, dr
 This module is also the one home of what the other whole-recording modes share (declip_long.py, bwe_long.py, lowrate_long.py, phase_long.py,
 spec_long.py; DESIGN.md, "The window scheme of whole recordings"): ``aligned_end`` / ``trimmed_windows`` / ``every_window_plan`` (the grid
 aligned to a period, the ownership trimmed by an operator's reach, every window a job), ``check_rows`` / ``check_batch`` (the refusals
-every mode raises), ``WindowOperator`` (the base of the five window operators) and ``run_passes`` (the pass loop).
+every mode raises), ``WindowOperator`` (the base of the five window operators) and ``run_passes`` (the pass loop).  ``run_pooled_passes`` is
+that loop over several ``Group`` records, one per recording length: the jobs of all lengths share the chunks of one pooled pass A and one
+pooled pass B; ``run_passes`` is its one-group case.
 
 Under an active process group (dist.py) ``run_passes`` shares every pass out over the ranks -- contiguous shares, the unchanged seed rule,
 one all-gather of the windows per pass, the whole pass scattered on every rank -- after ``guard_ranks`` has compared what the ranks were
@@ -28,7 +30,7 @@ given (``pass_digest``); host code only, the kernels and the sampler rounds are 
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence, Tuple
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -296,9 +298,21 @@ def no_jobs(*passes) -> bool:
     return not any(passes) and not _dist._active()
 
 
-def _job_seeds(seeds, jobs: Sequence[Job], step: int):
-    """the seed rule: the job of window w = s // step of recording r runs with seeds[r] * SEED_STRIDE + w (None without seeds)"""
-    return None if seeds is None else [int(seeds[r]) * SEED_STRIDE + s // step for r, s, *_ in jobs]
+class Group(NamedTuple):
+    """One set of equal-length recordings of a pooled run (run_pooled_passes): what a ``*_passes`` function hands to run_passes, and where
+    its recordings stand in the caller's list of seeds."""
+    out: torch.Tensor                                # [R_g, N_g], restored in place
+    passes: Sequence[Sequence[Job]]                  # (jobs_A, jobs_B); the r of a job is a row of ``out``
+    gather: Callable                                 # gather(table [J, 6]) -> the rows of the table's jobs, a tensor [J, ...] or a tuple of such
+    files: Optional[Sequence[int]] = None            # files[r]: the index of row r in ``seeds``; None: r itself
+
+
+def _job_seeds(seeds, jobs: Sequence[Job], step: int, files: Optional[Sequence[int]] = None):
+    """the seed rule: the job of window w = s // step of recording r runs with seeds[r] * SEED_STRIDE + w (None without seeds); with
+    ``files`` recording r is seeds[files[r]]"""
+    if seeds is None:
+        return None
+    return [int(seeds[r if files is None else files[r]]) * SEED_STRIDE + s // step for r, s, *_ in jobs]
 
 
 def pass_digest(out: torch.Tensor, passes: Sequence[Sequence[Job]], step: int, seeds, L) -> dict:
@@ -323,63 +337,133 @@ def guard_ranks(digest: dict) -> None:
                             + " (every rank passes the same recordings, arguments and seeds)")
 
 
-def _sharded_passes(sampler, out, passes, step, max_batch, seeds, gather, predict, L) -> None:
-    """run_passes under an active process group (its docstring states the rule)."""
-    if L is None:
-        raise _lib.AidError("run_passes under a process group needs L, the length of a window: a rank without a job in a pass contributes [0, L]")
-    rank, world = torch.distributed.get_rank(), torch.distributed.get_world_size()
-    guard_ranks(pass_digest(out, passes, step, seeds, L))
+def pooled_digest(groups: Sequence[Group], step: int, seeds, L) -> dict:
+    """pass_digest over all groups of a pooled run: its per-group fields as tuples over the groups (so a rank that was handed one other file
+    length differs in "shape"), the files of every group, and step, L and the seeds once."""
+    per = [pass_digest(g.out, g.passes, step, None, L) for g in groups]
+    d = {k: tuple(p[k] for p in per) for k in ("passes", "jobs", "plan", "shape", "recordings")}
+    d.update(files=tuple(None if g.files is None else tuple(int(i) for i in g.files) for g in groups),
+             step=int(step), L=int(L), seeds=None if seeds is None else tuple(int(s) for s in seeds))
+    return d
+
+
+def _cat_rows(wins: list):
+    """the gathered rows of several groups laid row-wise into one ``win`` (copies, bit-exact); one group's rows are used as they are"""
+    if len(wins) == 1:
+        return wins[0]
+    if isinstance(wins[0], (tuple, list)):
+        return tuple(torch.cat(ts) for ts in zip(*wins))
+    return torch.cat(wins)
+
+
+def _owned(bounds: Sequence[int], a: int, b: int):
+    """(group g, a_g, b_g) for every group with pooled jobs in [a, b): its jobs a_g:b_g, relative to the group's own job list"""
+    for g in range(len(bounds) - 1):
+        lo, hi = max(a, bounds[g]), min(b, bounds[g + 1])
+        if hi > lo:
+            yield g, lo - bounds[g], hi - bounds[g]
+
+
+def run_pooled_passes(sampler, groups: Sequence[Group], step: int, max_batch: int, seeds, predict, L: Optional[int] = None) -> None:
+    """The pass loop of every whole-recording restoration, over recordings of any lengths: ``groups`` holds one Group per length, and the jobs
+    of all groups share the sampler calls.  Per pass p the jobs of all groups, in group order and within a group ordered by recording and
+    window, are ONE list of J jobs.  Every group with jobs runs its own gather on its own table (one launch per group and pass), the gathered
+    rows are laid row-wise into one ``win`` (a window's row has the same length for every recording: it depends on L and the operator, not
+    on N), and per chunk [c0, c1) of at most ``max_batch`` pooled jobs -- a chunk may span recordings and groups -- ``x = predict(win, c0, c1)``
+    -> [c1 - c0, L] is scattered with one aid_window_scatter launch per group the chunk touches, into that group's ``out``.  A pass starts only
+    after every group's earlier pass has been scattered: same stream, in order.  Groups and passes without a job cost nothing.
+    ``sampler.seeds`` is set per chunk by the seed rule, seeds[group.files[r]] * SEED_STRIDE + w (None without seeds), and put back at the
+    end: a job's result depends on its seed alone, so the pooled result equals what the groups give one by one.
+
+    Under an active process group (dist._active()) of ``world`` ranks every rank calls with the same groups and seeds, and with the same
+    weights (call dist.broadcast_parameters first).  Before anything is launched one all_gather_object compares pooled_digest of every rank
+    and all ranks raise if one differs (guard_ranks).  Then per pass of J pooled jobs: rank k takes [lo, hi) = dist.shard_range(J, k, world),
+    gathers only the rows of its share, group by group, and calls ``predict`` per chunk of at most ``max_batch`` jobs of its share (max_batch
+    is per rank); ONE dist.gather_outputs per pass returns [J, L] in job order on every rank (a rank without a job contributes [0, L]: ``L``
+    is required here), and every rank scatters the whole pass group by group, in launches of at most 65535 jobs.  No collective inside
+    ``predict``, the sampler or the network."""
+    groups = list(groups)
+    if not groups:
+        return
+    n_pass = len(groups[0].passes)
+    if any(len(g.passes) != n_pass for g in groups):
+        raise _lib.AidError(f"run_pooled_passes: every group must hold the same number of passes, got {[len(g.passes) for g in groups]}")
+    sharded = _dist._active()
+    if sharded:
+        if L is None:
+            raise _lib.AidError("run_passes under a process group needs L, the length of a window: a rank without a job in a pass contributes [0, L]")
+        rank, world = torch.distributed.get_rank(), torch.distributed.get_world_size()
+        guard_ranks(pooled_digest(groups, step, seeds, L))
+    tables = [[job_table(g.passes[p], g.out.device) if g.passes[p] else None for g in groups] for p in range(n_pass)]
     keep = getattr(sampler, "seeds", None)
     try:
-        for jobs in passes:
-            if not jobs:
+        for p in range(n_pass):
+            bounds = [0]
+            for g in groups:
+                bounds.append(bounds[-1] + len(g.passes[p]))
+            J = bounds[-1]
+            if not J:
                 continue
-            J = len(jobs)
-            table = job_table(jobs, out.device)
-            lo, hi = _dist.shard_range(J, rank, world)
+            lo, hi = _dist.shard_range(J, rank, world) if sharded else (0, J)
             parts = []
             if hi > lo:
-                win = gather(table[lo:hi])                                   # (the closures index win relative to the table they were given)
+                # (the closures index win relative to the tables they were given: the pooled job j is row j - lo)
+                win = _cat_rows([groups[g].gather(tables[p][g][a:b]) for g, a, b in _owned(bounds, lo, hi)])
                 for c0 in range(lo, hi, max_batch):
                     c1 = min(hi, c0 + max_batch)
-                    sampler.seeds = _job_seeds(seeds, jobs[c0:c1], step)
-                    parts.append(predict(win, c0 - lo, c1 - lo))
-            local = parts[0] if len(parts) == 1 else torch.cat(parts) if parts else torch.zeros((0, int(L)), dtype=out.dtype, device=out.device)
-            allx = _dist.gather_outputs(local, J).contiguous()              # [J, L] in job order, the same on every rank
-            for j0 in range(0, J, SCATTER_JOBS):
-                window_scatter(allx[j0:j0 + SCATTER_JOBS], out, table[j0:j0 + SCATTER_JOBS])
+                    owned = list(_owned(bounds, c0, c1))
+                    sampler.seeds = None if seeds is None else [s for g, a, b in owned for s in _job_seeds(seeds, groups[g].passes[p][a:b], step, groups[g].files)]
+                    x = predict(win, c0 - lo, c1 - lo)
+                    if sharded:
+                        parts.append(x)
+                        continue
+                    x = x.contiguous()
+                    for g, a, b in owned:
+                        window_scatter(x[bounds[g] + a - c0:bounds[g] + b - c0], groups[g].out, tables[p][g][a:b])
+            if sharded:
+                out = groups[0].out
+                local = parts[0] if len(parts) == 1 else torch.cat(parts) if parts else torch.zeros((0, int(L)), dtype=out.dtype, device=out.device)
+                allx = _dist.gather_outputs(local, J).contiguous()          # [J, L] in job order, the same on every rank
+                for g, a, b in _owned(bounds, 0, J):
+                    for j0 in range(a, b, SCATTER_JOBS):
+                        j1 = min(b, j0 + SCATTER_JOBS)
+                        window_scatter(allx[bounds[g] + j0:bounds[g] + j1], groups[g].out, tables[p][g][j0:j1])
     finally:
         sampler.seeds = keep
 
 
 def run_passes(sampler, out: torch.Tensor, passes: Sequence[Sequence[Job]], step: int, max_batch: int, seeds, gather, predict, L: Optional[int] = None) -> None:
-    """The pass loop every whole-recording restoration shares.  Per non-empty job list of ``passes``: ``win = gather(table)`` (one launch for
-    the whole pass), then per chunk [c0, c1) of at most ``max_batch`` jobs ``x = predict(win, c0, c1)`` -> [c1 - c0, L] and one
-    aid_window_scatter launch of x into ``out``.  A later pass gathers what an earlier one scattered: same stream, in order.
-    ``sampler.seeds`` is set per chunk by the seed rule (None without seeds) and put back at the end.
+    """The pass loop of one set of equal-length recordings: run_pooled_passes over the one group (out, passes, gather).  Per non-empty job
+    list of ``passes``: ``win = gather(table)`` (one launch for the whole pass), then per chunk [c0, c1) of at most ``max_batch`` jobs
+    ``x = predict(win, c0, c1)`` -> [c1 - c0, L] and one aid_window_scatter launch of x into ``out``.  A later pass gathers what an earlier
+    one scattered: same stream, in order.  ``sampler.seeds`` is set per chunk by the seed rule (None without seeds) and put back at the end.
 
     Under an active process group (dist._active()) of ``world`` ranks a pass is shared out; every rank calls with the same recordings, plan
     and seeds, and with the same weights (call dist.broadcast_parameters first).  Before anything is launched one all_gather_object
-    compares pass_digest of every rank and all ranks raise if one differs (guard_ranks).  Then per pass of J jobs: rank k takes
+    compares the digest of every rank and all ranks raise if one differs (guard_ranks).  Then per pass of J jobs: rank k takes
     [lo, hi) = dist.shard_range(J, k, world), gathers ``win = gather(table[lo:hi])`` (nothing when its share is empty) and calls
     ``predict(win, c0 - lo, c1 - lo)`` per chunk of at most ``max_batch`` jobs of its share (max_batch is per rank), under the unchanged seed
     rule, so a job's result does not depend on the rank or chunk it ran in; ONE dist.gather_outputs per pass returns [J, L] in job order on
     every rank (a rank without a job contributes [0, L]: ``L`` is required here), and the whole pass is scattered, in launches of at most
     65535 jobs.  After a pass ``out`` is identical on every rank, and the next pass gathers from it as before.  No collective inside
     ``predict``, the sampler or the network."""
-    if _dist._active():
-        return _sharded_passes(sampler, out, passes, step, max_batch, seeds, gather, predict, L)
-    tables = [(jobs, job_table(jobs, out.device)) for jobs in passes if jobs]
-    keep = getattr(sampler, "seeds", None)
-    try:
-        for jobs, table in tables:
-            win = gather(table)
-            for c0 in range(0, len(jobs), max_batch):
-                c1 = min(len(jobs), c0 + max_batch)
-                sampler.seeds = _job_seeds(seeds, jobs[c0:c1], step)
-                window_scatter(predict(win, c0, c1).contiguous(), out, table[c0:c1])
-    finally:
-        sampler.seeds = keep
+    run_pooled_passes(sampler, [Group(out, passes, gather)], step, max_batch, seeds, predict, L)
+
+
+def restore_group(y: torch.Tensor, mask: torch.Tensor, L: int, end: int, max_batch: int = 8, seeds: Optional[Sequence[int]] = None) -> Group:
+    """The part of a restoration that checks, plans and builds: y [R, N] recordings on the GPU (rows contiguous, any row stride), mask
+    [1|R, N] -> Group(out = a copy of y, (jobs_A, jobs_B) of restore_plan, the aid_window_gather closure).  The plan is made on the host from
+    the mask; the mask goes to the GPU only when there is a job."""
+    mask = check_restore_args(y, mask, L, end, max_batch, seeds)
+    jobs_A, jobs_B, _ = restore_plan(mask, L, end, y.shape[0])
+    out = y.clone(memory_format=torch.contiguous_format)
+    dmask = mask.to(y.device, torch.float32).contiguous() if jobs_A or jobs_B else None
+    return Group(out, (jobs_A, jobs_B), lambda table: window_gather(y, out, dmask, table, L))    # (pass B reads what pass A scattered)
+
+
+def restore_predict(sampler):
+    """predict(win, c0, c1) of a restoration: ``sampler.predict_inpainting`` over rows c0:c1 of the gathered (y, m)"""
+    return lambda win, c0, c1: sampler.predict_inpainting(win[0][c0:c1], win[1][c0:c1])
 
 
 def restore_passes(sampler, y: torch.Tensor, mask: torch.Tensor, L: int, end: int, max_batch: int = 8, seeds: Optional[Sequence[int]] = None) -> torch.Tensor:
@@ -387,14 +471,7 @@ def restore_passes(sampler, y: torch.Tensor, mask: torch.Tensor, L: int, end: in
     (rows contiguous, any row stride), mask [1|R, N] -> restored [R, N].  Per pass: one gather launch, the sampler calls, one scatter launch per
     call.  Recordings, mask and result stay on the GPU; the plan is made on the host from the mask before pass A.  ``seeds`` [R]: the job of
     window w of recording r runs with ``sampler.seeds = [seeds[r] * 65536 + w, ...]`` (None: sampler.seeds = None, the global generator)."""
-    mask = check_restore_args(y, mask, L, end, max_batch, seeds)
-    R, N = y.shape
-    jobs_A, jobs_B, _ = restore_plan(mask, L, end, R)
-    out = y.clone(memory_format=torch.contiguous_format)
-    if no_jobs(jobs_A, jobs_B):
-        return out
-    dmask = mask.to(y.device, torch.float32).contiguous()
-    run_passes(sampler, out, (jobs_A, jobs_B), L - end, max_batch, seeds,
-               lambda table: window_gather(y, out, dmask, table, L),         # (pass B reads what pass A scattered)
-               lambda win, c0, c1: sampler.predict_inpainting(win[0][c0:c1], win[1][c0:c1]), L=L)
-    return out
+    group = restore_group(y, mask, L, end, max_batch, seeds)
+    if not no_jobs(*group.passes):
+        run_passes(sampler, group.out, group.passes, L - end, max_batch, seeds, group.gather, restore_predict(sampler), L=L)
+    return group.out

@@ -622,6 +622,83 @@ class Sampler:
         self._check_model()
         return spec_long.spec_passes(self, y, mask, st.n_fft, st.hop_length, L, end, st.win_length, st.window, max_batch, seeds)
 
+    POOLED_TASKS = ("inpainting", "declipping", "bwe", "bwe_lowrate", "pr")
+
+    def _pooled_task(self, task, device, filt=None, filt_type=None, factor=None):
+        """(check(group, max_batch, seeds), build(group, max_batch, seeds) -> restore.Group, predict(), step, L) of predict_long_pooled: per
+        task the refusals of the matching predict_*_long before its arguments are judged, its check_*_args, its group builder, and the one
+        predict closure (made by ``predict()``, after the checks) and step that the groups of a call share (the taps, the ratio, win_size / hop_size)."""
+        from . import bwe_long, declip_long, lowrate_long, phase_long, restore
+        if task == "inpainting":
+            L, end = self._long_grid("predict_inpainting_long")
+            return (lambda g, mb, sd: restore.check_restore_args(g[0], g[1], L, end, mb, sd),
+                    lambda g, mb, sd: restore.restore_group(g[0], g[1], L, end, mb, sd), lambda: restore.restore_predict(self), L - end, L)
+        if task == "declipping":
+            L, end = self._long_grid("predict_declipping_long", "declipped")
+            return (lambda g, mb, sd: declip_long.check_declip_args(g[0], g[1], L, end, mb, sd),
+                    lambda g, mb, sd: declip_long.declip_group(g[0], g[1], L, end, mb, sd), lambda: declip_long.declip_predict(self, L), L - end, L)
+        if task == "bwe":
+            L, end = self._long_grid("predict_bwe_long")
+            return (lambda g, mb, sd: bwe_long.check_bwe_args(g[0], filt, filt_type, L, end, mb, sd),
+                    lambda g, mb, sd: bwe_long.bwe_group(g[0], filt, filt_type, L, end, mb, sd),
+                    lambda: bwe_long.bwe_predict(self, filt, L, device), L - end, L)
+        if task == "bwe_lowrate":
+            L, end = self._long_grid("predict_bwe_lowrate_long", consistency="y + x - A(x) is undefined for an operator that changes the length")
+            ft = "resample" if filt_type is None else filt_type
+            lowrate_long.rate_of(factor, ft)                                       # (the ratio is judged first, as check_lowrate_args does)
+            return (lambda g, mb, sd: lowrate_long.check_lowrate_args(g[0], factor, ft, g[1], L, end, mb, sd),
+                    lambda g, mb, sd: lowrate_long.lowrate_group(g[0], factor, ft, L, end, g[1], mb, sd),
+                    lambda: lowrate_long.lowrate_predict(self, factor, ft, L, device), lowrate_long.lowrate_step(factor, ft, L, end), L)
+        L, end = self._long_grid("predict_pr_long", consistency="no data-consistency step exists for phase retrieval")
+        if not self.xi > 0:
+            raise _lib.AidError("predict_pr_long needs reconstruction guidance: tester.posterior_sampling.xi must be > 0 (the reference asserts xi > 0)")
+        win, hop = phase_retrieval_sizes(self.args)
+        return (lambda g, mb, sd: phase_long.check_pr_args(g[0], win, hop, g[1], L, end, mb, sd),
+                lambda g, mb, sd: phase_long.pr_group(g[0], win, hop, L, end, g[1], mb, sd),
+                lambda: phase_long.pr_predict(self, win, hop, L), L - restore.aligned_end(L, end, hop), L)
+
+    def predict_long_pooled(self, task, groups, max_batch=8, seeds=None, **task_args):
+        """Whole recordings of DIFFERENT lengths in shared passes: ``task`` is "inpainting", "declipping", "bwe", "bwe_lowrate" or "pr", and every
+        entry of ``groups`` is what the matching predict_*_long takes for one set of equal-length recordings -- (y, mask), (y, clip_value), y,
+        (y, length) and (y, length); a bare tensor is (y,) and a missing second entry None.  ``task_args`` are the arguments all groups share:
+        ``filt``, ``filt_type`` for "bwe"; ``factor``, ``filt_type`` = "resample" for "bwe_lowrate".  -> one [R_g, N_g] per group, in order.
+        The even windows of ALL groups run as one pooled pass in chunks of at most ``max_batch``, then the odd ones (restore.run_pooled_passes):
+        a chunk may hold windows of several recordings and lengths, so a folder of short files runs at the sampler's full-batch rate.
+        ``seeds``: one per recording, over all groups in order; the window w of a recording runs with seed * 65536 + w as in the plain
+        methods, so with seeds every group's result is what its predict_*_long call returns.  Each group is checked exactly as by the plain
+        method, all groups before anything is launched.
+        "spectrogram_inpainting" is refused: aid_stft_mask_observed reads one recording-shaped mask in place, so masks of different T_rec
+        cannot share a launch.
+        Under an active process group the pooled windows of each pass are shared out over the ranks (one guard over all groups, one exchange
+        per pass); ``seeds`` is then required."""
+        from . import restore
+        if task == "spectrogram_inpainting":
+            raise _lib.AidError("predict_long_pooled does not cover spectrogram inpainting: aid_stft_mask_observed reads one recording-shaped "
+                                "mask [F, T_rec] in place, so the windows of recordings with different T_rec cannot share a launch "
+                                "(call predict_spectrogram_inpainting_long per length)")
+        if task not in self.POOLED_TASKS:
+            raise NotImplementedError(f"predict_long_pooled: unknown task {task!r} (one of {', '.join(self.POOLED_TASKS)})")
+        allowed = {"bwe": ("filt", "filt_type"), "bwe_lowrate": ("factor", "filt_type")}.get(task, ())
+        if set(task_args) - set(allowed) or (task == "bwe" and set(task_args) != set(allowed)) or (task == "bwe_lowrate" and "factor" not in task_args):
+            raise TypeError(f"predict_long_pooled({task!r}) takes the task arguments ({', '.join(allowed)}), got ({', '.join(task_args)})")
+        groups = [tuple(g) + (None,) * (2 - len(g)) if isinstance(g, (tuple, list)) else (g, None) for g in groups]
+        device = next((g[0].device for g in groups if torch.is_tensor(g[0])), None)
+        check, build, predict, step, L = self._pooled_task(task, device, **task_args)
+        bounds = [0]
+        for g in groups:
+            bounds.append(bounds[-1] + (g[0].shape[0] if torch.is_tensor(g[0]) and g[0].dim() >= 1 else 0))
+        per = [None if seeds is None else [int(s) for s in seeds[bounds[i]:bounds[i + 1]]] for i in range(len(groups))]
+        for g, sd in zip(groups, per):
+            check(g, max_batch, sd)
+        if seeds is not None and len(seeds) != bounds[-1]:
+            raise _lib.AidError(f"{len(seeds)} seeds for {bounds[-1]} recordings")
+        if any(torch.is_tensor(g[0]) and g[0].device != device for g in groups):
+            raise _lib.AidError("predict_long_pooled: the recordings of all groups must be on one device")
+        self._check_model()
+        built = [build(g, max_batch, sd)._replace(files=range(bounds[i], bounds[i + 1])) for i, (g, sd) in enumerate(zip(groups, per))]
+        restore.run_pooled_passes(self, built, step, max_batch, seeds, predict(), L=L)
+        return [b.out for b in built]
+
     # ---- the remaining public methods of the reference class (its testers never call them; kept so that code written against
     # ---- testing.edm_sampler_inpainting.Sampler finds every name).  They run outside the sampling loop. ------------------------------
     def apply_mask(self, x, mask=None):
