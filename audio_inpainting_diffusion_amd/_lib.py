@@ -28,6 +28,7 @@ AID_CQT_MAX_OCT = 12
 AID_STATS_SPLIT = 32
 AID_CONV2D_SPLIT_FLAG_BYTES = 4096     # leading flag region of the split-K scratch
 AID_ATTN_MAX_T = 128          # aid_time_attention: one workgroup holds a whole [T, T] score tile
+AID_ATTN_LONG_MAX_T = 1024    # aid_time_attention_long: a wave holds one 32-key tile of each of up to eight 128-key chunks
 
 
 class AidError(RuntimeError):
@@ -440,7 +441,8 @@ ABIS = (
                   "aid_conv2d_wgrad": WgradParams, "aid_wino_gy": WinoGyParams, "aid_pack_conv_weight": PackConvWeightParams,
                   "aid_wgrad_reduce": WgradReduceParams, "aid_channel_dot": ChannelDotParams, "aid_relpos_bwd": RelposBwdParams,
                   "aid_scale_bwd": ScaleBwdParams, "aid_modulation_bwd": ModulationBwdParams, "aid_embed_bwd": EmbedBwdParams,
-                  "aid_adam": AdamParams, "aid_ema": EmaParams, "aid_sumsq": SumsqParams},
+                  "aid_adam": AdamParams, "aid_ema": EmaParams, "aid_sumsq": SumsqParams,
+                  "aid_time_attention_long": AttentionParams, "aid_time_attention_long_bwd": AttentionBwdParams},
         queries={"aid_last_error": (C.c_char_p, []), "aid_last_kernel": (C.c_char_p, []),
                  "aid_conv2d_pack_dims": (None, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
                  "aid_conv2d_wino_input_supported": (C.c_int, _ints(3)), "aid_conv2d_wino_input_ok": (C.c_int, _ints(6)),
@@ -451,7 +453,7 @@ ABIS = (
                  "aid_conv2d_wgrad_tiles": (C.c_int, _ints(5)), "aid_conv2d_wino2d_supported": (C.c_int, _ints(5)),
                  "aid_conv2d_wino2d_positions": (C.c_int64, _ints(4)), "aid_conv2d_wino2d_wanted": (C.c_int, _ints(6)),
                  "aid_conv2d_wino2d_tform": (C.c_int, _ints(6)), "aid_wino2d_set_split": (C.c_int, _ints(1))},
-        macros=("AID_CQT_MAX_OCT", "AID_STATS_SPLIT", "AID_CONV2D_SPLIT_FLAG_BYTES", "AID_SUMSQ_BLOCKS")),
+        macros=("AID_CQT_MAX_OCT", "AID_STATS_SPLIT", "AID_CONV2D_SPLIT_FLAG_BYTES", "AID_SUMSQ_BLOCKS", "AID_ATTN_LONG_MAX_T")),
     Abi("aid_degrade.h", "aid_degrade_abi_version", 1,
         structs={"aid_fir_params": FirParams, "aid_iir_params": IirParams, "aid_clip_params": ClipParams},
         launches={"aid_fir": FirParams, "aid_iir": IirParams, "aid_clip": ClipParams}),

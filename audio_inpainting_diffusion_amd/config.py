@@ -84,6 +84,8 @@ def make_args(name: str = "maestro22k", audio_len: int = 184184, T: int = 36, ga
     musicnet44k  : exp=musicnet44k_4s/8s (fs 44100) + 8-octave net
     maestro22k_noattention : same as maestro22k with conf/network/paper_1912_unet_cqt_oct_noattention_adaln.yaml
                    (attention_layers all 0, use_rel_pos: True -- unused without attention blocks)
+    audio_len=368368 (16.7 s at 22.05 kHz, attention T = 256 / 128 / 64) works for maestro22k and librispeech16k too: the weights do not depend on
+    the segment length, and attention levels up to T = 1024 run on aid_time_attention_long (network.attention_entries).
     """
     if name == "maestro22k_noattention":
         fs, net = 22050, copy.deepcopy(NETWORK_22K)

@@ -57,6 +57,18 @@ SQRT2 = math.sqrt(2.0)
 _CUBIC = (-0.01171875, -0.03515625, 0.11328125, 0.43359375, 0.43359375, 0.11328125, -0.03515625, -0.01171875)
 
 
+def attention_entries(T: int):
+    """(forward, backward) entry points of the time attention at sequence length ``T``: the one-tile-per-wave kernels up to AID_ATTN_MAX_T (what every
+    184184-sample configuration launches), the chunked ones of csrc/aid_attn_long.hip up to AID_ATTN_LONG_MAX_T; beyond that the saved [B, H, T, T]
+    probabilities are the wrong design and nothing is planned."""
+    T = int(T)
+    if T > _lib.AID_ATTN_LONG_MAX_T:
+        raise NotImplementedError(f"attention over T={T} > {_lib.AID_ATTN_LONG_MAX_T} time steps (aid_time_attention_long limit)")
+    if T > _lib.AID_ATTN_MAX_T:
+        return "aid_time_attention_long", "aid_time_attention_long_bwd"
+    return "aid_time_attention", "aid_time_attention_bwd"
+
+
 # =========================================================================================================
 # Parameter containers (names/shapes identical to the reference modules; no forward of their own)
 # =========================================================================================================
@@ -746,8 +758,9 @@ class _Builder:
         B = v.shape[0]
         probs = self.buf(B, heads, T, T)
         scale = float(F) ** -0.5
+        fwd_name, bwd_name = attention_entries(T)
         p = _lib.AttentionParams(qk.data_ptr(), v.data_ptr(), out.data_ptr(), probs.data_ptr(), B, heads, F, T, scale, _lib.ptr(bias))
-        self._add("aid_time_attention", p, qk, v, out, probs, bias, flops=4 * B * heads * T * T * F, writes=(out, probs))
+        self._add(fwd_name, p, qk, v, out, probs, bias, flops=4 * B * heads * T * T * F, writes=(out, probs))
         self._wrote(out)
 
         def bw():
@@ -757,7 +770,7 @@ class _Builder:
             dsws = self._scratch(("ds", B, heads, T, T))
             bp = _lib.AttentionBwdParams(qk.data_ptr(), v.data_ptr(), probs.data_ptr(), go.data_ptr(), gq.data_ptr(), gv.data_ptr(),
                                          B, heads, F, T, scale, 1 if self._gacc(v) else 0, dsws.data_ptr())
-            self._add("aid_time_attention_bwd", bp, qk, v, probs, go, gq, gv, dsws, flops=10 * B * heads * T * T * F, writes=(gq, gv, dsws))
+            self._add(bwd_name, bp, qk, v, probs, go, gq, gv, dsws, flops=10 * B * heads * T * T * F, writes=(gq, gv, dsws))
             self._wrote(gq)
             self._wrote(gv)
             if self.train and relpos is not None:           # d(bias table) = dS summed over samples, scattered back onto the embedding rows
@@ -1043,8 +1056,11 @@ class Unet_CQT_oct_with_attention(nn.Module):
             assert Tl[i] * 2 == Tl[i - 1], "octave lengths must halve per level (unet...py:768-774,786)"
         Fl = [(i + 1) * bpo for i in range(n)]
         for i in range(n):
-            if self.attention_layers[i] and Tl[i] > _lib.AID_ATTN_MAX_T:
-                raise NotImplementedError(f"attention at level {i} has T={Tl[i]} > {_lib.AID_ATTN_MAX_T} (aid_time_attention limit)")
+            if self.attention_layers[i]:
+                try:
+                    attention_entries(Tl[i])
+                except NotImplementedError as e:
+                    raise NotImplementedError(f"attention at level {i}: {e}") from None
         for nm in ("downsamplerT", "upsamplerT"):
             k = getattr(self, nm).kernel.detach().float().cpu()
             if not torch.allclose(k, torch.tensor(_CUBIC), atol=1e-7):
@@ -1225,7 +1241,8 @@ class Unet_CQT_oct_with_attention(nn.Module):
         return self._csplit_streams
 
     def _type_lane(self, op) -> int:
-        if op.name in ("aid_conv2d_wino2d_gemm", "aid_time_attention", "aid_time_attention_bwd"):
+        if op.name in ("aid_conv2d_wino2d_gemm", "aid_time_attention", "aid_time_attention_bwd", "aid_time_attention_long",
+                       "aid_time_attention_long_bwd"):
             return 0
         if op.name == "aid_conv2d" and op.flops > 0 and op.nbytes > 0 and op.flops / op.nbytes >= self.cu_partition_ridge:
             return 0

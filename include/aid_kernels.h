@@ -253,6 +253,16 @@ typedef struct {
 int aid_time_attention(const aid_attention_params* p, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * aid_time_attention_long / aid_time_attention_long_bwd -- the same attention core and its VJP for longer segments.
+ *   Same structs, layouts, bias, scale, probs == NULL and accumulate_gv rules as aid_time_attention / aid_time_attention_bwd
+ *   (declared further down); the only difference is the bound 1 <= T <= AID_ATTN_LONG_MAX_T.  T <= 128 is accepted too.
+ *   A wave keeps one 32-key tile of every 128-key chunk in registers, so the softmax stays the exact two-pass one; P V
+ *   walks the chunks through LDS.  All products on v_mfma_f32_32x32x2_f32; deterministic; static LDS only.
+ * ------------------------------------------------------------------------------------------------- */
+#define AID_ATTN_LONG_MAX_T 1024
+int aid_time_attention_long(const aid_attention_params* p, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * aid_embed -- RFF noise-level embedding + 3-layer ReLU MLP.
  *   replaces: RFF_MLP_Block.forward (unet...py:184-211).   sigma[B] -> emb[B, emb_dim]
  * aid_modulation -- every affine/gate Linear of the network as ONE batched product.
@@ -436,6 +446,7 @@ typedef struct {
     float* ws;                    /* scratch [B,H,T,T] (dS) */
 } aid_attention_bwd_params;
 int aid_time_attention_bwd(const aid_attention_bwd_params* p, void* stream);
+int aid_time_attention_long_bwd(const aid_attention_bwd_params* p, void* stream);   /* T <= AID_ATTN_LONG_MAX_T, see aid_time_attention_long */
 
 typedef struct {
     const float* xhat; const float* y; const float* mask; int64_t mask_sB;   /* mask NULL: all ones (operator degradations) */
