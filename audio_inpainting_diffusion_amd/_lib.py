@@ -472,7 +472,8 @@ ABIS = (
         structs={"aid_resample_poly_adj_params": ResamplePolyAdjParams}, launches={"aid_resample_poly_adj": ResamplePolyAdjParams}),
     Abi("aid_bwe_long.h", "aid_bwe_long_abi_version", 1,
         structs={"aid_fir_observed_params": FirObservedParams, "aid_bwe_gather_params": BweGatherParams},
-        launches={"aid_fir_observed": FirObservedParams, "aid_bwe_gather": BweGatherParams}),
+        launches={"aid_fir_observed": FirObservedParams, "aid_bwe_gather": BweGatherParams,
+                  "aid_iir_observed": FirObservedParams, "aid_iir_gather": BweGatherParams}),
     Abi("aid_lowrate_long.h", "aid_lowrate_long_abi_version", 1,
         structs={"aid_rate_observed_params": RateObservedParams, "aid_lowrate_gather_params": LowrateGatherParams},
         launches={"aid_rate_observed": RateObservedParams, "aid_lowrate_gather": LowrateGatherParams}),

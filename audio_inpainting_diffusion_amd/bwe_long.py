@@ -33,9 +33,11 @@ from . import restore
 
 FIR_TYPES = ("firwin", "firwin_hpf")
 # why the other degradations of predict_bwe do not window
+_IIR = ("an IIR filter carries state from the start of the recording, so a window cut out of the filtered recording is not the filtered window "
+        "(predict_bwe_iir_long seeds the recursion of every window from the recording instead).")
 NOT_WINDOWED = {
-    "cheby1": "an IIR filter carries state from the start of the recording, so a window cut out of the filtered recording is not the filtered window.",
-    "biquad": "an IIR filter carries state from the start of the recording, so a window cut out of the filtered recording is not the filtered window.",
+    "cheby1": _IIR,
+    "biquad": _IIR,
     "decimate": "a decimator's phase depends on the window start, so the windows of the grid do not see the recording's samples.",
     "resample": "a resampler is a decimator whose phase depends on the window start, so the windows of the grid do not see the recording's samples.",
 }

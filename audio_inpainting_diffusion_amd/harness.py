@@ -238,6 +238,17 @@ def bwe_long(sampler, files: Sequence[torch.Tensor], filt, filt_type: str = "fir
         pooled=None if not pool else lambda gs, sd: sampler.predict_long_pooled("bwe", [y for y, _, _ in gs], max_batch=max_batch, seeds=sd, filt=filt, filt_type=filt_type))
 
 
+def bwe_iir_long(sampler, files: Sequence[torch.Tensor], filt, filt_type: str = "cheby1", seeds: Optional[Sequence[int]] = None, max_batch: int = 8,
+                 device="cuda", pool: bool = False) -> List[torch.Tensor]:
+    """Bandwidth-extend every 1-D waveform of ``files`` (any lengths), each low-passed as a whole with the IIR filter ``filt`` ("cheby1": (b, a);
+    "biquad": (b0, b1, b2, a0, a1, a2); one filter for all files), and return the full-length results on ``device``, in the order of ``files``.
+    Files of equal length go through ONE Sampler.predict_bwe_iir_long call, so their windows share the two batched passes; every other length
+    is a call of its own.  Seeds, process groups and ``pool`` as bwe_long (the pooled task is "bwe_iir")."""
+    return _long_groups("bwe_iir_long", files, seeds, device, lambda i: files[i].numel(), lambda y, idx, _, sd: sampler.predict_bwe_iir_long(
+        y, filt, filt_type, max_batch=max_batch, seeds=sd),
+        pooled=None if not pool else lambda gs, sd: sampler.predict_long_pooled("bwe_iir", [y for y, _, _ in gs], max_batch=max_batch, seeds=sd, filt=filt, filt_type=filt_type))
+
+
 def bwe_lowrate_long(sampler, files: Sequence[torch.Tensor], factor, filt_type: str = "resample", lengths: Optional[Sequence[Optional[int]]] = None,
                      seeds: Optional[Sequence[int]] = None, max_batch: int = 8, device="cuda", pool: bool = False) -> List[torch.Tensor]:
     """Bandwidth-extend every 1-D low-sample-rate waveform of ``files`` (any lengths; one ``factor`` and ``filt_type`` for all files) and return the

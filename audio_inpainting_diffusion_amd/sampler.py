@@ -542,7 +542,8 @@ class Sampler:
         """Bandwidth-extend whole recordings y[R, N] -- N any length, low-passed as a whole with the FIR taps ``filt`` ([K], [1, K] or [1, 1, K],
         conv1d padding="same", as predict_bwe takes them) -> [R, N] on y.device (bwe_long.py).  filt_type "firwin" / "firwin_hpf" only: an IIR
         filter ("cheby1", "biquad") carries state from the start of the recording and a decimator's phase ("decimate", "resample") depends on
-        the window start, so neither windows; they are refused.  The window grid, the two batched passes and the seeds are those of
+        the window start, so neither windows here; they are refused (an IIR-filtered recording goes through predict_bwe_iir_long, which seeds
+        the recursion of every window from the recording).  The window grid, the two batched passes and the seeds are those of
         predict_inpainting_long, with every window a job and the ownership trimmed by K - 1 samples (more than one window needs
         end = int(overlap * L) >= 2 (K - 1)).  Each chunk of at most ``max_batch`` windows is one predict_resample through bwe_long.FIRObserved,
         which uses a filtered sample as an observation only where the window holds its whole filter support and takes the overlaps its
@@ -555,6 +556,25 @@ class Sampler:
         bwe_long.check_bwe_args(y, filt, filt_type, L, end, max_batch, seeds)
         self._check_model()
         return bwe_long.bwe_passes(self, y, filt, filt_type, L, end, max_batch, seeds)
+
+    def predict_bwe_iir_long(self, y, filt, filt_type, max_batch=8, seeds=None):
+        """Bandwidth-extend whole recordings y[R, N] -- N any length, low-passed as a whole with an IIR filter from a zero state -> [R, N] on
+        y.device (bwe_iir_long.py).  filt_type "cheby1": filt = (b, a), as predict_bwe takes them (lfilter, clamp=False); "biquad":
+        (b0, b1, b2, a0, a1, a2).  The coefficients are those of degrade.iir_coefficients (order <= 16) under IIRFilter's conditioning refusal.
+        The window grid, the two batched passes, the seeds, the refusal of rid and the behaviour under a process group are those of
+        predict_bwe_long with K - 1 = order (more than one window needs end = int(overlap * L) >= 2 order).  A window that does not start the
+        recording takes its first ``order`` filtered samples as the initial state of the recursion instead of as observations, so from there
+        on the window operator (bwe_iir_long.IIRObserved) does the recording's own arithmetic on the recording's own numbers; the float32
+        rounding of those seeds moves a filtered sample by at most IIRObserved.seed_error_bound = order * amplification * 2^-24 of max|y|.
+        tester.data_consistency off / "end" / "always" mean what they mean for predict_bwe "cheby1".
+        "biquad" DEPARTS from predict_bwe "biquad": torchaudio clamps the filtered signal to [-1, 1]; here a recording with a sample |y| >= 1 is
+        refused (the clamp acted, the recording no longer satisfies the recursion) and the window operator is the linear filter, whereas
+        predict_bwe "biquad" also drops the gradient where the model's own filtered estimate leaves [-1, 1]."""
+        from . import bwe_iir_long
+        L, end = self._long_grid("predict_bwe_iir_long")
+        bwe_iir_long.check_bwe_iir_args(y, filt, filt_type, L, end, max_batch, seeds)
+        self._check_model()
+        return bwe_iir_long.bwe_iir_passes(self, y, filt, filt_type, L, end, max_batch, seeds)
 
     def predict_bwe_lowrate_long(self, y, factor, filt_type="resample", length=None, max_batch=8, seeds=None):
         """Bandwidth-extend whole recordings that exist only at a low sample rate: y[R, M] on the GPU -> [R, N] at the high rate, N any length
@@ -622,13 +642,13 @@ class Sampler:
         self._check_model()
         return spec_long.spec_passes(self, y, mask, st.n_fft, st.hop_length, L, end, st.win_length, st.window, max_batch, seeds)
 
-    POOLED_TASKS = ("inpainting", "declipping", "bwe", "bwe_lowrate", "pr")
+    POOLED_TASKS = ("inpainting", "declipping", "bwe", "bwe_iir", "bwe_lowrate", "pr")
 
     def _pooled_task(self, task, device, filt=None, filt_type=None, factor=None):
         """(check(group, max_batch, seeds), build(group, max_batch, seeds) -> restore.Group, predict(), step, L) of predict_long_pooled: per
         task the refusals of the matching predict_*_long before its arguments are judged, its check_*_args, its group builder, and the one
         predict closure (made by ``predict()``, after the checks) and step that the groups of a call share (the taps, the ratio, win_size / hop_size)."""
-        from . import bwe_long, declip_long, lowrate_long, phase_long, restore
+        from . import bwe_iir_long, bwe_long, declip_long, lowrate_long, phase_long, restore
         if task == "inpainting":
             L, end = self._long_grid("predict_inpainting_long")
             return (lambda g, mb, sd: restore.check_restore_args(g[0], g[1], L, end, mb, sd),
@@ -642,6 +662,16 @@ class Sampler:
             return (lambda g, mb, sd: bwe_long.check_bwe_args(g[0], filt, filt_type, L, end, mb, sd),
                     lambda g, mb, sd: bwe_long.bwe_group(g[0], filt, filt_type, L, end, mb, sd),
                     lambda: bwe_long.bwe_predict(self, filt, L, device), L - end, L)
+        if task == "bwe_iir":
+            L, end = self._long_grid("predict_bwe_iir_long")
+            shared = []                                                            # (the one predict closure, made after the checks; it holds the one table)
+
+            def predict():
+                if not shared:
+                    shared.append(bwe_iir_long.bwe_iir_predict(self, filt, filt_type, L, device))
+                return shared[0]
+            return (lambda g, mb, sd: bwe_iir_long.check_bwe_iir_args(g[0], filt, filt_type, L, end, mb, sd),
+                    lambda g, mb, sd: bwe_iir_long.bwe_iir_group(g[0], filt, filt_type, L, end, mb, sd, table=predict().table), predict, L - end, L)
         if task == "bwe_lowrate":
             L, end = self._long_grid("predict_bwe_lowrate_long", consistency="y + x - A(x) is undefined for an operator that changes the length")
             ft = "resample" if filt_type is None else filt_type
@@ -658,10 +688,10 @@ class Sampler:
                 lambda: phase_long.pr_predict(self, win, hop, L), L - restore.aligned_end(L, end, hop), L)
 
     def predict_long_pooled(self, task, groups, max_batch=8, seeds=None, **task_args):
-        """Whole recordings of DIFFERENT lengths in shared passes: ``task`` is "inpainting", "declipping", "bwe", "bwe_lowrate" or "pr", and every
-        entry of ``groups`` is what the matching predict_*_long takes for one set of equal-length recordings -- (y, mask), (y, clip_value), y,
+        """Whole recordings of DIFFERENT lengths in shared passes: ``task`` is "inpainting", "declipping", "bwe", "bwe_iir", "bwe_lowrate" or "pr", and every
+        entry of ``groups`` is what the matching predict_*_long takes for one set of equal-length recordings -- (y, mask), (y, clip_value), y, y,
         (y, length) and (y, length); a bare tensor is (y,) and a missing second entry None.  ``task_args`` are the arguments all groups share:
-        ``filt``, ``filt_type`` for "bwe"; ``factor``, ``filt_type`` = "resample" for "bwe_lowrate".  -> one [R_g, N_g] per group, in order.
+        ``filt``, ``filt_type`` for "bwe" and "bwe_iir"; ``factor``, ``filt_type`` = "resample" for "bwe_lowrate".  -> one [R_g, N_g] per group, in order.
         The even windows of ALL groups run as one pooled pass in chunks of at most ``max_batch``, then the odd ones (restore.run_pooled_passes):
         a chunk may hold windows of several recordings and lengths, so a folder of short files runs at the sampler's full-batch rate.
         ``seeds``: one per recording, over all groups in order; the window w of a recording runs with seed * 65536 + w as in the plain
@@ -678,8 +708,8 @@ class Sampler:
                                 "(call predict_spectrogram_inpainting_long per length)")
         if task not in self.POOLED_TASKS:
             raise NotImplementedError(f"predict_long_pooled: unknown task {task!r} (one of {', '.join(self.POOLED_TASKS)})")
-        allowed = {"bwe": ("filt", "filt_type"), "bwe_lowrate": ("factor", "filt_type")}.get(task, ())
-        if set(task_args) - set(allowed) or (task == "bwe" and set(task_args) != set(allowed)) or (task == "bwe_lowrate" and "factor" not in task_args):
+        allowed = {"bwe": ("filt", "filt_type"), "bwe_iir": ("filt", "filt_type"), "bwe_lowrate": ("factor", "filt_type")}.get(task, ())
+        if set(task_args) - set(allowed) or (task in ("bwe", "bwe_iir") and set(task_args) != set(allowed)) or (task == "bwe_lowrate" and "factor" not in task_args):
             raise TypeError(f"predict_long_pooled({task!r}) takes the task arguments ({', '.join(allowed)}), got ({', '.join(task_args)})")
         groups = [tuple(g) + (None,) * (2 - len(g)) if isinstance(g, (tuple, list)) else (g, None) for g in groups]
         device = next((g[0].device for g in groups if torch.is_tensor(g[0])), None)

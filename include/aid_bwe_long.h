@@ -75,6 +75,33 @@ typedef struct {
 } aid_bwe_gather_params;
 int aid_bwe_gather(const aid_bwe_gather_params* p, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * aid_iir_observed -- the same window seen through an IIR filter (bwe_iir_long.py), on the parameter block of aid_fir_observed:
+ *   K = order + 1 in [2, 17]; h is a float table [2 K], b[0..K) then a[0..K), normalised (a[0] = 1; exact in fp32); L <= 2^20.
+ *   A fifth state, -3 (SEED): the leading run of -3 states of a row, S samples long, holds samples of the filtered recording
+ *   that start the recursion instead of being observed.  A -3 after that run counts as -1.  Any other state <= -2 is absent.
+ *   With k = state[b, i], xin = absent ? 0 : x, u[i] = sum_{j<K, i-j>=0} b[j] xin[i-j], and the recursion in fp64
+ *       yh[i] = 0 (i < S);   yh[i] = u[i] - sum_{1<=j<K, i-j>=S} a[j] yh[i-j]  (i >= S):
+ *   mode 0 (apply):       out = k > 0 ? x : (k == 0 ? yh : 0)
+ *   mode 1 (adjoint):     g0 = k == 0 ? x : 0;  w[i] = 0 (i < S),  w[i] = g0[i] - sum_{1<=j<K, i+j<L} a[j] w[i+j]  (i >= S, backwards);
+ *                         c[i] = sum_{j<K, i+j<L} b[j] w[i+j];   out = absent ? 0 : (k > 0 ? c + x : c)
+ *   mode 2 (projection):  out = k > 0 ? y : (k == 0 ? (y - yh) + x : x)
+ *   mode 3 (preparation): x is a raw row of aid_iir_gather;  r[i] = x[i] (i < S),  r[i] = -sum_{1<=j<K, i-j>=0} a[j] r[i-j]  (i >= S);
+ *                         out = k > 0 ? x : (k == 0 ? x - r (fp64, rounded once) : 0)
+ *   Strides, the shared state row (state_ld = 0) and the no-overlap rule are those of aid_fir_observed.  One workgroup per
+ *   row; registers and static LDS only: no scratch, nothing kept between calls.  Deterministic.
+ * aid_iir_gather -- on the parameter block of aid_bwe_gather, K = order + 1 in [2, 17]; for job j and i < L, q = s_j + i; the
+ *   first match decides:
+ *   q >= N                                                   state[j, i] = -2,  y[j, i] = 0
+ *   s_j > 0 and i < K - 1                                    state[j, i] = -3,  y[j, i] = rec[r_j, q]
+ *   i < head_j  or  i >= L - tail_j                          state[j, i] =  1,  y[j, i] = out[r_j, q]
+ *   otherwise                                                state[j, i] =  0,  y[j, i] = rec[r_j, q]
+ *   Everything else as aid_bwe_gather (invalid jobs, clamping, copies only).  The rows are raw: one mode-3 launch of
+ *   aid_iir_observed turns them into the observations.
+ * ------------------------------------------------------------------------------------------------- */
+int aid_iir_observed(const aid_fir_observed_params* p, void* stream);
+int aid_iir_gather(const aid_bwe_gather_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
