@@ -464,7 +464,8 @@ ABIS = (
         structs={"aid_ar_carry_params": ArCarryParams}, launches={"aid_ar_carry": ArCarryParams}),
     Abi("aid_restore.h", "aid_restore_abi_version", 1,
         structs={"aid_window_gather_params": WindowGatherParams, "aid_window_scatter_params": WindowScatterParams},
-        launches={"aid_window_gather": WindowGatherParams, "aid_window_scatter": WindowScatterParams}, macros=("AID_RESTORE_JOB_FIELDS",)),
+        launches={"aid_window_gather": WindowGatherParams, "aid_window_scatter": WindowScatterParams, "aid_gap_states": WindowGatherParams},
+        macros=("AID_RESTORE_JOB_FIELDS",)),
     Abi("aid_declip.h", "aid_declip_abi_version", 1,
         structs={"aid_clip_known_params": ClipKnownParams, "aid_declip_gather_params": DeclipGatherParams},
         launches={"aid_clip_known": ClipKnownParams, "aid_declip_gather": DeclipGatherParams}),
@@ -473,7 +474,7 @@ ABIS = (
     Abi("aid_bwe_long.h", "aid_bwe_long_abi_version", 1,
         structs={"aid_fir_observed_params": FirObservedParams, "aid_bwe_gather_params": BweGatherParams},
         launches={"aid_fir_observed": FirObservedParams, "aid_bwe_gather": BweGatherParams,
-                  "aid_iir_observed": FirObservedParams, "aid_iir_gather": BweGatherParams}),
+                  "aid_iir_observed": FirObservedParams, "aid_iir_gather": BweGatherParams, "aid_fir_clip_observed": FirObservedParams}),
     Abi("aid_lowrate_long.h", "aid_lowrate_long_abi_version", 1,
         structs={"aid_rate_observed_params": RateObservedParams, "aid_lowrate_gather_params": LowrateGatherParams},
         launches={"aid_rate_observed": RateObservedParams, "aid_lowrate_gather": LowrateGatherParams}),

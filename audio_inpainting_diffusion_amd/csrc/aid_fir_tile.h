@@ -1,4 +1,5 @@
-// The stride-1 FIR tile loop shared by aid_fir (aid_degrade.hip) and aid_fir_observed (aid_bwe_long.hip).
+// The stride-1 FIR tile loop shared by aid_fir (aid_degrade.hip), aid_fir_observed (aid_bwe_long.hip) and aid_fir_clip_observed
+// (aid_bwe_declip_long.hip).
 //
 //   One workgroup of FIR_THREADS lanes computes FIR_TO = 2048 consecutive outputs of one row.  Taps and the input tile plus its halo are
 //   staged in LDS in chunks of FIR_KC = 1024 taps; each lane owns FIR_R = 8 consecutive outputs and walks the taps in blocks of 8 with a

@@ -1,5 +1,5 @@
-// Row helpers shared by the kernels of whole-recording restoration (aid_restore.hip, aid_declip.hip, aid_bwe_long.hip, aid_lowrate_long.hip,
-// aid_phase_long.hip, aid_spec_long.hip): the job table of include/aid_restore.h and the window of a job, the state codes of a window's
+// Row helpers shared by the kernels of whole-recording restoration (aid_restore.hip, aid_declip.hip, aid_bwe_long.hip, aid_bwe_declip_long.hip,
+// aid_lowrate_long.hip, aid_phase_long.hip, aid_spec_long.hip): the job table of include/aid_restore.h and the window of a job, the state codes of a window's
 // entries, float4 access over the 16-byte-aligned body of a row with scalars at its ragged ends, and the tile count.
 //
 //   STATE CODES of an entry of a window (float32, one per sample and, where a mode has them, one per low-rate sample or frame):

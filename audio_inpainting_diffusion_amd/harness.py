@@ -249,6 +249,42 @@ def bwe_iir_long(sampler, files: Sequence[torch.Tensor], filt, filt_type: str = 
         pooled=None if not pool else lambda gs, sd: sampler.predict_long_pooled("bwe_iir", [y for y, _, _ in gs], max_batch=max_batch, seeds=sd, filt=filt, filt_type=filt_type))
 
 
+def bwe_declip_long(sampler, files: Sequence[torch.Tensor], filt, filt_type: str = "firwin", clip_values=None, masks: Optional[Sequence[Optional[torch.Tensor]]] = None,
+                    seeds: Optional[Sequence[int]] = None, max_batch: int = 8, device="cuda", pool: bool = False) -> List[torch.Tensor]:
+    """Bandwidth-extend every 1-D waveform of ``files`` (any lengths) that was low-passed as a whole with the FIR taps ``filt`` (one filter for
+    all files), THEN clipped at +-clip_values (None: not clipped; one float for all files, or one per file) and THEN dropped where its mask
+    (``masks``: None, or per file None or a mask of the file's length; 1 = kept, 0 = dropped) is 0 -- y = mask * clamp(taps * x, -c, c), in this
+    order -- and return the full-length results on ``device``, in the order of ``files``.  Files of equal length go through ONE
+    Sampler.predict_bwe_declip_long call, so their windows share the two batched passes (a file without a mask gets all ones beside one that
+    has one); every other length is a call of its own.  Seeds, process groups and ``pool`` as bwe_long (the pooled task is "bwe_declip")."""
+    if clip_values is None:
+        levels = None
+    else:
+        levels = [float(v) for v in (clip_values.reshape(-1).tolist() if torch.is_tensor(clip_values) else
+                                     (list(clip_values) if hasattr(clip_values, "__len__") else [clip_values]))]
+        if len(levels) not in (1, len(files)):
+            raise ValueError(f"bwe_declip_long: {len(levels)} clip values for {len(files)} files")
+        if len(levels) == 1:
+            levels = levels * len(files)
+    if masks is not None and len(masks) != len(files):
+        raise ValueError(f"bwe_declip_long: {len(masks)} masks for {len(files)} files")
+
+    def key(i):
+        if masks is not None and masks[i] is not None and masks[i].numel() != files[i].numel():
+            raise ValueError(f"bwe_declip_long: file {i} has {files[i].numel()} samples, its mask {masks[i].numel()}")
+        return files[i].numel()
+
+    def mask_of(idx):
+        if masks is None or all(masks[i] is None for i in idx):
+            return None
+        return torch.stack([torch.ones(files[i].numel()) if masks[i] is None else masks[i].reshape(-1).float().cpu() for i in idx])
+    level_of = lambda idx: None if levels is None else [levels[i] for i in idx]                                          # noqa: E731
+    return _long_groups("bwe_declip_long", files, seeds, device, key, lambda y, idx, _, sd: sampler.predict_bwe_declip_long(
+        y, filt, filt_type, clip_value=level_of(idx), mask=mask_of(idx), max_batch=max_batch, seeds=sd),
+        pooled=None if not pool else lambda gs, sd: sampler.predict_long_pooled("bwe_declip", [(y, level_of(idx), mask_of(idx)) for y, idx, _ in gs],
+                                                                                max_batch=max_batch, seeds=sd, filt=filt, filt_type=filt_type))
+
+
 def bwe_lowrate_long(sampler, files: Sequence[torch.Tensor], factor, filt_type: str = "resample", lengths: Optional[Sequence[Optional[int]]] = None,
                      seeds: Optional[Sequence[int]] = None, max_batch: int = 8, device="cuda", pool: bool = False) -> List[torch.Tensor]:
     """Bandwidth-extend every 1-D low-sample-rate waveform of ``files`` (any lengths; one ``factor`` and ``filt_type`` for all files) and return the

@@ -17,10 +17,10 @@ autoregressive mode, testing/edm_sampler.py:416).
 ``restore_plan`` is host code (the only part that looks at the mask on the host); ``window_gather`` / ``window_scatter`` launch the
 two HIP kernels of csrc/aid_restore.hip; ``restore_passes`` is the pass code, driven with anything that has ``predict_inpainting``.
 
-This module is also the one home of what the other whole-recording modes share (declip_long.py, bwe_long.py, lowrate_long.py, phase_long.py,
-spec_long.py; DESIGN.md, "The window scheme of whole recordings"): ``aligned_end`` / ``trimmed_windows`` / ``every_window_plan`` (the grid
+This module is also the one home of what the other whole-recording modes share (declip_long.py, bwe_long.py, bwe_declip_long.py, lowrate_long.py,
+phase_long.py, spec_long.py; DESIGN.md, "The window scheme of whole recordings"): ``aligned_end`` / ``trimmed_windows`` / ``every_window_plan`` (the grid
 aligned to a period, the ownership trimmed by an operator's reach, every window a job), ``check_rows`` / ``check_batch`` (the refusals
-every mode raises), ``WindowOperator`` (the base of the five window operators) and ``run_passes`` (the pass loop).  ``run_pooled_passes`` is
+every mode raises), ``WindowOperator`` (the base of the window operators) and ``run_passes`` (the pass loop).  ``run_pooled_passes`` is
 that loop over several ``Group`` records, one per recording length: the jobs of all lengths share the chunks of one pooled pass A and one
 pooled pass B; ``run_passes`` is its one-group case.
 
@@ -222,7 +222,7 @@ def check_batch(y: torch.Tensor, max_batch, seeds, task: str) -> None:
 
 
 class WindowOperator(degrade._Operator):
-    """What the observation operators of a window share (ClipObserved, FIRObserved, RateObserved, STFTMagObserved, SpectralMaskObserved): the
+    """What the observation operators of a window share (ClipObserved, FIRObserved, FIRClipObserved, RateObserved, STFTMagObserved, SpectralMaskObserved): the
     operator protocol of degrade.py over a per-sample ``state`` [1|B, row] (float32 on the GPU; aid_rows.h describes the codes).  They hold
     per-item rows, so ``shared_mask`` is False; ``rows(lo, hi)`` is the operator of items lo:hi, kept per range so that the apply / adjoint
     pair of a sub-batch meets the same object, which is what lets network.denoise_guided run sub-batches on concurrent streams.  A subclass

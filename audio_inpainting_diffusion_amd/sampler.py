@@ -576,6 +576,28 @@ class Sampler:
         self._check_model()
         return bwe_iir_long.bwe_iir_passes(self, y, filt, filt_type, L, end, max_batch, seeds)
 
+    def predict_bwe_declip_long(self, y, filt, filt_type, clip_value=None, mask=None, max_batch=8, seeds=None):
+        """Bandwidth-extend whole recordings y[R, N] that are also clipped and have dropouts -- N any length -> [R, N] on y.device
+        (bwe_declip_long.py).  The degradation model, applied to the recording as a whole, is y = mask * clamp(taps * x, -c_r, +c_r), in this
+        order and no other: low-passed with the FIR taps ``filt`` ("same" padding, as predict_bwe_long; filt_type "firwin" / "firwin_hpf" only,
+        the others are refused for predict_bwe_long's reasons), THEN clipped at +-clip_value (a float, or R floats: one level per recording, as
+        predict_declipping_long; None: not clipped, carried as a level of +inf), THEN dropped where mask ([N], [1, N] or [R, N]; 1 = kept,
+        0 = dropped; None: all ones) is 0.  The window grid, the ownership, the two batched passes and the seeds are those of predict_bwe_long
+        (every window a job; more than one window needs end = int(overlap * L) >= 2 (K - 1)).  Each chunk of at most ``max_batch`` windows is one
+        predict_resample through bwe_declip_long.FIRClipObserved, which sees a filtered sample through the clipper where the window holds its
+        whole filter support, takes a dropped sample as unobserved (it still feeds its neighbours' filter sums) and the overlaps its neighbours
+        restored as known.  With clip_value = None and mask = None the result is predict_bwe_long's, bit for bit.
+        Guidance only: rid and tester.data_consistency in use are refused (no projection exists for the clipped filter).  A recording with a
+        window that holds neither a filtered nor a known sample -- a dropout that swallows a whole window -- is refused before anything is
+        launched, naming the recording and the window.
+        Under an active process group the windows of each pass are shared out over the ranks as predict_inpainting_long states: the same
+        arguments and weights (dist.broadcast_parameters) on every rank, ``seeds`` required, ``max_batch`` per rank, the full result on every rank."""
+        from . import bwe_declip_long
+        L, end = self._long_grid("predict_bwe_declip_long", consistency=bwe_declip_long.NO_PROJECTION)
+        bwe_declip_long.check_bwe_declip_args(y, filt, filt_type, clip_value, mask, L, end, max_batch, seeds)
+        self._check_model()
+        return bwe_declip_long.bwe_declip_passes(self, y, filt, filt_type, clip_value, mask, L, end, max_batch, seeds)
+
     def predict_bwe_lowrate_long(self, y, factor, filt_type="resample", length=None, max_batch=8, seeds=None):
         """Bandwidth-extend whole recordings that exist only at a low sample rate: y[R, M] on the GPU -> [R, N] at the high rate, N any length
         (lowrate_long.py).  filt_type "resample": torchaudio's default resampler at degrade.bwe_resample_ratio(factor), as predict_bwe's
@@ -642,13 +664,13 @@ class Sampler:
         self._check_model()
         return spec_long.spec_passes(self, y, mask, st.n_fft, st.hop_length, L, end, st.win_length, st.window, max_batch, seeds)
 
-    POOLED_TASKS = ("inpainting", "declipping", "bwe", "bwe_iir", "bwe_lowrate", "pr")
+    POOLED_TASKS = ("inpainting", "declipping", "bwe", "bwe_iir", "bwe_declip", "bwe_lowrate", "pr")
 
     def _pooled_task(self, task, device, filt=None, filt_type=None, factor=None):
         """(check(group, max_batch, seeds), build(group, max_batch, seeds) -> restore.Group, predict(), step, L) of predict_long_pooled: per
         task the refusals of the matching predict_*_long before its arguments are judged, its check_*_args, its group builder, and the one
         predict closure (made by ``predict()``, after the checks) and step that the groups of a call share (the taps, the ratio, win_size / hop_size)."""
-        from . import bwe_iir_long, bwe_long, declip_long, lowrate_long, phase_long, restore
+        from . import bwe_declip_long, bwe_iir_long, bwe_long, declip_long, lowrate_long, phase_long, restore
         if task == "inpainting":
             L, end = self._long_grid("predict_inpainting_long")
             return (lambda g, mb, sd: restore.check_restore_args(g[0], g[1], L, end, mb, sd),
@@ -672,6 +694,11 @@ class Sampler:
                 return shared[0]
             return (lambda g, mb, sd: bwe_iir_long.check_bwe_iir_args(g[0], filt, filt_type, L, end, mb, sd),
                     lambda g, mb, sd: bwe_iir_long.bwe_iir_group(g[0], filt, filt_type, L, end, mb, sd, table=predict().table), predict, L - end, L)
+        if task == "bwe_declip":
+            L, end = self._long_grid("predict_bwe_declip_long", consistency=bwe_declip_long.NO_PROJECTION)
+            return (lambda g, mb, sd: bwe_declip_long.check_bwe_declip_args(g[0], filt, filt_type, g[1], g[2], L, end, mb, sd),
+                    lambda g, mb, sd: bwe_declip_long.bwe_declip_group(g[0], filt, filt_type, g[1], g[2], L, end, mb, sd),
+                    lambda: bwe_declip_long.bwe_declip_predict(self, filt, L, device), L - end, L)
         if task == "bwe_lowrate":
             L, end = self._long_grid("predict_bwe_lowrate_long", consistency="y + x - A(x) is undefined for an operator that changes the length")
             ft = "resample" if filt_type is None else filt_type
@@ -688,10 +715,10 @@ class Sampler:
                 lambda: phase_long.pr_predict(self, win, hop, L), L - restore.aligned_end(L, end, hop), L)
 
     def predict_long_pooled(self, task, groups, max_batch=8, seeds=None, **task_args):
-        """Whole recordings of DIFFERENT lengths in shared passes: ``task`` is "inpainting", "declipping", "bwe", "bwe_iir", "bwe_lowrate" or "pr", and every
+        """Whole recordings of DIFFERENT lengths in shared passes: ``task`` is "inpainting", "declipping", "bwe", "bwe_iir", "bwe_declip", "bwe_lowrate" or "pr", and every
         entry of ``groups`` is what the matching predict_*_long takes for one set of equal-length recordings -- (y, mask), (y, clip_value), y, y,
-        (y, length) and (y, length); a bare tensor is (y,) and a missing second entry None.  ``task_args`` are the arguments all groups share:
-        ``filt``, ``filt_type`` for "bwe" and "bwe_iir"; ``factor``, ``filt_type`` = "resample" for "bwe_lowrate".  -> one [R_g, N_g] per group, in order.
+        (y, clip_value, mask), (y, length) and (y, length); a bare tensor is (y,) and a missing entry None.  ``task_args`` are the arguments all groups share:
+        ``filt``, ``filt_type`` for "bwe", "bwe_iir" and "bwe_declip"; ``factor``, ``filt_type`` = "resample" for "bwe_lowrate".  -> one [R_g, N_g] per group, in order.
         The even windows of ALL groups run as one pooled pass in chunks of at most ``max_batch``, then the odd ones (restore.run_pooled_passes):
         a chunk may hold windows of several recordings and lengths, so a folder of short files runs at the sampler's full-batch rate.
         ``seeds``: one per recording, over all groups in order; the window w of a recording runs with seed * 65536 + w as in the plain
@@ -708,10 +735,12 @@ class Sampler:
                                 "(call predict_spectrogram_inpainting_long per length)")
         if task not in self.POOLED_TASKS:
             raise NotImplementedError(f"predict_long_pooled: unknown task {task!r} (one of {', '.join(self.POOLED_TASKS)})")
-        allowed = {"bwe": ("filt", "filt_type"), "bwe_iir": ("filt", "filt_type"), "bwe_lowrate": ("factor", "filt_type")}.get(task, ())
-        if set(task_args) - set(allowed) or (task in ("bwe", "bwe_iir") and set(task_args) != set(allowed)) or (task == "bwe_lowrate" and "factor" not in task_args):
+        allowed = {"bwe": ("filt", "filt_type"), "bwe_iir": ("filt", "filt_type"), "bwe_declip": ("filt", "filt_type"),
+                   "bwe_lowrate": ("factor", "filt_type")}.get(task, ())
+        if set(task_args) - set(allowed) or (task in ("bwe", "bwe_iir", "bwe_declip") and set(task_args) != set(allowed)) or (task == "bwe_lowrate" and "factor" not in task_args):
             raise TypeError(f"predict_long_pooled({task!r}) takes the task arguments ({', '.join(allowed)}), got ({', '.join(task_args)})")
-        groups = [tuple(g) + (None,) * (2 - len(g)) if isinstance(g, (tuple, list)) else (g, None) for g in groups]
+        width = 3 if task == "bwe_declip" else 2
+        groups = [tuple(g) + (None,) * (width - len(g)) if isinstance(g, (tuple, list)) else (g,) + (None,) * (width - 1) for g in groups]
         device = next((g[0].device for g in groups if torch.is_tensor(g[0])), None)
         check, build, predict, step, L = self._pooled_task(task, device, **task_args)
         bounds = [0]

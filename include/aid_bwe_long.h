@@ -102,6 +102,27 @@ int aid_bwe_gather(const aid_bwe_gather_params* p, void* stream);
 int aid_iir_observed(const aid_fir_observed_params* p, void* stream);
 int aid_iir_gather(const aid_bwe_gather_params* p, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * aid_fir_clip_observed -- the same window seen through the FIR filter FOLLOWED BY a hard clipper, one level per item
+ *   (bwe_declip_long.py), on the parameter block of aid_fir_observed: h is a float table [K + B], the K taps, then the level
+ *   c_b of every item (> 0; +inf: the item is not clipped).  States, P, "samples outside [0, L) are 0" and the sums as
+ *   aid_fir_observed; k = state[b, i].
+ *   mode 0 (apply):       xin = k <= -2 ? 0 : x;  c[i] = sum_{j<K} h[j] xin[i + j - P]
+ *                         out[b, i]     = k > 0 ? x : (k == 0 ? fminf(fmaxf(c, -c_b), c_b) : 0)      plane 0: the observation
+ *                         out[B + b, i] = k == 0 ? c : 0                                             plane 1: the pre-clip sum
+ *                         out holds TWO planes of B rows, [2 B] rows with row stride out_ld: the plane stride is B * out_ld.
+ *   mode 1 (adjoint):     x: incoming gradient; y: plane 1 of the matching mode-0 launch, row stride y_ld >= L
+ *                         gin = (k == 0 and -c_b <= y <= c_b) ? x : 0      (inclusive bounds, as aid_clip and aid_clip_known)
+ *                         a[i] = sum_{j<K} h[j] gin[i - j + P];   out = k <= -2 ? 0 : (k > 0 ? a + x : a)        one plane
+ *   Any other mode is refused (the clipped filter has no projection), and so is a null y in mode 1; y may be null in mode 0.
+ *   Strides, the shared state row (state_ld = 0) and the no-overlap rule are those of aid_fir_observed.  The sums are
+ *   aid_fir_observed's, in the same order: plane 0 carries the bits of aid_clip_known (mode 0, states 0 / 1 / < 0) applied to
+ *   mode 0 of aid_fir_observed, plane 1 those of aid_fir_observed where k == 0, and mode 1 those of aid_fir_observed's mode 1
+ *   applied to aid_clip_known's mode 1 -- in one launch each instead of two.  With every level +inf, modes 0 (plane 0) and 1
+ *   give aid_fir_observed's bits.  Selections are exact.  No LDS beyond the tile's, no atomics, nothing kept between calls.
+ * ------------------------------------------------------------------------------------------------- */
+int aid_fir_clip_observed(const aid_fir_observed_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,18 @@ typedef struct {
 int aid_window_gather(const aid_window_gather_params* p, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * aid_gap_states -- dropouts of a filtered recording (bwe_declip_long.py), on the parameter block of aid_window_gather, IN
+ *   PLACE over the rows aid_bwe_gather (aid_bwe_long.h) produced: y its observations, m its states.  For job j, i < L and
+ *   q = s_j + i < N:
+ *   m[j, i] == 0  and  mask[r_j, q] == 0      m[j, i] = -1,  y[j, i] = 0      (a dropped filtered sample is unobserved)
+ *   Everything else is untouched: the other states, samples at or past N, and the rows of a job whose r is outside [0, R) or
+ *   whose s is outside [0, N) (skipped).  mask: [R, N] with row stride mask_ld >= N, or one shared row (mask_ld = 0); y, m:
+ *   contiguous [J, L], not overlapping mask.  rec, out, rec_ld and out_ld are unused; rec and out may be null.  Comparisons
+ *   and constants only (bit-exact); no atomics.
+ * ------------------------------------------------------------------------------------------------- */
+int aid_gap_states(const aid_window_gather_params* p, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * aid_window_scatter -- out[r_j, s_j + i] = x[j, i]   for lo_j <= i < hi_j and s_j + i < N
  *   x: contiguous [J, L]; out: [R, N] with row stride out_ld >= N.  The owned ranges of the jobs of one call must not
  *   overlap (restore_plan: they partition the recording), so no atomics.  Copies only (bit-exact).
