@@ -459,7 +459,11 @@ ABIS = (
         launches={"aid_fir": FirParams, "aid_iir": IirParams, "aid_clip": ClipParams}),
     Abi("aid_phase.h", "aid_phase_abi_version", 1,
         structs={"aid_stft_mag_params": StftMagParams, "aid_matrix_norm_params": MatrixNormParams},
-        launches={"aid_stft_mag": StftMagParams, "aid_matrix_norm_seed": MatrixNormParams}),
+        # (blind.py: aid_stft_band_stats reads x = x_hat, g = |Y| [B, F, T], frames = scratch [B, T, 2, F], out = stats [B, 2, F], adjoint = 0;
+        #  aid_lowpass_fit reads den = stats, y = float table [NC cut-offs | NA slopes | floor_dB, k_lo], r = tap window [K], writes g = taps [B, K] and
+        #  norm = fit [B, 4]; diag = null, T = NC, ord = NA, max_iter = K, tol = eps)
+        launches={"aid_stft_mag": StftMagParams, "aid_matrix_norm_seed": MatrixNormParams,
+                  "aid_stft_band_stats": StftMagParams, "aid_lowpass_fit": MatrixNormParams}),
     Abi("aid_autoregressive.h", "aid_ar_abi_version", 1,
         structs={"aid_ar_carry_params": ArCarryParams}, launches={"aid_ar_carry": ArCarryParams}),
     Abi("aid_restore.h", "aid_restore_abi_version", 1,
@@ -474,7 +478,9 @@ ABIS = (
     Abi("aid_bwe_long.h", "aid_bwe_long_abi_version", 1,
         structs={"aid_fir_observed_params": FirObservedParams, "aid_bwe_gather_params": BweGatherParams},
         launches={"aid_fir_observed": FirObservedParams, "aid_bwe_gather": BweGatherParams,
-                  "aid_iir_observed": FirObservedParams, "aid_iir_gather": BweGatherParams, "aid_fir_clip_observed": FirObservedParams}),
+                  "aid_iir_observed": FirObservedParams, "aid_iir_gather": BweGatherParams, "aid_fir_clip_observed": FirObservedParams,
+                  # (blind.py: aid_fir_observed's fields, h = taps [B, K] with row stride K)
+                  "aid_fir_observed_items": FirObservedParams}),
     Abi("aid_lowrate_long.h", "aid_lowrate_long_abi_version", 1,
         structs={"aid_rate_observed_params": RateObservedParams, "aid_lowrate_gather_params": LowrateGatherParams},
         launches={"aid_rate_observed": RateObservedParams, "aid_lowrate_gather": LowrateGatherParams}),

@@ -412,6 +412,46 @@ class Sampler:
             raise NotImplementedError(f"predict_bwe: unknown filt_type {filt_type!r}")
         return self.predict_conditional(ylpf, op)
 
+    def predict_blind_bwe(self, y, frozen_taps=None):
+        """Blind bandwidth extension (blind.py): y [B, L = args.exp.audio_len] on the GPU went through an UNKNOWN zero-phase low-pass -> x [B, L].
+        One predict_resample through blind.BlindLowpass, which fits a one-knee low-pass per item to the current estimate inside every guided
+        evaluation (statistics, fit, filter: three launches, no host round trip) and guides through the taps it found.  Afterwards
+        ``blind_fit`` [B, 2] holds the cut-off in Hz and the slope in dB per octave of the last evaluation, ``blind_taps`` [B, K] its taps and
+        ``blind_operator`` the operator.  Settings: args.tester.blind_bwe where the config has it (n_fft, hop, K, floor_dB, k_lo, eps, cutoffs,
+        slopes), else the defaults of blind.py.  ``frozen_taps`` [B, K] or [K]: no fit, guidance through these taps (equal rows: predict_bwe
+        "firwin" bit for bit).  Guidance only -- xi > 0, data consistency off, rid False -- checked before anything is installed.  A whole
+        recording: run this on one segment, then predict_bwe_long(y, blind_taps[b], "firwin")."""
+        from . import blind
+        if self.rid:
+            raise _lib.AidError("predict_blind_bwe returns the restored segments only: rid must be False")
+        if not self.xi > 0:
+            raise _lib.AidError("predict_blind_bwe needs reconstruction guidance: tester.posterior_sampling.xi must be > 0 (the filter is fitted inside "
+                                "the guided evaluation)")
+        if self.data_consistency or self.data_consistency_end:
+            raise _lib.AidError("predict_blind_bwe runs without data consistency (a projection onto the consistent set of an estimated filter is not a "
+                                "projection onto the data): set tester.data_consistency.use = False")
+        cfg = blind.settings_of(self.args)
+        L = int(self.args.exp.audio_len)
+        if not (torch.is_tensor(y) and y.dtype == torch.float32 and y.dim() == 2 and y.shape[0] >= 1 and y.shape[1] == L):
+            raise _lib.AidError(f"predict_blind_bwe: y must be float32 [B, {L}] (args.exp.audio_len samples), got "
+                                f"{tuple(y.shape) if torch.is_tensor(y) else type(y).__name__}")
+        if frozen_taps is not None:
+            frozen_taps = blind.frozen_rows(frozen_taps, y.shape[0], cfg.K)
+        if not y.is_cuda:
+            raise _lib.AidError("predict_blind_bwe runs on the GPU only (no CPU fallback): y must be a float32 tensor on the GPU")
+        self._check_model()
+        y = y.contiguous()
+        op = blind.BlindLowpass(y, cfg, taps=frozen_taps, frozen=frozen_taps is not None)
+        op.log = self.blind_log
+        self.blind_operator = op
+        x = self.predict_resample(y, tuple(y.shape), op)
+        self.blind_taps = op.taps
+        self.blind_fit = blind.fit_in_hz(op.fit, cfg, self.args.exp.sample_rate)
+        return x
+
+    blind_log = None            # set to [] before predict_blind_bwe to record (taps, fit) of every evaluation (blind.BlindLowpass.log)
+    blind_fit = blind_taps = blind_operator = None
+
     def predict_declipping(self, y_clipped, clip_value):
         """(SamplerDeclipping.predict_declipping, edm_sampler.py:370-385) guidance through hard clipping at +-clip_value; the reference
         asserts data consistency off -- with tester.data_consistency.use the first projection raises."""

@@ -123,6 +123,14 @@ int aid_iir_gather(const aid_bwe_gather_params* p, void* stream);
  * ------------------------------------------------------------------------------------------------- */
 int aid_fir_clip_observed(const aid_fir_observed_params* p, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * aid_fir_observed_items -- aid_fir_observed with one filter per item (blind.py: the taps fitted for every item), on the parameter
+ *   block of aid_fir_observed: h is a float table [B, K] with row stride K, item b is filtered with h[b, 0..K).  Everything else --
+ *   states, modes 0 / 1 / 2, strides, the shared state row (state_ld = 0), the no-overlap rule, the sums and their order -- is
+ *   aid_fir_observed's: with equal rows of h it gives aid_fir_observed's bits, and with every state 0 as well those of aid_fir.
+ * ------------------------------------------------------------------------------------------------- */
+int aid_fir_observed_items(const aid_fir_observed_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,33 @@ typedef struct {
 } aid_matrix_norm_params;
 int aid_matrix_norm_seed(const aid_matrix_norm_params* p, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Blind bandwidth extension (blind.py): the statistics and the fit of a one-knee low-pass, on the two parameter blocks above.
+ *
+ * aid_stft_band_stats -- on aid_stft_mag_params, with the framing, window and twiddle of aid_stft_mag (T = n_frames, F = N/2 + 1):
+ *   x [B, L] (row stride x_ld) = the current estimate x_hat; g [B, F, T] contiguous = |Y|, an output of aid_stft_mag;
+ *   out [B, 2, F] contiguous:  out[b, 0, k] = Sxx = sum_t |X[b, k, t]|^2,   out[b, 1, k] = Sxy = sum_t |X[b, k, t]| * g[b, k, t]
+ *   |X| carries aid_stft_mag's bits (the same frame body).  frames [B, T, 2, F] contiguous is scratch: one workgroup per frame writes
+ *   its fp32 products there, a second pass adds them over t = 0 .. T-1 in fp64 and rounds once.  No atomics; deterministic; item b
+ *   does not depend on the other items.  adjoint must be 0, g and frames non-null; out_ld is not read.
+ *
+ * aid_lowpass_fit -- on aid_matrix_norm_params, one workgroup per item, fp64, static LDS only, nothing kept between calls:
+ *   den  = stats [B, 2, F], an output of aid_stft_band_stats                                                            (read)
+ *   y    = a float table [NC + NA + 2]: cut-off candidates c_j > 0 in bins, slope candidates A_i < 0 in dB per octave,
+ *          then floor_dB (< 0) and k_lo (>= 0, a whole number)                                                          (read)
+ *   r    = the tap window w [K]                                                                                         (read)
+ *   g    = taps [B, K]                                                                                                  (written)
+ *   norm = fit [B, 4]: c, A, cost, number of valid bins                                                                 (written)
+ *   diag = must be null;   T = NC,  ord = NA,  max_iter = K (odd, K <= N - 1, N = 2 (F - 1)),  tol = eps;   F in [9, 1025]
+ *   H(k; c, A) = 10^(max(floor_dB, min(0, A log2(k / c))) / 20) for k > c, 1 for k <= c;   gmin = 10^(floor_dB / 20)
+ *   g_k = clamp(Sxy_k / Sxx_k, gmin, 1);  bin k is valid when k >= k_lo and Sxx_k >= eps * max_k Sxx_k and Sxx_k > 0
+ *   cost(j, i) = mean over the valid bins of (H(k; c_j, A_i) - g_k)^2  (0 without a valid bin); the lowest cost wins, ties go to the
+ *   lowest j, then the lowest i.  With (c, A) the winner, P = (K - 1) / 2 and H_k = H(k; c, A):
+ *   taps[b, n] = w[n] / N * (H_0 + 2 sum_{k=1}^{N/2-1} H_k cos(2 pi k (n - P) / N) + H_{N/2} cos(pi (n - P))),  rounded to fp32 once.
+ * ------------------------------------------------------------------------------------------------- */
+int aid_stft_band_stats(const aid_stft_mag_params* p, void* stream);
+int aid_lowpass_fit(const aid_matrix_norm_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
