@@ -395,6 +395,8 @@ class SpecGatherParams(C.Structure):
 
 AID_SPEC_ITEM_FIELDS = 3
 
+AID_LOWPASS_FIT_MAX_ITEMS = 256        # aid_lowpass_fit_groups: the group ids of a launch travel in the kernel arguments
+
 
 class Abi(NamedTuple):
     """One header under include/ as the binding sees it.  Adding a header, a struct or an export is one edit here: ``lib()`` binds from this table and
@@ -463,7 +465,9 @@ ABIS = (
         #  aid_lowpass_fit reads den = stats, y = float table [NC cut-offs | NA slopes | floor_dB, k_lo], r = tap window [K], writes g = taps [B, K] and
         #  norm = fit [B, 4]; diag = null, T = NC, ord = NA, max_iter = K, tol = eps)
         launches={"aid_stft_mag": StftMagParams, "aid_matrix_norm_seed": MatrixNormParams,
-                  "aid_stft_band_stats": StftMagParams, "aid_lowpass_fit": MatrixNormParams}),
+                  "aid_stft_band_stats": StftMagParams, "aid_lowpass_fit": MatrixNormParams,
+                  # (blind_long.py: aid_lowpass_fit's fields, diag = B group ids as ints in HOST memory, read by the launcher)
+                  "aid_lowpass_fit_groups": MatrixNormParams}, macros=("AID_LOWPASS_FIT_MAX_ITEMS",)),
     Abi("aid_autoregressive.h", "aid_ar_abi_version", 1,
         structs={"aid_ar_carry_params": ArCarryParams}, launches={"aid_ar_carry": ArCarryParams}),
     Abi("aid_restore.h", "aid_restore_abi_version", 1,
@@ -480,7 +484,9 @@ ABIS = (
         launches={"aid_fir_observed": FirObservedParams, "aid_bwe_gather": BweGatherParams,
                   "aid_iir_observed": FirObservedParams, "aid_iir_gather": BweGatherParams, "aid_fir_clip_observed": FirObservedParams,
                   # (blind.py: aid_fir_observed's fields, h = taps [B, K] with row stride K)
-                  "aid_fir_observed_items": FirObservedParams}),
+                  "aid_fir_observed_items": FirObservedParams,
+                  # (blind_long.py: rec = recordings, jobs = the job table, y = J doubles, the energy of every job's window)
+                  "aid_window_energy": BweGatherParams}),
     Abi("aid_lowrate_long.h", "aid_lowrate_long_abi_version", 1,
         structs={"aid_rate_observed_params": RateObservedParams, "aid_lowrate_gather_params": LowrateGatherParams},
         launches={"aid_rate_observed": RateObservedParams, "aid_lowrate_gather": LowrateGatherParams}),

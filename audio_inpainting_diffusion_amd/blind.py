@@ -26,8 +26,8 @@ projection onto the data.
 tested against.  ``BlindLowpass`` is the operator (restore.WindowOperator's protocol); ``Sampler.predict_blind_bwe`` drives it.  GPU only for
 the operator; no fallback.
 
-Not covered: whole recordings (one filter per recording pooled over its windows -- until then: run blind on one segment, then
-``predict_bwe_long(y, sampler.blind_taps[b], "firwin")``), more than one knee, IIR or decimating models.
+Whole recordings, one filter per recording pooled over several of its windows: blind_long.py (``Sampler.predict_blind_bwe_long``).
+Not covered: more than one knee, IIR or decimating models.
 """
 from __future__ import annotations
 

@@ -7,24 +7,18 @@
 //                              read n_fft / hop times through LDS, |Y| once.
 //   band_stats_sum_kernel    : grid (tiles of 64 of the 2 F columns, items); 4 lane groups add a quarter of the frames each, ascending, in fp64,
 //                              and the four partial sums are added in group order: a fixed order, no atomics.
-//   lowpass_fit_kernel       : one workgroup of 1024 lanes per item, all in fp64.  g_k and the valid bins -> LDS; the pass band left of a cut-off
-//                              and the stop band at the floor are prefix / suffix sums, so a candidate (c_j, A_i) costs only the bins of its
-//                              transition: H = k^(A s) / c^(A s), s = log2(10) / 20, with k^(A s) tabulated once per slope.  The two halves of
-//                              the workgroup take two slopes at a time; a lane takes a low and a high cut-off (a long and a short transition);
-//                              the arg-min carries (cost, j * NA + i) and breaks ties by the lower index.
-//                              Then H on the grid and the taps by frequency sampling, cosines from a quarter-wave-exact table of N/2 + 1 entries.
+//   lowpass_fit_kernel       : one workgroup of 1024 lanes per item, all in fp64: the fit and the tap design of aid_lowpass_fit.h on the
+//                              statistics of the item.
 //   fir_observed_items_kernel: fir_observed_kernel of aid_bwe_long.hip with the taps of item b at h + b * K (the tile loop fir_tile).
 #include "aid_rows.h"
 #include "aid_fir_tile.h"
 #include "aid_stft_mag_tile.h"
+#include "aid_lowpass_fit.h"
 #include "aid_phase.h"
 #include "aid_bwe_long.h"
 
 #define BS_COLS 64                        // columns of the scratch per workgroup of the sum pass
 #define BS_GROUPS 4                       // lane groups that share the frames of a column
-#define LF_THREADS 1024
-#define LF_WAVES (LF_THREADS / AID_WAVE)
-#define LF_MAX_F 1025                     // n_fft <= 2048: five fp64 tables of F entries in static LDS
 
 // ---- band statistics -------------------------------------------------------------------------------------------------
 struct bs_row {                                                    // sample q of the row, 0 at and past L
@@ -86,146 +80,13 @@ extern "C" int aid_stft_band_stats(const aid_stft_mag_params* p, void* stream) {
 }
 
 // ---- the fit ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double lf_wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
+// (the body is lf_fit_and_design of aid_lowpass_fit.h, shared with lowpass_fit_groups_kernel of aid_blind_long.hip)
 __global__ __launch_bounds__(LF_THREADS) void lowpass_fit_kernel(const aid_matrix_norm_params p) {
-    __shared__ double gk[LF_MAX_F];                 // g_k, -1 where the bin is not valid
-    __shared__ double Ek[2][LF_MAX_F];              // k^(A s) of the two slopes in hand; [0]: H_k of the winner at the end
-    __shared__ double P1[LF_MAX_F + 1];             // P1[m] = sum over the valid k < m of (1 - g_k)^2; the cosine table at the end
-    __shared__ double S3[LF_MAX_F + 1];             // S3[m] = sum over the valid k >= m of (gmin - g_k)^2
-    __shared__ double redv[LF_WAVES];
-    __shared__ int redi[LF_WAVES];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int F = p.F, NC = p.T, NA = p.ord, K = p.max_iter, N = 2 * (F - 1);
-    const float* __restrict__ sxx = p.den + (int64_t)b * 2 * F;
-    const float* __restrict__ sxy = sxx + F;
-    const float* __restrict__ cc = p.y;
-    const float* __restrict__ ca = cc + NC;
-    const double floor_dB = (double)ca[NA], s20 = 0.16609640474436813;       // log2(10) / 20
-    const double gmin = exp2(floor_dB * s20);
-    const int k_lo = (int)fminf(fmaxf(ca[NA + 1], 0.f), (float)F);
-
-    // the largest Sxx, then g_k and the valid bins
-    double mx = 0.0;
-    for (int k = tid; k < F; k += LF_THREADS) mx = fmax(mx, (double)sxx[k]);
-    mx = lf_wave_max(mx);
-    if (lane == 0) redv[wave] = mx;
-    __syncthreads();
-    mx = redv[0];
-    for (int i = 1; i < LF_WAVES; ++i) mx = fmax(mx, redv[i]);
-    const double thr = p.tol * mx;
-    for (int k = tid; k < F; k += LF_THREADS) {
-        const double xx = (double)sxx[k];
-        const bool valid = k >= k_lo && xx > 0.0 && xx >= thr;
-        gk[k] = valid ? fmin(fmax((double)sxy[k] / xx, gmin), 1.0) : -1.0;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double a = 0.0;
-        P1[0] = 0.0;
-        for (int k = 0; k < F; ++k) {
-            const double g = gk[k], d = 1.0 - g;
-            if (g >= 0.0) a = fma(d, d, a);
-            P1[k + 1] = a;
-        }
-    } else if (tid == AID_WAVE) {
-        double a = 0.0;
-        int n = 0;
-        S3[F] = 0.0;
-        for (int k = F - 1; k >= 0; --k) {
-            const double g = gk[k], d = gmin - g;
-            if (g >= 0.0) { a = fma(d, d, a); ++n; }
-            S3[k] = a;
-        }
-        redi[0] = n;
-    }
-    __syncthreads();
-    const int n_valid = redi[0];
-    const double inv_n = n_valid > 0 ? 1.0 / (double)n_valid : 0.0;
-    __syncthreads();                                          // (redi is written again below)
-
-    // every candidate: lane-private best (cost, j * NA + i), ties to the lower index.  The transition of a low cut-off is long and that of a
-    // high one short, so lane q of a half takes the cut-offs j = q and NC - 1 - q (q += 512): about F bins per lane and slope whatever q.
-    // The two halves of the workgroup take the two slopes of a pair, each with its own table k^(A s).
-    const int half_id = tid >> 9, q0 = tid & (LF_THREADS / 2 - 1), n_pairs = (NC + 1) / 2;
-    double bc = INFINITY;
-    int bi = 0x7fffffff;
-    for (int i0 = 0; i0 < NA; i0 += 2) {
-        for (int e = tid; e < 2 * F; e += LF_THREADS) {
-            const int s = e >= F, k = e - s * F, i = i0 + s;
-            Ek[s][k] = (k && i < NA) ? exp2((double)ca[i] * s20 * log2((double)k)) : 1.0;
-        }
-        __syncthreads();
-        const int i = i0 + half_id;
-        if (i < NA) {
-            const double As = (double)ca[i] * s20;
-            const double* __restrict__ E = Ek[half_id];
-            for (int q = q0; q < n_pairs; q += LF_THREADS / 2) {
-                for (int side = 0; side < 2; ++side) {
-                    const int j = side ? NC - 1 - q : q;
-                    if (side && j <= q) break;                 // (the middle cut-off of an odd NC is taken once)
-                    const double c = (double)cc[j];
-                    const double inv = exp2(-As * log2(c));
-                    const int k0 = min((int)floor(fmin(fmax(c, 0.0), (double)F)) + 1, F);      // the first bin right of the cut-off
-                    double acc = P1[k0];
-                    for (int k = k0; k < F; ++k) {
-                        double h = E[k] * inv;
-                        if (h <= gmin) { acc += S3[k]; break; }      // at the floor from here on (k^(A s) falls with k)
-                        h = fmin(h, 1.0);
-                        const double g = gk[k], d = h - g;
-                        if (g >= 0.0) acc = fma(d, d, acc);
-                    }
-                    const double cost = acc * inv_n;
-                    const int idx = j * NA + i;
-                    if (cost < bc || (cost == bc && idx < bi)) { bc = cost; bi = idx; }
-                }
-            }
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double oc = __shfl_xor(bc, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (oc < bc || (oc == bc && oi < bi)) { bc = oc; bi = oi; }
-    }
-    if (lane == 0) { redv[wave] = bc; redi[wave] = bi; }
-    __syncthreads();
-    bc = redv[0]; bi = redi[0];
-    for (int i = 1; i < LF_WAVES; ++i)
-        if (redv[i] < bc || (redv[i] == bc && redi[i] < bi)) { bc = redv[i]; bi = redi[i]; }
-    if (bi == 0x7fffffff) bi = 0;                             // (no cost compared: statistics that are not numbers)
-    const double c = (double)cc[bi / NA], A = (double)ca[bi % NA];
-    if (tid == 0) {
-        float* fit = p.norm + (int64_t)b * 4;
-        fit[0] = (float)c; fit[1] = (float)A; fit[2] = (float)bc; fit[3] = (float)n_valid;
-    }
-
-    // H on the grid, cos(2 pi m / N) for m <= N/2, then the taps
-    const double lc = log2(c);
-    double* __restrict__ Hk = Ek[0];
-    for (int k = tid; k < F; k += LF_THREADS) {
-        Hk[k] = (double)k <= c ? 1.0 : exp2(fmax(floor_dB, fmin(0.0, A * (log2((double)k) - lc))) * s20);
-        P1[k] = cospi(2.0 * (double)k / (double)N);
-    }
-    __syncthreads();
-    const int P = (K - 1) / 2, half = N >> 1;
-    const float* __restrict__ w = p.r;
-    float* __restrict__ taps = p.g + (int64_t)b * K;
-    for (int n = tid; n < K; n += LF_THREADS) {
-        const int d = n - P;
-        double acc = Hk[0];
-        for (int k = 1; k < half; ++k) {
-            const int m = (k * d) & (N - 1), mm = m > half ? N - m : m;
-            acc = fma(2.0 * Hk[k], P1[mm], acc);
-        }
-        acc += (d & 1) ? -Hk[half] : Hk[half];
-        taps[n] = (float)((double)w[n] / (double)N * acc);
-    }
+    __shared__ lf_lds lds;
+    const int b = blockIdx.x, F = p.F;
+    const float* __restrict__ st = p.den + (int64_t)b * 2 * F;
+    lf_fit_and_design(lds, [&](int s, int k) { return (double)st[s * F + k]; }, F, p.T, p.ord, p.max_iter, p.y, p.tol, p.r,
+                      p.norm + (int64_t)b * 4, p.g + (int64_t)b * p.max_iter);
 }
 
 extern "C" int aid_lowpass_fit(const aid_matrix_norm_params* p, void* stream) {

@@ -238,6 +238,30 @@ def bwe_long(sampler, files: Sequence[torch.Tensor], filt, filt_type: str = "fir
         pooled=None if not pool else lambda gs, sd: sampler.predict_long_pooled("bwe", [y for y, _, _ in gs], max_batch=max_batch, seeds=sd, filt=filt, filt_type=filt_type))
 
 
+def blind_bwe_long(sampler, files: Sequence[torch.Tensor], probes: int = 4, seeds: Optional[Sequence[int]] = None, max_batch: int = 8,
+                   device="cuda") -> List[torch.Tensor]:
+    """Bandwidth-extend every 1-D waveform of ``files`` (any lengths), each low-passed as a whole by an unknown low-pass of its own, and return
+    the full-length results on ``device``, in the order of ``files``.  Files of equal length go through ONE Sampler.predict_blind_bwe_long
+    call: their probe windows share the chunks of stage 1 and their windows the two batched passes of stage 2; every other length is a call
+    of its own -- there is no ``pool`` argument.  Afterwards ``sampler.blind_fit`` [len(files), 2], ``sampler.blind_taps`` [len(files), K] and
+    ``sampler.blind_probes`` hold every file's filter, in the order of ``files``.  ``seeds``: one RNG seed per file (file i's filter and result
+    then depend on seeds[i] alone, not on the grouping).  Under an active process group every rank passes the same files and gets the full
+    results, and ``seeds`` = None means dist.item_seeds(0, 0, len(files)), as bwe_long."""
+    held = {}
+
+    def call(y, idx, _, sd):
+        res = sampler.predict_blind_bwe_long(y, probes=probes, max_batch=max_batch, seeds=sd)
+        for j, i in enumerate(idx):
+            held[i] = (sampler.blind_fit[j], sampler.blind_taps[j], sampler.blind_probes[j])
+        return res
+    out = _long_groups("blind_bwe_long", files, seeds, device, lambda i: files[i].numel(), call)
+    if held:
+        sampler.blind_fit = torch.stack([held[i][0] for i in range(len(files))])
+        sampler.blind_taps = torch.stack([held[i][1] for i in range(len(files))])
+        sampler.blind_probes = [held[i][2] for i in range(len(files))]
+    return out
+
+
 def bwe_iir_long(sampler, files: Sequence[torch.Tensor], filt, filt_type: str = "cheby1", seeds: Optional[Sequence[int]] = None, max_batch: int = 8,
                  device="cuda", pool: bool = False) -> List[torch.Tensor]:
     """Bandwidth-extend every 1-D waveform of ``files`` (any lengths), each low-passed as a whole with the IIR filter ``filt`` ("cheby1": (b, a);

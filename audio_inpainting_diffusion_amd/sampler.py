@@ -420,7 +420,7 @@ class Sampler:
         ``blind_operator`` the operator.  Settings: args.tester.blind_bwe where the config has it (n_fft, hop, K, floor_dB, k_lo, eps, cutoffs,
         slopes), else the defaults of blind.py.  ``frozen_taps`` [B, K] or [K]: no fit, guidance through these taps (equal rows: predict_bwe
         "firwin" bit for bit).  Guidance only -- xi > 0, data consistency off, rid False -- checked before anything is installed.  A whole
-        recording: run this on one segment, then predict_bwe_long(y, blind_taps[b], "firwin")."""
+        recording goes through predict_blind_bwe_long, which fits one filter per recording pooled over several of its windows."""
         from . import blind
         if self.rid:
             raise _lib.AidError("predict_blind_bwe returns the restored segments only: rid must be False")
@@ -596,6 +596,39 @@ class Sampler:
         bwe_long.check_bwe_args(y, filt, filt_type, L, end, max_batch, seeds)
         self._check_model()
         return bwe_long.bwe_passes(self, y, filt, filt_type, L, end, max_batch, seeds)
+
+    def predict_blind_bwe_long(self, y, probes=4, max_batch=8, seeds=None, frozen_taps=None):
+        """Blind bandwidth extension of whole recordings y[R, N] -- N any length, each low-passed as a whole by an UNKNOWN zero-phase low-pass
+        of its own -> [R, N] on y.device (blind_long.py).  Two stages, both through predict_resample.  Stage 1 fits ONE filter per recording:
+        its ``probes`` windows of largest energy among the windows of predict_bwe_long's grid that lie wholly inside it (one aid_window_energy
+        launch, read back once; window 0 when N < L) are sampled in chunks of whole recordings of at most ``max_batch`` probes through
+        blind_long.PooledBlindLowpass, which in every guided evaluation fits one low-pass to the band statistics of all probes of a recording
+        together (statistics, pooled fit, filter: three launches, no host round trip; on one stream); nothing carries over between evaluations
+        and the probes' restorations are discarded.  Stage 2 is predict_bwe_long -- the grid, the ownership trimmed by K - 1 (more than one
+        window needs end = int(overlap * L) >= 2 (K - 1)), the two batched passes, the seeds -- with the taps fitted for a window's recording
+        (blind_long.FIRObservedRows).  Afterwards ``blind_fit`` [R, 2] holds the cut-off in Hz and the slope in dB per octave of every
+        recording, ``blind_taps`` [R, K] its taps and ``blind_probes`` per recording the starts of the windows that were fitted on.  Settings:
+        blind.settings_of(args), as predict_blind_bwe.  ``frozen_taps`` [K] or [R, K]: stage 1 is skipped entirely (no launch, no sampler
+        call) and the result is predict_bwe_long's with those taps, bit for bit.  Guidance only -- xi > 0, data consistency off, rid False.
+        ``seeds`` [R]: window w of recording r runs with seeds[r] * 65536 + w, its probe p with seeds[r] * 65536 + 65535 - p, so a recording's
+        filter and result depend neither on the other recordings nor on max_batch.  There is no ``pool`` argument: recordings of different
+        lengths are calls of their own.
+        Under an active process group every rank calls with the same y and seeds (required) and gets the full result: rank k estimates the
+        recordings dist.shard_range(R, k, world), one dist.gather_outputs brings all filters to every rank, and stage 2 shares the windows of
+        each pass out as predict_inpainting_long states."""
+        from . import blind, blind_long
+        L, end = self._long_grid("predict_blind_bwe_long", consistency=blind_long.NO_PROJECTION)
+        if not self.xi > 0:
+            raise _lib.AidError("predict_blind_bwe_long needs reconstruction guidance: tester.posterior_sampling.xi must be > 0 (the filter is fitted "
+                                "inside the guided evaluation)")
+        cfg = blind.settings_of(self.args)
+        blind_long.check_blind_long_args(y, cfg, L, end, probes, max_batch, seeds, frozen_taps)
+        self._check_model()
+        out, taps, fit, starts = blind_long.blind_bwe_long_passes(self, y, cfg, L, end, probes, max_batch, seeds, frozen_taps)
+        self.blind_taps, self.blind_fit, self.blind_probes = taps, blind.fit_in_hz(fit, cfg, self.args.exp.sample_rate), starts
+        return out
+
+    blind_probes = None         # after predict_blind_bwe_long: per recording, the starts of the windows its filter was fitted on
 
     def predict_bwe_iir_long(self, y, filt, filt_type, max_batch=8, seeds=None):
         """Bandwidth-extend whole recordings y[R, N] -- N any length, low-passed as a whole with an IIR filter from a zero state -> [R, N] on

@@ -131,6 +131,18 @@ int aid_fir_clip_observed(const aid_fir_observed_params* p, void* stream);
  * ------------------------------------------------------------------------------------------------- */
 int aid_fir_observed_items(const aid_fir_observed_params* p, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * aid_window_energy -- the energy of the windows of a job table (blind_long.py: the windows a recording's filter is fitted on), on
+ *   the parameter block of aid_bwe_gather: for job j of the table of aid_restore.h (r, s, ...; 6 int64),
+ *       energy[j] = sum over i < L with s_j + i < N of rec[r_j, s_j + i]^2        in fp64.
+ *   rec: [R, N] fp32 with row stride rec_ld >= N; jobs: [J, 6] in device memory; y = energy: J DOUBLES behind the float pointer
+ *   (contiguous, 8-byte aligned).  out and state are not read, K and out_ld are ignored.  As in aid_bwe_gather a job whose r is outside
+ *   [0, R) or whose s is outside [0, N) is skipped: its energy is 0.  One workgroup per job: every lane adds the squares of the samples
+ *   i = lane, lane + 256, ... ascending, and the 256 partial sums are added as a fixed binary tree.  No atomics: a second launch gives
+ *   the same bits.
+ * ------------------------------------------------------------------------------------------------- */
+int aid_window_energy(const aid_bwe_gather_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

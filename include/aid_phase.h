@@ -84,9 +84,21 @@ int aid_matrix_norm_seed(const aid_matrix_norm_params* p, void* stream);
  *   cost(j, i) = mean over the valid bins of (H(k; c_j, A_i) - g_k)^2  (0 without a valid bin); the lowest cost wins, ties go to the
  *   lowest j, then the lowest i.  With (c, A) the winner, P = (K - 1) / 2 and H_k = H(k; c, A):
  *   taps[b, n] = w[n] / N * (H_0 + 2 sum_{k=1}^{N/2-1} H_k cos(2 pi k (n - P) / N) + H_{N/2} cos(pi (n - P))),  rounded to fp32 once.
+ *
+ * aid_lowpass_fit_groups -- aid_lowpass_fit on statistics pooled over groups of items (blind_long.py: one filter per recording, fitted
+ *   to all its probe windows together), on aid_matrix_norm_params with aid_lowpass_fit's fields and
+ *   diag = the group ids: B ints in HOST memory behind the float pointer, group[b] in [0, B), B <= AID_LOWPASS_FIT_MAX_ITEMS.  The
+ *          launcher reads them before it returns -- so it can refuse an id outside [0, B) -- and hands them to the kernel with its
+ *          arguments; the memory may be reused as soon as the call returns.
+ *   For item b,  S[s, k] = sum over the items b' with group[b'] == group[b], in ascending b', of stats[b', s, k]  in fp64, and fit[b]
+ *   and taps[b] are those of aid_lowpass_fit on S: the same code on the same candidates, S not rounded to fp32.  Every item of a group
+ *   gets the same bits; with every item in a group of its own the output is aid_lowpass_fit's bit for bit.  One workgroup per item;
+ *   static LDS only; no atomics, nothing kept between calls.  Deterministic.
  * ------------------------------------------------------------------------------------------------- */
+#define AID_LOWPASS_FIT_MAX_ITEMS 256
 int aid_stft_band_stats(const aid_stft_mag_params* p, void* stream);
 int aid_lowpass_fit(const aid_matrix_norm_params* p, void* stream);
+int aid_lowpass_fit_groups(const aid_matrix_norm_params* p, void* stream);
 
 #ifdef __cplusplus
 }
