@@ -143,6 +143,7 @@ __global__ __launch_bounds__(256) void group_dot_partial(const DotDev a) {
 extern "C" int aid_group_dot(const aid_group_dot_params* p, void* stream) {
     AID_REQUIRE(p && p->u.p && p->v.p && p->ws, "aid_group_dot: null pointer");
     AID_REQUIRE(p->groups > 0 && p->C % p->groups == 0 && (p->T % 4) == 0, "aid_group_dot: bad shape");
+    AID_REQUIRE(aid_view_aligned(p->u, 4) && aid_view_aligned(p->v, 4), "aid_group_dot: views must be float4-addressable");
     DotDev a;
     a.p = *p;
     a.cg = p->C / p->groups;
@@ -370,6 +371,8 @@ int aid_w2d_input_nb(const aid_norm_bwd_params* p, const float* coef, hipStream_
 extern "C" int aid_norm_bwd(const aid_norm_bwd_params* p, void* stream) {
     AID_REQUIRE(p && p->gd.p && p->x.p && p->out.p && p->stats && p->ws, "aid_norm_bwd: null pointer");
     AID_REQUIRE(p->groups > 0 && p->C % p->groups == 0 && (p->T % 4) == 0, "aid_norm_bwd: bad shape");
+    AID_REQUIRE(aid_view_aligned(p->gd, 4) && aid_view_aligned(p->x, 4) && (!p->gy.p || aid_view_aligned(p->gy, 4)) && aid_view_aligned(p->out, 4),
+                "aid_norm_bwd: gd, x, gy and out must be float4-addressable");
     AID_REQUIRE(p->coef_ready == 0 || (p->coef_ready == 1 && p->ws_n > 0 && p->groups == 8), "aid_norm_bwd: coef_ready goes with conv-epilogue partials (ws_n > 0, 8 groups)");
     NbDev a;
     a.p = *p;
@@ -552,6 +555,7 @@ extern "C" int aid_scale_act(const aid_scale_act_params* p, void* stream) {
     AID_REQUIRE(p && p->x.p && p->y.p, "aid_scale_act: null pointer");
     AID_REQUIRE((p->T % 4) == 0, "aid_scale_act: T must be a multiple of 4");
     if (p->wino == 3 || p->wino == 4) return aid_w2d_input(p, (hipStream_t)stream);       // 2-D form F(4,5) x F(4,3): V [48][C][N]; wino = 4: F(4,5) x F(8,3), V [80][C][N]
+    AID_REQUIRE(aid_view_aligned(p->x, 4) && (p->wino != 0 || aid_view_aligned(p->y, 4)), "aid_scale_act: x (and y of the plain form) must be float4-addressable");
     SaDev a;
     a.p = *p;
     if (p->wino == 2) {

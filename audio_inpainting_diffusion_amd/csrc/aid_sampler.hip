@@ -82,6 +82,7 @@ __global__ __launch_bounds__(256) void add2_kernel(const Add2Dev a) {
 extern "C" int aid_add2(const aid_add2_params* p, void* stream) {
     AID_REQUIRE(p && p->u.p && p->y.p, "aid_add2: null pointer");
     AID_REQUIRE((p->T % 4) == 0, "aid_add2: T must be a multiple of 4");
+    AID_REQUIRE(aid_view_aligned(p->u, 4) && (!p->v.p || aid_view_aligned(p->v, 4)) && aid_view_aligned(p->y, 4), "aid_add2: views must be float4-addressable");
     Add2Dev a;
     a.p = *p;
     int lpr = aid_pow2ceil(p->T / 4);
