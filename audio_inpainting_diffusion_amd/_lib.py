@@ -486,13 +486,18 @@ ABIS = (
                   # (blind.py: aid_fir_observed's fields, h = taps [B, K] with row stride K)
                   "aid_fir_observed_items": FirObservedParams,
                   # (blind_long.py: rec = recordings, jobs = the job table, y = J doubles, the energy of every job's window)
-                  "aid_window_energy": BweGatherParams}),
+                  "aid_window_energy": BweGatherParams,
+                  # (metrics.py: x = estimate, y = reference, state = region weights or null, h = frame distances [B, K], out = 8 doubles per item)
+                  "aid_eval_sums": FirObservedParams}),
     Abi("aid_lowrate_long.h", "aid_lowrate_long_abi_version", 1,
         structs={"aid_rate_observed_params": RateObservedParams, "aid_lowrate_gather_params": LowrateGatherParams},
         launches={"aid_rate_observed": RateObservedParams, "aid_lowrate_gather": LowrateGatherParams}),
     Abi("aid_phase_long.h", "aid_phase_long_abi_version", 1,
         structs={"aid_stft_mag_observed_params": StftMagObservedParams, "aid_pr_gather_params": PrGatherParams},
-        launches={"aid_stft_mag_observed": StftMagObservedParams, "aid_pr_gather": PrGatherParams}),
+        launches={"aid_stft_mag_observed": StftMagObservedParams, "aid_pr_gather": PrGatherParams,
+                  # (metrics.py: x = estimate, g = reference, state = region weights or null, frames = k_lo, k_hi, floor as 3 floats in HOST memory,
+                  #  out = frame distances [B, T], mode = 0)
+                  "aid_stft_logspec_dist": StftMagObservedParams}),
     Abi("aid_spec_long.h", "aid_spec_long_abi_version", 1,
         structs={"aid_stft_mask_observed_params": StftMaskObservedParams, "aid_spec_gather_params": SpecGatherParams},
         launches={"aid_stft_mask_observed": StftMaskObservedParams, "aid_spec_gather": SpecGatherParams}, macros=("AID_SPEC_ITEM_FIELDS",)),

@@ -380,6 +380,47 @@ def spectrogram_inpainting_long(sampler, files: Sequence[torch.Tensor], masks: S
         y, torch.stack([masks[i].float() for i in idx]).to(device), max_batch=max_batch, seeds=sd))
 
 
+def evaluate_long(refs: Sequence[torch.Tensor], ests: Sequence[torch.Tensor], regions: Optional[Sequence[Optional[torch.Tensor]]] = None,
+                  device="cuda", evaluate=None, **metric_args):
+    """Objective metrics (metrics.py) of every restored 1-D waveform of ``ests`` against the waveform of ``refs`` at the same place, any lengths:
+    ``regions[i]`` (same length, non-zero = evaluate here; None = everywhere) is what file i is judged on, ``metric_args`` go to
+    metrics.evaluate (sample_rate=, n_fft=, hop=, band=, floor=).  Files of equal length are stacked and go through ONE metrics.evaluate call
+    (two launches, one read-back); every other length is a call of its own.  Returns (rows, summary):
+    rows: one dict per file, in the order of the input: index, n (its length) and a float per metric (lsd, snr_db, si_sdr_db, max_abs_err,
+          n_samples, n_frames);
+    summary: per metric of metrics.METRICS the mean and the median over the files where it is finite, and how many were not
+             (n_not_finite), plus n_files.
+    ``evaluate``: the function called per length in place of metrics.evaluate (tests)."""
+    from . import metrics
+    import math
+    evaluate = metrics.evaluate if evaluate is None else evaluate
+    if len(ests) != len(refs) or (regions is not None and len(regions) != len(refs)):
+        raise ValueError(f"evaluate_long: {len(refs)} references, {len(ests)} estimates" + ("" if regions is None else f", {len(regions)} regions"))
+    for i in range(len(refs)):
+        if ests[i].numel() != refs[i].numel() or (regions is not None and regions[i] is not None and regions[i].numel() != refs[i].numel()):
+            raise ValueError(f"evaluate_long: file {i} has {refs[i].numel()} reference samples, {ests[i].numel()} estimated ones" +
+                             ("" if regions is None or regions[i] is None else f" and a region of {regions[i].numel()}"))
+    names = ("lsd", "snr_db", "si_sdr_db", "max_abs_err", "n_samples", "n_frames")
+
+    def call(r, idx, n, _):
+        e = torch.stack([ests[i].reshape(-1).float() for i in idx]).to(device)
+        w = None
+        if regions is not None and any(regions[i] is not None for i in idx):
+            w = torch.stack([torch.ones(n) if regions[i] is None else (regions[i].reshape(-1) != 0).float().cpu() for i in idx]).to(device)
+        res = evaluate(r, e, w, **metric_args)
+        return [dict({"index": i, "n": n}, **{k: float(res[k][j]) for k in names}) for j, i in enumerate(idx)]
+    # (nothing here draws random numbers: the placeholder seeds keep _long_groups from asking a process group for some)
+    rows = _long_groups("evaluate_long", refs, [0] * len(refs), device, lambda i: refs[i].numel(), call)
+    summary = {"n_files": len(rows)}
+    for k in metrics.METRICS:
+        v = sorted(row[k] for row in rows if math.isfinite(row[k]))
+        mid = len(v) // 2
+        summary[k] = {"mean": sum(v) / len(v) if v else float("nan"),
+                      "median": (v[mid] if len(v) % 2 else (v[mid - 1] + v[mid]) / 2) if v else float("nan"),
+                      "n_not_finite": len(rows) - len(v)}
+    return rows, summary
+
+
 # ---- waveform pre-/post-processing of the tester --------------------------------------------------------------------------------
 # (torchaudio's default resampling kernel: one builder and one table cache, in degrade.py, serve this module and degrade.SincResample)
 from .degrade import sinc_kernel as _sinc_kernel  # noqa: E402

@@ -143,6 +143,24 @@ int aid_fir_observed_items(const aid_fir_observed_params* p, void* stream);
  * ------------------------------------------------------------------------------------------------- */
 int aid_window_energy(const aid_bwe_gather_params* p, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * aid_eval_sums -- the weighted time-domain sums and the frame mean behind the restoration metrics (metrics.py), on the parameter
+ *   block of aid_fir_observed.  What every field means here:
+ *   x      the estimate  e [B, L], row stride x_ld >= L                                                                   (read)
+ *   y      the reference r [B, L], row stride y_ld >= L                                                                   (read)
+ *   state  the region weights [B, L], row stride state_ld >= L, or one shared row (state_ld = 0); 0 or non-zero, not fractional;
+ *          null: every sample counts                                                                                      (read)
+ *   h      the frame distances [B, K] with row stride K, an output of aid_stft_logspec_dist (K = its n_frames): a value < 0 marks
+ *          a frame that is not counted                                                                                    (read)
+ *   out    sums [B, 8]: 8 DOUBLES per item behind the float pointer (contiguous, 8-byte aligned); out_ld is ignored        (written)
+ *   mode   must be 0
+ *   sums[b] = n (the samples with a non-zero weight), sum r^2, sum e^2, sum r e, sum (r - e)^2 and max |r - e| over those samples,
+ *   the number of counted frames, the sum of their distances -- all in fp64.  One workgroup of 512 lanes per item: lane l takes the
+ *   samples (then the frames) l, l + 512, ... ascending, and the 512 partial results are combined as a fixed binary tree.  No
+ *   atomics: a second launch gives the same bits; item b does not depend on the other items.
+ * ------------------------------------------------------------------------------------------------- */
+int aid_eval_sums(const aid_fir_observed_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -87,6 +87,31 @@ typedef struct {
 } aid_pr_gather_params;
 int aid_pr_gather(const aid_pr_gather_params* p, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * aid_stft_logspec_dist -- the per-frame log-spectral distance between an estimate and a reference (metrics.py), on the parameter
+ *   block of aid_stft_mag_observed, with the framing, window and twiddle of aid_stft_mag (zero-extended signals, center=False,
+ *   T = n_frames = 1 + L / hop).  What every field means here:
+ *   x       the estimate  [B, L], row stride x_ld >= L                                                                    (read)
+ *   g       the reference [B, L], row stride g_ld >= L                                                                    (read)
+ *   state   the region weights [B, L], row stride state_ld >= L, or one shared row (state_ld = 0); 0 or non-zero, not fractional;
+ *           null: every sample counts                                                                                     (read)
+ *   window  [n_fft];  twiddle [n_fft/2] complex                                                                           (read)
+ *   frames  the band: 3 floats in HOST memory, k_lo, k_hi (whole numbers, 0 <= k_lo <= k_hi <= n_fft/2) and floor >= 0.  The
+ *           launcher reads them before it returns -- so it can refuse a band outside the spectrum -- and hands them to the
+ *           kernel with its arguments; the memory may be reused as soon as the call returns.                              (read)
+ *   out     [B, T], row stride out_ld >= T                                                                                (written)
+ *   mode    must be 0
+ *   A frame t is COUNTED when it holds a sample q < L, t*hop <= q < t*hop + n_fft, whose weight is non-zero; without weights that is
+ *   every frame with t*hop < L (the trailing frame at t = L / hop when hop divides L holds no sample).  With R, E the spectra of the
+ *   reference and the estimate over the frame,
+ *       out[b, t] = sqrt( 1/(k_hi - k_lo + 1) * sum_{k = k_lo .. k_hi} (log10(|R_k|^2 + floor) - log10(|E_k|^2 + floor))^2 )
+ *   for a counted frame and -1 for any other, which runs no FFT.  |R_k|^2 and |E_k|^2 are fp32, the logarithms and the sum over the
+ *   bins fp64: lane l of 256 adds the bins k_lo + l, k_lo + l + 256, ... ascending and the partial sums are added as a fixed binary
+ *   tree.  One workgroup per (item, frame); no atomics, a second launch gives the same bits; item b does not depend on the others.
+ *   n_fft a power of two in [16, 8192]; 0 < hop <= n_fft; B * T < 2^31.
+ * ------------------------------------------------------------------------------------------------- */
+int aid_stft_logspec_dist(const aid_stft_mag_observed_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
