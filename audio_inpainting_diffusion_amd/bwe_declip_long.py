@@ -186,17 +186,22 @@ def bwe_declip_gather(rec: torch.Tensor, out: torch.Tensor, mask: Optional[torch
     return y, k, levels[jobs[:, 0]]
 
 
-def check_bwe_declip_args(y: torch.Tensor, filt, filt_type: str, clip_value, mask, L: int, end: int, max_batch: int, seeds) -> Tuple[torch.Tensor, np.ndarray, Optional[torch.Tensor]]:
-    """The refusals of the mode, all raised before anything is launched -> (taps float32 [K] on the host, R levels float32 on the host,
-    mask [1|R, N] or None).  What can be judged without a GPU is judged first -- the filter type, the recordings, the taps and the grid as
-    bwe_long.check_bwe_args, then the levels, the mask and the windows without any observation -- max_batch, the seeds and the device of y last."""
+def bwe_declip_prepare(args, filt, filt_type: str):
+    """The filter type, judged before any recording -> bwe_long.fir_state(filt)"""
     if filt_type in bwe_long.NOT_WINDOWED:
         raise _lib.AidError(f"bandwidth extension of clipped whole recordings covers stride-1 FIR filters only ({', '.join(bwe_long.FIR_TYPES)}), "
                             f"not {filt_type!r}: " + bwe_long.NOT_WINDOWED[filt_type])
     if filt_type not in bwe_long.FIR_TYPES:
         raise NotImplementedError(f"predict_bwe_declip_long: unknown filt_type {filt_type!r}")
+    return bwe_long.fir_state(filt)
+
+
+def check_bwe_declip_args(y: torch.Tensor, clip_value, mask, state, L: int, end: int, max_batch: int, seeds) -> Tuple[torch.Tensor, np.ndarray, Optional[torch.Tensor]]:
+    """The refusals of the mode after bwe_declip_prepare's, all raised before anything is launched -> (taps float32 [K] on the host, R levels
+    float32 on the host, mask [1|R, N] or None).  What can be judged without a GPU is judged first -- the recordings, the taps and the grid as
+    bwe_long.check_bwe_args, then the levels, the mask and the windows without any observation -- max_batch, the seeds and the device of y last."""
     restore.check_rows(y, "recordings [R, N]")
-    taps = bwe_long.fir_taps(filt)
+    taps = state()
     R, N = y.shape
     bwe_long.bwe_windows(N, L, end, taps.numel())                            # (end in [1, L/2); end >= 2 (K - 1) with more than one window)
     levels = levels_of(clip_value, R)
@@ -206,12 +211,12 @@ def check_bwe_declip_args(y: torch.Tensor, filt, filt_type: str, clip_value, mas
     return taps, levels, mask
 
 
-def bwe_declip_group(y: torch.Tensor, filt, filt_type: str, clip_value, mask, L: int, end: int, max_batch: int = 8,
-                     seeds: Optional[Sequence[int]] = None) -> restore.Group:
-    """The part that checks, plans and builds: y [R, N] degraded recordings on the GPU -> restore.Group(out = a copy of y, (jobs_A, jobs_B)
-    of bwe_long.bwe_plan, the ``bwe_declip_gather`` closure).  The taps are shared by every group of a call (``bwe_declip_predict``); the
-    states and the level of a job travel in the gathered rows, so groups of other lengths, levels and masks can share the predict closure."""
-    taps, levels, mask = check_bwe_declip_args(y, filt, filt_type, clip_value, mask, L, end, max_batch, seeds)
+def bwe_declip_group(y: torch.Tensor, checked, state, L: int, end: int) -> restore.Group:
+    """The part that plans and builds: y [R, N] degraded recordings on the GPU, (taps, levels, mask) of check_bwe_declip_args ->
+    restore.Group(out = a copy of y, (jobs_A, jobs_B) of bwe_long.bwe_plan, the ``bwe_declip_gather`` closure).  The taps are shared by
+    every group of a call (``bwe_declip_predict``); the states and the level of a job travel in the gathered rows, so groups of other
+    lengths, levels and masks can share the predict closure."""
+    taps, levels, mask = checked
     K = taps.numel()
     R, N = y.shape
     out = y.clone(memory_format=torch.contiguous_format)
@@ -220,10 +225,10 @@ def bwe_declip_group(y: torch.Tensor, filt, filt_type: str, clip_value, mask, L:
     return restore.Group(out, bwe_long.bwe_plan(R, N, L, end, K), lambda table: bwe_declip_gather(y, out, dmask, dlevels, table, L, K))
 
 
-def bwe_declip_predict(sampler, filt, L: int, device):
+def bwe_declip_predict(sampler, state, L: int, device):
     """predict(win, c0, c1) of the mode: ``sampler.predict_resample`` through FIRClipObserved(taps on ``device``) over rows c0:c1 of the
     gathered (y, k, c)"""
-    dtaps = bwe_long.fir_taps(filt).to(device)
+    dtaps = state().to(device)
 
     def predict(win, c0, c1):
         yw, kw, cw = (t[c0:c1] for t in win)
@@ -231,12 +236,16 @@ def bwe_declip_predict(sampler, filt, L: int, device):
     return predict
 
 
+restore.long_task(name="bwe_declip", method="predict_bwe_declip_long", what="restored", consistency=NO_PROJECTION, guided=None, entries=("clip_value", "mask"),
+                  call_args=bwe_long.FIR_CALL_ARGS, prepare=bwe_declip_prepare, check=check_bwe_declip_args, build=bwe_declip_group,
+                  predict=bwe_declip_predict, step=restore.plain_step)
+
+
 def bwe_declip_passes(sampler, y: torch.Tensor, filt, filt_type: str, clip_value, mask, L: int, end: int, max_batch: int = 8,
                       seeds: Optional[Sequence[int]] = None) -> torch.Tensor:
     """The two passes over ``sampler.predict_resample(yw [B, L], (B, L), FIRClipObserved(taps, kw [B, L], cw [B])) -> [B, L]`` with
     B <= max_batch: y [R, N] recordings filtered with ``filt``, clipped at ``clip_value`` and dropped where ``mask`` is 0, on the GPU (rows
     contiguous, any row stride) -> restored [R, N].  Per pass: one aid_bwe_gather and one aid_gap_states launch, the sampler calls, one
-    aid_window_scatter launch per call (restore.run_passes).  Recordings and result stay on the GPU.  Seeds as restore.restore_passes."""
-    group = bwe_declip_group(y, filt, filt_type, clip_value, mask, L, end, max_batch, seeds)
-    restore.run_passes(sampler, group.out, group.passes, L - end, max_batch, seeds, group.gather, bwe_declip_predict(sampler, filt, L, y.device), L=L)
-    return group.out
+    aid_window_scatter launch per call (restore.run_task).  Recordings and result stay on the GPU.  Seeds as restore.restore_passes."""
+    return restore.run_task(restore.LONG_TASKS["bwe_declip"], sampler, bwe_declip_prepare(None, filt, filt_type), [(y, clip_value, mask)],
+                            L, end, max_batch, seeds)[0]

@@ -27,12 +27,14 @@ from predict_bwe "biquad" on purpose, which also drops the gradient where the mo
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence, Tuple
+import functools
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
+from . import bwe_long
 from . import degrade
 from . import restore
 
@@ -168,15 +170,28 @@ def iir_gather(rec: torch.Tensor, out: torch.Tensor, jobs: torch.Tensor, L: int,
     return IIRObserved(table, k).prepare(raw), k
 
 
-def check_bwe_iir_args(y: torch.Tensor, filt, filt_type: str, L: int, end: int, max_batch: int, seeds) -> IIRTable:
-    """The refusals of a bandwidth extension of whole recordings through an IIR filter, all raised before anything is launched -> the
-    coefficient table (host).  What can be judged without a GPU is judged first; the device of y last."""
+class IIRCall(NamedTuple):
+    """What the groups of a call share: the filter type and table() -> the one coefficient table of the call (host until a group or the
+    predict closure moves it).  The coefficients are judged at the first call, which is after the first group's recordings, and the table
+    is made once."""
+    filt_type: str
+    table: Callable[[], IIRTable]
+
+
+def bwe_iir_prepare(args, filt, filt_type: str) -> IIRCall:
+    """The filter type, judged before any recording -> IIRCall"""
     if filt_type in ELSEWHERE:
         raise _lib.AidError(f"predict_bwe_iir_long covers IIR filters only ({', '.join(IIR_TYPES)}), not {filt_type!r}: use {ELSEWHERE[filt_type]}")
     if filt_type not in IIR_TYPES:
         raise NotImplementedError(f"predict_bwe_iir_long: unknown filt_type {filt_type!r}")
+    return IIRCall(filt_type, functools.lru_cache(None)(lambda: IIRTable(filt, filt_type)))
+
+
+def check_bwe_iir_args(y: torch.Tensor, state: IIRCall, L: int, end: int, max_batch: int, seeds) -> IIRTable:
+    """The refusals of a bandwidth extension of whole recordings through an IIR filter after bwe_iir_prepare's, all raised before anything
+    is launched -> the coefficient table (host).  What can be judged without a GPU is judged first; the device of y last."""
     restore.check_rows(y, "recordings [R, N]")
-    table = IIRTable(filt, filt_type)
+    table = state.table()
     iir_windows(y.shape[1], L, end, table.order)                         # (end in [1, L/2); end >= 2 order with more than one window)
     restore.check_batch(y, max_batch, seeds, "bandwidth extension of whole recordings")
     return table
@@ -189,39 +204,36 @@ def check_unclamped(y: torch.Tensor) -> None:
                             "recording no longer satisfies the recursion and its windows cannot be seeded from it")
 
 
-def bwe_iir_group(y: torch.Tensor, filt, filt_type: str, L: int, end: int, max_batch: int = 8, seeds: Optional[Sequence[int]] = None,
-                  table: Optional[IIRTable] = None) -> restore.Group:
-    """The part that checks, plans and builds: y [R, N] recordings filtered with ``filt`` on the GPU -> restore.Group(out = a copy of y,
-    (jobs_A, jobs_B) of iir_plan, the iir_gather closure).  ``table``: the coefficient table every group of a call shares
-    (``bwe_iir_predict(...).table``); the states of a job travel in the gathered rows."""
-    checked = check_bwe_iir_args(y, filt, filt_type, L, end, max_batch, seeds)
-    table = (checked if table is None else table).to(y.device)
-    if filt_type == "biquad":
+def bwe_iir_group(y: torch.Tensor, table: IIRTable, state: IIRCall, L: int, end: int) -> restore.Group:
+    """The part that plans and builds: y [R, N] recordings filtered through ``table`` on the GPU -> restore.Group(out = a copy of y,
+    (jobs_A, jobs_B) of iir_plan, the iir_gather closure).  The table is the one every group of a call shares; the states of a job travel
+    in the gathered rows."""
+    table.to(y.device)
+    if state.filt_type == "biquad":
         check_unclamped(y)
     R, N = y.shape
     out = y.clone(memory_format=torch.contiguous_format)
     return restore.Group(out, iir_plan(R, N, L, end, table.order), lambda jobs: iir_gather(y, out, jobs, L, table))
 
 
-def bwe_iir_predict(sampler, filt, filt_type: str, L: int, device):
+def bwe_iir_predict(sampler, state: IIRCall, L: int, device):
     """predict(win, c0, c1) of the mode: ``sampler.predict_resample`` through IIRObserved(the table on ``device``) over rows c0:c1 of the
-    gathered (y', k); ``predict.table`` is the one coefficient table of the call"""
-    table = IIRTable(filt, filt_type).to(device)
+    gathered (y', k)"""
+    table = state.table().to(device)
 
     def predict(win, c0, c1):
         yw, kw = (t[c0:c1] for t in win)
         return sampler.predict_resample(yw, (c1 - c0, L), IIRObserved(table, kw))
-    predict.table = table
     return predict
+
+
+restore.long_task(name="bwe_iir", method="predict_bwe_iir_long", what="restored", consistency=None, guided=None, entries=(), call_args=bwe_long.FIR_CALL_ARGS,
+                  prepare=bwe_iir_prepare, check=check_bwe_iir_args, build=bwe_iir_group, predict=bwe_iir_predict, step=restore.plain_step)
 
 
 def bwe_iir_passes(sampler, y: torch.Tensor, filt, filt_type: str, L: int, end: int, max_batch: int = 8, seeds: Optional[Sequence[int]] = None) -> torch.Tensor:
     """The two passes over ``sampler.predict_resample(y'w [B, L], (B, L), IIRObserved(table, kw [B, L])) -> [B, L]`` with B <= max_batch:
     y [R, N] recordings filtered with ``filt`` on the GPU (rows contiguous, any row stride) -> restored [R, N].  Per pass: one aid_iir_gather
-    and one mode-3 aid_iir_observed launch, the sampler calls, one aid_window_scatter launch per call (restore.run_passes).  Seeds as
+    and one mode-3 aid_iir_observed launch, the sampler calls, one aid_window_scatter launch per call (restore.run_task).  Seeds as
     restore.restore_passes."""
-    check_bwe_iir_args(y, filt, filt_type, L, end, max_batch, seeds)
-    predict = bwe_iir_predict(sampler, filt, filt_type, L, y.device)
-    group = bwe_iir_group(y, filt, filt_type, L, end, max_batch, seeds, table=predict.table)
-    restore.run_passes(sampler, group.out, group.passes, L - end, max_batch, seeds, group.gather, predict, L=L)
-    return group.out
+    return restore.run_task(restore.LONG_TASKS["bwe_iir"], sampler, bwe_iir_prepare(None, filt, filt_type), [(y,)], L, end, max_batch, seeds)[0]

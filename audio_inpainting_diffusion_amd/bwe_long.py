@@ -23,6 +23,7 @@ tile is staged and one in the epilogue); ``bwe_gather`` builds the observations 
 """
 from __future__ import annotations
 
+import functools
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -133,35 +134,46 @@ def bwe_gather(rec: torch.Tensor, out: torch.Tensor, jobs: torch.Tensor, L: int,
     return y, k
 
 
-def check_bwe_args(y: torch.Tensor, filt, filt_type: str, L: int, end: int, max_batch: int, seeds) -> torch.Tensor:
-    """The refusals of a bandwidth extension of whole recordings, all raised before anything is launched -> the taps (float32 [K], host).
-    What can be judged without a GPU is judged first; the device of y last."""
+def fir_state(filt):
+    """What the groups of a call through FIR taps share: taps() -> float32 [K] on the host.  The taps are judged at the first call, which
+    is after the first group's recordings, and made once."""
+    return functools.lru_cache(None)(lambda: fir_taps(filt))
+
+
+def bwe_prepare(args, filt, filt_type: str):
+    """The filter type, judged before any recording -> fir_state(filt)"""
     if filt_type in NOT_WINDOWED:
         raise _lib.AidError(f"bandwidth extension of whole recordings covers stride-1 FIR filters only ({', '.join(FIR_TYPES)}), not {filt_type!r}: "
                             + NOT_WINDOWED[filt_type])
     if filt_type not in FIR_TYPES:
         raise NotImplementedError(f"predict_bwe_long: unknown filt_type {filt_type!r}")
+    return fir_state(filt)
+
+
+def check_bwe_args(y: torch.Tensor, state, L: int, end: int, max_batch: int, seeds) -> torch.Tensor:
+    """The refusals of a bandwidth extension of whole recordings after bwe_prepare's, all raised before anything is launched -> the taps
+    (float32 [K], host).  What can be judged without a GPU is judged first; the device of y last."""
     restore.check_rows(y, "recordings [R, N]")
-    taps = fir_taps(filt)
+    taps = state()
     bwe_windows(y.shape[1], L, end, taps.numel())                        # (end in [1, L/2); end >= 2 (K - 1) with more than one window)
     restore.check_batch(y, max_batch, seeds, "bandwidth extension of whole recordings")
     return taps
 
 
-def bwe_group(y: torch.Tensor, filt, filt_type: str, L: int, end: int, max_batch: int = 8, seeds: Optional[Sequence[int]] = None) -> restore.Group:
-    """The part of a bandwidth extension that checks, plans and builds: y [R, N] recordings filtered with ``filt`` on the GPU ->
+def bwe_group(y: torch.Tensor, taps: torch.Tensor, state, L: int, end: int) -> restore.Group:
+    """The part of a bandwidth extension that plans and builds: y [R, N] recordings filtered with ``taps`` on the GPU ->
     restore.Group(out = a copy of y, (jobs_A, jobs_B) of bwe_plan, the aid_bwe_gather closure).  The taps are shared by every group of a
     call (``bwe_predict``); the states of a job travel in the gathered rows."""
-    K = check_bwe_args(y, filt, filt_type, L, end, max_batch, seeds).numel()
+    K = taps.numel()
     R, N = y.shape
     out = y.clone(memory_format=torch.contiguous_format)
     return restore.Group(out, bwe_plan(R, N, L, end, K), lambda table: bwe_gather(y, out, table, L, K))
 
 
-def bwe_predict(sampler, filt, L: int, device):
+def bwe_predict(sampler, state, L: int, device):
     """predict(win, c0, c1) of a bandwidth extension: ``sampler.predict_resample`` through FIRObserved(taps on ``device``) over rows c0:c1 of the
     gathered (y, k)"""
-    dtaps = fir_taps(filt).to(device)
+    dtaps = state().to(device)
 
     def predict(win, c0, c1):
         yw, kw = (t[c0:c1] for t in win)
@@ -169,11 +181,14 @@ def bwe_predict(sampler, filt, L: int, device):
     return predict
 
 
+FIR_CALL_ARGS = {"filt": restore.REQUIRED, "filt_type": restore.REQUIRED}
+restore.long_task(name="bwe", method="predict_bwe_long", what="restored", consistency=None, guided=None, entries=(), call_args=FIR_CALL_ARGS,
+                  prepare=bwe_prepare, check=check_bwe_args, build=bwe_group, predict=bwe_predict, step=restore.plain_step)
+
+
 def bwe_passes(sampler, y: torch.Tensor, filt, filt_type: str, L: int, end: int, max_batch: int = 8, seeds: Optional[Sequence[int]] = None) -> torch.Tensor:
     """The two passes over ``sampler.predict_resample(yw [B, L], (B, L), FIRObserved(taps, kw [B, L])) -> [B, L]`` with B <= max_batch:
     y [R, N] recordings filtered with ``filt`` on the GPU (rows contiguous, any row stride) -> restored [R, N].  Per pass: one aid_bwe_gather
-    launch, the sampler calls, one aid_window_scatter launch per call (restore.run_passes).  Recordings and result stay on the GPU.  Seeds
+    launch, the sampler calls, one aid_window_scatter launch per call (restore.run_task).  Recordings and result stay on the GPU.  Seeds
     as restore.restore_passes."""
-    group = bwe_group(y, filt, filt_type, L, end, max_batch, seeds)
-    restore.run_passes(sampler, group.out, group.passes, L - end, max_batch, seeds, group.gather, bwe_predict(sampler, filt, L, y.device), L=L)
-    return group.out
+    return restore.run_task(restore.LONG_TASKS["bwe"], sampler, bwe_prepare(None, filt, filt_type), [(y,)], L, end, max_batch, seeds)[0]

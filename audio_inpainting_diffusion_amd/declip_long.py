@@ -107,7 +107,7 @@ def declip_gather(rec: torch.Tensor, out: torch.Tensor, clip: torch.Tensor, jobs
     return y, k, c
 
 
-def check_declip_args(y: torch.Tensor, clip, L: int, end: int, max_batch: int, seeds) -> np.ndarray:
+def check_declip_args(y: torch.Tensor, clip, state, L: int, end: int, max_batch: int, seeds) -> np.ndarray:
     """The refusals of a declipping run, all raised before anything is launched -> the R clip levels (float32, host).  What can be judged
     without a GPU is judged first; the device of y last."""
     restore.check_rows(y, "recordings [R, N]")
@@ -124,18 +124,17 @@ def declip_plan(y: torch.Tensor, levels, L: int, end: int):
     return restore.restore_plan(y.abs() < c[:, None], L, end, y.shape[0])
 
 
-def declip_group(y: torch.Tensor, clip, L: int, end: int, max_batch: int = 8, seeds: Optional[Sequence[int]] = None) -> restore.Group:
-    """The part of a declipping run that checks, plans and builds: y [R, N] clipped recordings on the GPU, clip a level or R levels ->
+def declip_group(y: torch.Tensor, levels: np.ndarray, state, L: int, end: int) -> restore.Group:
+    """The part of a declipping run that plans and builds: y [R, N] clipped recordings on the GPU, the R levels of check_declip_args ->
     restore.Group(out = a copy of y, (jobs_A, jobs_B) of declip_plan, the aid_declip_gather closure).  The clip level of a job travels in
     the gathered rows, so groups of other lengths and levels can share ``declip_predict``."""
-    levels = check_declip_args(y, clip, L, end, max_batch, seeds)
     jobs_A, jobs_B, _ = declip_plan(y, levels, L, end)
     out = y.clone(memory_format=torch.contiguous_format)
     dclip = torch.from_numpy(levels).to(y.device) if jobs_A or jobs_B else None
     return restore.Group(out, (jobs_A, jobs_B), lambda table: declip_gather(y, out, dclip, table, L))
 
 
-def declip_predict(sampler, L: int):
+def declip_predict(sampler, state, L: int, device):
     """predict(win, c0, c1) of a declipping run: ``sampler.predict_resample`` through ClipObserved over rows c0:c1 of the gathered (y, k, c)"""
     def predict(win, c0, c1):
         yw, kw, cw = (t[c0:c1] for t in win)
@@ -143,12 +142,13 @@ def declip_predict(sampler, L: int):
     return predict
 
 
+restore.long_task(name="declipping", method="predict_declipping_long", what="declipped", consistency=None, guided=None, entries=("clip_value",), call_args={},
+                  prepare=lambda args: None, check=check_declip_args, build=declip_group, predict=declip_predict, step=restore.plain_step)
+
+
 def declip_passes(sampler, y: torch.Tensor, clip, L: int, end: int, max_batch: int = 8, seeds: Optional[Sequence[int]] = None) -> torch.Tensor:
     """The two passes over ``sampler.predict_resample(yw [B, L], (B, L), ClipObserved(kw [B, L], cw [B])) -> [B, L]`` with B <= max_batch:
     y [R, N] clipped recordings on the GPU (rows contiguous, any row stride), clip a level or R levels -> declipped [R, N].  Per pass: one
-    aid_declip_gather launch, the sampler calls, one aid_window_scatter launch per call (restore.run_passes).  Recordings and result stay on
+    aid_declip_gather launch, the sampler calls, one aid_window_scatter launch per call (restore.run_task).  Recordings and result stay on
     the GPU; the plan is made on the host from |y| < c before pass A.  Seeds as restore.restore_passes."""
-    group = declip_group(y, clip, L, end, max_batch, seeds)
-    if not restore.no_jobs(*group.passes):
-        restore.run_passes(sampler, group.out, group.passes, L - end, max_batch, seeds, group.gather, declip_predict(sampler, L), L=L)
-    return group.out
+    return restore.run_task(restore.LONG_TASKS["declipping"], sampler, None, [(y, clip)], L, end, max_batch, seeds)[0]

@@ -14,7 +14,8 @@ No device code here; everything numerical happens in the sampler / network.
 """
 from __future__ import annotations
 
-from typing import Optional, List, Sequence, Tuple
+import types
+from typing import Callable, NamedTuple, Optional, List, Sequence, Tuple
 
 import torch
 
@@ -141,13 +142,30 @@ def generate_long(sampler, n_items: int, n_windows: int, seeds: Optional[Sequenc
     return D.gather_outputs(local, n_items)
 
 
-def _long_groups(who: str, files, seeds, device, key, call, flat: bool = True, pooled=None) -> List[torch.Tensor]:
-    """The loop the *_long functions below share: the files with equal ``key(i)`` are stacked on ``device`` (``flat``: each as a 1-D waveform)
-    and go through ONE ``call(y, idx, key, seeds of idx)`` -> [len(idx), ...]; its rows come back in the order of ``files``.
-    With ``pooled`` (pool=True) all stacks go through ONE ``pooled([(y, idx, key), ...], the seeds in that order)`` -> [one [len(idx), ...]
-    per stack] instead: Sampler.predict_long_pooled, where the windows of all lengths share the two batched passes.
-    Under an active process group ``seeds`` = None becomes dist.item_seeds(0, 0, len(files)), as in generate_long: the ranks share the windows
-    of every call (restore.run_passes), and a file's result must not depend on the world size."""
+class _LongMode(NamedTuple):
+    """One whole-recording mode as ``_long_groups`` drives it, plainly and pooled."""
+    method: str                                      # the sampler method, e.g. "predict_bwe_long"
+    task: Optional[str]                              # the task of Sampler.predict_long_pooled; None: the mode does not pool
+    key: Callable                                    # key(i): the files with equal keys are stacked into one call
+    group_of: Callable = lambda y, idx, key: ()      # group_of(y, idx, key) -> the entries of the stack after y, in the order of the method's parameters
+    shared: dict = {}                                # the arguments all files share, by name, in the order of the method's parameters after y
+
+
+def _long_groups(who: str, sampler, files, seeds, max_batch, device, mode: _LongMode, pool: bool = False, flat: bool = True, after=None) -> List[torch.Tensor]:
+    """What the *_long functions below are: every file of ``files`` (any lengths) goes through ``mode`` and the full-length results come
+    back on ``device``, in the order of ``files``.
+    GROUPING.  The files with equal ``mode.key(i)`` (the length, mostly) are stacked on ``device`` (``flat``: each as a 1-D waveform) and go
+    through ONE call of the sampler method, ``method(y, *shared, *entries, max_batch, seeds)``, so their windows share the two batched passes;
+    every other key is a call of its own (``after(idx)`` follows each).
+    SEEDS.  One RNG seed per file: file i's result then depends on seeds[i] alone, not on the grouping.
+    PROCESS GROUPS.  Under an active process group (dist.init_distributed; weights made equal with dist.broadcast_parameters first) every
+    rank passes the same files and gets the full results: the windows of each pass are shared out over the ranks and exchanged once per
+    pass (restore.run_pooled_passes), ``max_batch`` is per rank, and ``seeds`` = None means dist.item_seeds(0, 0, len(files)), as in
+    generate_long: a file's result must not depend on the world size.
+    POOL.  ``pool`` = True: all stacks go through ONE Sampler.predict_long_pooled(mode.task, [(y, *entries), ...], the seeds in that
+    order, **shared), where the windows of ALL files, whatever their lengths, share the two batched passes: a chunk of ``max_batch``
+    windows may span files, so a folder of short files of different lengths runs full batches; with seeds the results are those of
+    ``pool`` = False."""
     from . import dist as D
     if seeds is not None and len(seeds) != len(files):
         raise ValueError(f"{who}: {len(seeds)} seeds for {len(files)} files")
@@ -155,36 +173,39 @@ def _long_groups(who: str, files, seeds, device, key, call, flat: bool = True, p
         seeds = D.item_seeds(0, 0, len(files))
     groups = {}
     for i in range(len(files)):
-        groups.setdefault(key(i), []).append(i)
+        groups.setdefault(mode.key(i), []).append(i)
+    seeds_of = lambda idx: None if seeds is None else [int(seeds[i]) for i in idx]                                        # noqa: E731
+    stacks = ((torch.stack([(files[i].reshape(-1) if flat else files[i]).float() for i in idx]).to(device), idx, k) for k, idx in groups.items())
+    if pool:
+        every = sampler.predict_long_pooled(mode.task, [(y, *mode.group_of(y, idx, k)) for y, idx, k in stacks], max_batch=max_batch,
+                                            seeds=seeds_of([i for idx in groups.values() for i in idx]), **mode.shared)
+    else:
+        every = []
+        for y, idx, k in stacks:
+            every.append(getattr(sampler, mode.method)(y, *mode.shared.values(), *mode.group_of(y, idx, k), max_batch=max_batch, seeds=seeds_of(idx)))
+            if after is not None:
+                after(idx)
     out: List[Optional[torch.Tensor]] = [None] * len(files)
-    stack = lambda idx: torch.stack([(files[i].reshape(-1) if flat else files[i]).float() for i in idx]).to(device)      # noqa: E731
-    if pooled is not None:
-        every = pooled([(stack(idx), idx, k) for k, idx in groups.items()],
-                       None if seeds is None else [int(seeds[i]) for idx in groups.values() for i in idx])
-        for res, idx in zip(every, groups.values()):
-            for j, i in enumerate(idx):
-                out[i] = res[j]
-        return out
-    for k, idx in groups.items():
-        y = stack(idx)
-        res = call(y, idx, k, None if seeds is None else [int(seeds[i]) for i in idx])
+    for res, idx in zip(every, groups.values()):
         for j, i in enumerate(idx):
             out[i] = res[j]
     return out
 
 
+def _levels_per_file(who: str, clip_values, n_files: int) -> List[float]:
+    """one float for all files, or one per file -> one per file"""
+    levels = [float(v) for v in (clip_values.reshape(-1).tolist() if torch.is_tensor(clip_values) else
+                                 (list(clip_values) if hasattr(clip_values, "__len__") else [clip_values]))]
+    if len(levels) not in (1, n_files):
+        raise ValueError(f"{who}: {len(levels)} clip values for {n_files} files")
+    return levels * n_files if len(levels) == 1 else levels
+
+
 def restore_long(sampler, files: Sequence[torch.Tensor], masks: Sequence[torch.Tensor], seeds: Optional[Sequence[int]] = None, max_batch: int = 8,
                  device="cuda", pool: bool = False) -> List[torch.Tensor]:
     """Restore every 1-D waveform of ``files`` (any lengths) where its mask (same length; 1 = observed, 0 = gap, gaps anywhere) is 0 and return the
-    full-length results on ``device``, in the order of ``files``.  Files of equal length go through ONE Sampler.predict_inpainting_long call, so
-    their windows share the two batched passes; every other length is a call of its own.  ``seeds``: one RNG seed per file (file i's result then
-    depends on seeds[i] alone, not on the grouping).
-    Under an active process group (dist.init_distributed; weights made equal with dist.broadcast_parameters first) every rank passes the same
-    files and gets the full results: the windows of each pass are shared out over the ranks and exchanged once per pass, ``max_batch`` is
-    per rank, and ``seeds`` = None means dist.item_seeds(0, 0, len(files)).
-    ``pool`` = True: the windows of ALL files, whatever their lengths, share the two batched passes (Sampler.predict_long_pooled): a chunk of
-    ``max_batch`` windows may span files, so a folder of short files of different lengths runs full batches; with seeds the results are
-    those of ``pool`` = False."""
+    full-length results on ``device``, in the order of ``files``.  Files of equal length go through ONE Sampler.predict_inpainting_long call.
+    Grouping, seeds, process groups and ``pool`` as ``_long_groups`` states (the pooled task is "inpainting")."""
     if len(masks) != len(files):
         raise ValueError(f"restore_long: {len(masks)} masks for {len(files)} files")
 
@@ -192,50 +213,27 @@ def restore_long(sampler, files: Sequence[torch.Tensor], masks: Sequence[torch.T
         if files[i].numel() != masks[i].numel():
             raise ValueError(f"restore_long: file {i} has {files[i].numel()} samples, its mask {masks[i].numel()}")
         return files[i].numel()
-    mask_of = lambda idx: torch.stack([masks[i].reshape(-1).float() for i in idx])                                     # noqa: E731
-    return _long_groups("restore_long", files, seeds, device, key, lambda y, idx, _, sd: sampler.predict_inpainting_long(
-        y, mask_of(idx), max_batch=max_batch, seeds=sd),
-        pooled=None if not pool else lambda gs, sd: sampler.predict_long_pooled("inpainting", [(y, mask_of(idx)) for y, idx, _ in gs], max_batch=max_batch, seeds=sd))
+    mode = _LongMode("predict_inpainting_long", "inpainting", key, lambda y, idx, k: (torch.stack([masks[i].reshape(-1).float() for i in idx]),))
+    return _long_groups("restore_long", sampler, files, seeds, max_batch, device, mode, pool)
 
 
 def declip_long(sampler, files: Sequence[torch.Tensor], clip_values, seeds: Optional[Sequence[int]] = None, max_batch: int = 8,
                 device="cuda", pool: bool = False) -> List[torch.Tensor]:
     """Declip every 1-D waveform of ``files`` (any lengths), clipped at +-clip_values (one float for all files, or one per file), and return the
-    full-length results on ``device``, in the order of ``files``.  Files of equal length go through ONE Sampler.predict_declipping_long call, so
-    their windows share the two batched passes; every other length is a call of its own.  ``seeds``: one RNG seed per file (file i's result then
-    depends on seeds[i] alone, not on the grouping).
-    Under an active process group (dist.init_distributed; weights made equal with dist.broadcast_parameters first) every rank passes the same
-    files and gets the full results: the windows of each pass are shared out over the ranks and exchanged once per pass, ``max_batch`` is
-    per rank, and ``seeds`` = None means dist.item_seeds(0, 0, len(files)).
-    ``pool`` = True: the windows of ALL files, whatever their lengths, share the two batched passes (Sampler.predict_long_pooled): a chunk of
-    ``max_batch`` windows may span files, so a folder of short files of different lengths runs full batches; with seeds the results are
-    those of ``pool`` = False."""
-    levels = [float(v) for v in (clip_values.reshape(-1).tolist() if torch.is_tensor(clip_values) else
-                                 (list(clip_values) if hasattr(clip_values, "__len__") else [clip_values]))]
-    if len(levels) not in (1, len(files)):
-        raise ValueError(f"declip_long: {len(levels)} clip values for {len(files)} files")
-    if len(levels) == 1:
-        levels = levels * len(files)
-    return _long_groups("declip_long", files, seeds, device, lambda i: files[i].numel(), lambda y, idx, _, sd: sampler.predict_declipping_long(
-        y, [levels[i] for i in idx], max_batch=max_batch, seeds=sd),
-        pooled=None if not pool else lambda gs, sd: sampler.predict_long_pooled("declipping", [(y, [levels[i] for i in idx]) for y, idx, _ in gs], max_batch=max_batch, seeds=sd))
+    full-length results on ``device``, in the order of ``files``.  Files of equal length go through ONE Sampler.predict_declipping_long call.
+    Grouping, seeds, process groups and ``pool`` as ``_long_groups`` states (the pooled task is "declipping")."""
+    levels = _levels_per_file("declip_long", clip_values, len(files))
+    mode = _LongMode("predict_declipping_long", "declipping", lambda i: files[i].numel(), lambda y, idx, k: ([levels[i] for i in idx],))
+    return _long_groups("declip_long", sampler, files, seeds, max_batch, device, mode, pool)
 
 
 def bwe_long(sampler, files: Sequence[torch.Tensor], filt, filt_type: str = "firwin", seeds: Optional[Sequence[int]] = None, max_batch: int = 8,
              device="cuda", pool: bool = False) -> List[torch.Tensor]:
     """Bandwidth-extend every 1-D waveform of ``files`` (any lengths), each low-passed as a whole with the FIR taps ``filt`` (one filter for all
     files), and return the full-length results on ``device``, in the order of ``files``.  Files of equal length go through ONE
-    Sampler.predict_bwe_long call, so their windows share the two batched passes; every other length is a call of its own.  ``seeds``: one RNG
-    seed per file (file i's result then depends on seeds[i] alone, not on the grouping).
-    Under an active process group (dist.init_distributed; weights made equal with dist.broadcast_parameters first) every rank passes the same
-    files and gets the full results: the windows of each pass are shared out over the ranks and exchanged once per pass, ``max_batch`` is
-    per rank, and ``seeds`` = None means dist.item_seeds(0, 0, len(files)).
-    ``pool`` = True: the windows of ALL files, whatever their lengths, share the two batched passes (Sampler.predict_long_pooled): a chunk of
-    ``max_batch`` windows may span files, so a folder of short files of different lengths runs full batches; with seeds the results are
-    those of ``pool`` = False."""
-    return _long_groups("bwe_long", files, seeds, device, lambda i: files[i].numel(), lambda y, idx, _, sd: sampler.predict_bwe_long(
-        y, filt, filt_type, max_batch=max_batch, seeds=sd),
-        pooled=None if not pool else lambda gs, sd: sampler.predict_long_pooled("bwe", [y for y, _, _ in gs], max_batch=max_batch, seeds=sd, filt=filt, filt_type=filt_type))
+    Sampler.predict_bwe_long call.  Grouping, seeds, process groups and ``pool`` as ``_long_groups`` states (the pooled task is "bwe")."""
+    mode = _LongMode("predict_bwe_long", "bwe", lambda i: files[i].numel(), shared=dict(filt=filt, filt_type=filt_type))
+    return _long_groups("bwe_long", sampler, files, seeds, max_batch, device, mode, pool)
 
 
 def blind_bwe_long(sampler, files: Sequence[torch.Tensor], probes: int = 4, seeds: Optional[Sequence[int]] = None, max_batch: int = 8,
@@ -244,17 +242,15 @@ def blind_bwe_long(sampler, files: Sequence[torch.Tensor], probes: int = 4, seed
     the full-length results on ``device``, in the order of ``files``.  Files of equal length go through ONE Sampler.predict_blind_bwe_long
     call: their probe windows share the chunks of stage 1 and their windows the two batched passes of stage 2; every other length is a call
     of its own -- there is no ``pool`` argument.  Afterwards ``sampler.blind_fit`` [len(files), 2], ``sampler.blind_taps`` [len(files), K] and
-    ``sampler.blind_probes`` hold every file's filter, in the order of ``files``.  ``seeds``: one RNG seed per file (file i's filter and result
-    then depend on seeds[i] alone, not on the grouping).  Under an active process group every rank passes the same files and gets the full
-    results, and ``seeds`` = None means dist.item_seeds(0, 0, len(files)), as bwe_long."""
+    ``sampler.blind_probes`` hold every file's filter, in the order of ``files``.  Grouping, seeds (file i's filter, too, depends on seeds[i]
+    alone) and process groups as ``_long_groups`` states."""
     held = {}
 
-    def call(y, idx, _, sd):
-        res = sampler.predict_blind_bwe_long(y, probes=probes, max_batch=max_batch, seeds=sd)
+    def after(idx):
         for j, i in enumerate(idx):
             held[i] = (sampler.blind_fit[j], sampler.blind_taps[j], sampler.blind_probes[j])
-        return res
-    out = _long_groups("blind_bwe_long", files, seeds, device, lambda i: files[i].numel(), call)
+    mode = _LongMode("predict_blind_bwe_long", None, lambda i: files[i].numel(), shared=dict(probes=probes))
+    out = _long_groups("blind_bwe_long", sampler, files, seeds, max_batch, device, mode, after=after)
     if held:
         sampler.blind_fit = torch.stack([held[i][0] for i in range(len(files))])
         sampler.blind_taps = torch.stack([held[i][1] for i in range(len(files))])
@@ -266,11 +262,10 @@ def bwe_iir_long(sampler, files: Sequence[torch.Tensor], filt, filt_type: str = 
                  device="cuda", pool: bool = False) -> List[torch.Tensor]:
     """Bandwidth-extend every 1-D waveform of ``files`` (any lengths), each low-passed as a whole with the IIR filter ``filt`` ("cheby1": (b, a);
     "biquad": (b0, b1, b2, a0, a1, a2); one filter for all files), and return the full-length results on ``device``, in the order of ``files``.
-    Files of equal length go through ONE Sampler.predict_bwe_iir_long call, so their windows share the two batched passes; every other length
-    is a call of its own.  Seeds, process groups and ``pool`` as bwe_long (the pooled task is "bwe_iir")."""
-    return _long_groups("bwe_iir_long", files, seeds, device, lambda i: files[i].numel(), lambda y, idx, _, sd: sampler.predict_bwe_iir_long(
-        y, filt, filt_type, max_batch=max_batch, seeds=sd),
-        pooled=None if not pool else lambda gs, sd: sampler.predict_long_pooled("bwe_iir", [y for y, _, _ in gs], max_batch=max_batch, seeds=sd, filt=filt, filt_type=filt_type))
+    Files of equal length go through ONE Sampler.predict_bwe_iir_long call.  Grouping, seeds, process groups and ``pool`` as ``_long_groups``
+    states (the pooled task is "bwe_iir")."""
+    mode = _LongMode("predict_bwe_iir_long", "bwe_iir", lambda i: files[i].numel(), shared=dict(filt=filt, filt_type=filt_type))
+    return _long_groups("bwe_iir_long", sampler, files, seeds, max_batch, device, mode, pool)
 
 
 def bwe_declip_long(sampler, files: Sequence[torch.Tensor], filt, filt_type: str = "firwin", clip_values=None, masks: Optional[Sequence[Optional[torch.Tensor]]] = None,
@@ -279,17 +274,9 @@ def bwe_declip_long(sampler, files: Sequence[torch.Tensor], filt, filt_type: str
     all files), THEN clipped at +-clip_values (None: not clipped; one float for all files, or one per file) and THEN dropped where its mask
     (``masks``: None, or per file None or a mask of the file's length; 1 = kept, 0 = dropped) is 0 -- y = mask * clamp(taps * x, -c, c), in this
     order -- and return the full-length results on ``device``, in the order of ``files``.  Files of equal length go through ONE
-    Sampler.predict_bwe_declip_long call, so their windows share the two batched passes (a file without a mask gets all ones beside one that
-    has one); every other length is a call of its own.  Seeds, process groups and ``pool`` as bwe_long (the pooled task is "bwe_declip")."""
-    if clip_values is None:
-        levels = None
-    else:
-        levels = [float(v) for v in (clip_values.reshape(-1).tolist() if torch.is_tensor(clip_values) else
-                                     (list(clip_values) if hasattr(clip_values, "__len__") else [clip_values]))]
-        if len(levels) not in (1, len(files)):
-            raise ValueError(f"bwe_declip_long: {len(levels)} clip values for {len(files)} files")
-        if len(levels) == 1:
-            levels = levels * len(files)
+    Sampler.predict_bwe_declip_long call (a file without a mask gets all ones beside one that has one).  Grouping, seeds, process groups and
+    ``pool`` as ``_long_groups`` states (the pooled task is "bwe_declip")."""
+    levels = None if clip_values is None else _levels_per_file("bwe_declip_long", clip_values, len(files))
     if masks is not None and len(masks) != len(files):
         raise ValueError(f"bwe_declip_long: {len(masks)} masks for {len(files)} files")
 
@@ -302,48 +289,30 @@ def bwe_declip_long(sampler, files: Sequence[torch.Tensor], filt, filt_type: str
         if masks is None or all(masks[i] is None for i in idx):
             return None
         return torch.stack([torch.ones(files[i].numel()) if masks[i] is None else masks[i].reshape(-1).float().cpu() for i in idx])
-    level_of = lambda idx: None if levels is None else [levels[i] for i in idx]                                          # noqa: E731
-    return _long_groups("bwe_declip_long", files, seeds, device, key, lambda y, idx, _, sd: sampler.predict_bwe_declip_long(
-        y, filt, filt_type, clip_value=level_of(idx), mask=mask_of(idx), max_batch=max_batch, seeds=sd),
-        pooled=None if not pool else lambda gs, sd: sampler.predict_long_pooled("bwe_declip", [(y, level_of(idx), mask_of(idx)) for y, idx, _ in gs],
-                                                                                max_batch=max_batch, seeds=sd, filt=filt, filt_type=filt_type))
+    mode = _LongMode("predict_bwe_declip_long", "bwe_declip", key, lambda y, idx, k: (None if levels is None else [levels[i] for i in idx], mask_of(idx)),
+                     dict(filt=filt, filt_type=filt_type))
+    return _long_groups("bwe_declip_long", sampler, files, seeds, max_batch, device, mode, pool)
 
 
 def bwe_lowrate_long(sampler, files: Sequence[torch.Tensor], factor, filt_type: str = "resample", lengths: Optional[Sequence[Optional[int]]] = None,
                      seeds: Optional[Sequence[int]] = None, max_batch: int = 8, device="cuda", pool: bool = False) -> List[torch.Tensor]:
     """Bandwidth-extend every 1-D low-sample-rate waveform of ``files`` (any lengths; one ``factor`` and ``filt_type`` for all files) and return the
     high-rate results on ``device``, in the order of ``files``.  ``lengths``: the number of high-rate samples per file (None, for all files or for
-    one: the largest consistent with the file).  Files of equal (low-rate length, length) go through ONE Sampler.predict_bwe_lowrate_long call, so
-    their windows share the two batched passes; every other pair is a call of its own.  ``seeds``: one RNG seed per file (file i's result then
-    depends on seeds[i] alone, not on the grouping).
-    Under an active process group (dist.init_distributed; weights made equal with dist.broadcast_parameters first) every rank passes the same
-    files and gets the full results: the windows of each pass are shared out over the ranks and exchanged once per pass, ``max_batch`` is
-    per rank, and ``seeds`` = None means dist.item_seeds(0, 0, len(files)).
-    ``pool`` = True: the windows of ALL files, whatever their lengths, share the two batched passes (Sampler.predict_long_pooled): a chunk of
-    ``max_batch`` windows may span files, so a folder of short files of different lengths runs full batches; with seeds the results are
-    those of ``pool`` = False."""
+    one: the largest consistent with the file).  Files of equal (low-rate length, length) go through ONE Sampler.predict_bwe_lowrate_long call.
+    Grouping, seeds, process groups and ``pool`` as ``_long_groups`` states (the pooled task is "bwe_lowrate")."""
     if lengths is not None and len(lengths) != len(files):
         raise ValueError(f"bwe_lowrate_long: {len(lengths)} lengths for {len(files)} files")
-    return _long_groups("bwe_lowrate_long", files, seeds, device,
-                        lambda i: (files[i].numel(), None if lengths is None or lengths[i] is None else int(lengths[i])),
-                        lambda y, idx, k, sd: sampler.predict_bwe_lowrate_long(y, factor, filt_type, length=k[1], max_batch=max_batch, seeds=sd),
-                        pooled=None if not pool else lambda gs, sd: sampler.predict_long_pooled("bwe_lowrate", [(y, k[1]) for y, _, k in gs], max_batch=max_batch, seeds=sd,
-                                                                                        factor=factor, filt_type=filt_type))
+    mode = _LongMode("predict_bwe_lowrate_long", "bwe_lowrate", lambda i: (files[i].numel(), None if lengths is None or lengths[i] is None else int(lengths[i])),
+                     lambda y, idx, k: (k[1],), dict(factor=factor, filt_type=filt_type))
+    return _long_groups("bwe_lowrate_long", sampler, files, seeds, max_batch, device, mode, pool)
 
 
 def pr_long(sampler, spectrograms: Sequence[torch.Tensor], lengths: Optional[Sequence[Optional[int]]] = None, seeds: Optional[Sequence[int]] = None,
             max_batch: int = 8, device="cuda", pool: bool = False) -> List[torch.Tensor]:
     """Retrieve the phase of every 2-D magnitude spectrogram [F, T_rec] of ``spectrograms`` (any numbers of frames) and return the waveforms on
     ``device``, in the order of ``spectrograms``.  ``lengths``: the number of samples per file (None, for all files or for one: the largest
-    consistent with the file's frames).  Files of equal (T_rec, length) go through ONE Sampler.predict_pr_long call, so their windows share the
-    two batched passes; every other pair is a call of its own.  ``seeds``: one RNG seed per file (file i's result then depends on seeds[i] alone,
-    not on the grouping).
-    Under an active process group (dist.init_distributed; weights made equal with dist.broadcast_parameters first) every rank passes the same
-    files and gets the full results: the windows of each pass are shared out over the ranks and exchanged once per pass, ``max_batch`` is
-    per rank, and ``seeds`` = None means dist.item_seeds(0, 0, len(files)).
-    ``pool`` = True: the windows of ALL files, whatever their lengths, share the two batched passes (Sampler.predict_long_pooled): a chunk of
-    ``max_batch`` windows may span files, so a folder of short files of different lengths runs full batches; with seeds the results are
-    those of ``pool`` = False."""
+    consistent with the file's frames).  Files of equal (T_rec, length) go through ONE Sampler.predict_pr_long call.  Grouping, seeds,
+    process groups and ``pool`` as ``_long_groups`` states (the pooled task is "pr")."""
     if lengths is not None and len(lengths) != len(spectrograms):
         raise ValueError(f"pr_long: {len(lengths)} lengths for {len(spectrograms)} files")
 
@@ -351,20 +320,15 @@ def pr_long(sampler, spectrograms: Sequence[torch.Tensor], lengths: Optional[Seq
         if spectrograms[i].dim() != 2:
             raise ValueError(f"pr_long: file {i} must be a magnitude spectrogram [F, T_rec], got {tuple(spectrograms[i].shape)}")
         return tuple(spectrograms[i].shape), None if lengths is None or lengths[i] is None else int(lengths[i])
-    return _long_groups("pr_long", spectrograms, seeds, device, key,
-                        lambda y, idx, k, sd: sampler.predict_pr_long(y, length=k[1], max_batch=max_batch, seeds=sd), flat=False,
-                        pooled=None if not pool else lambda gs, sd: sampler.predict_long_pooled("pr", [(y, k[1]) for y, _, k in gs], max_batch=max_batch, seeds=sd))
+    mode = _LongMode("predict_pr_long", "pr", key, lambda y, idx, k: (k[1],))
+    return _long_groups("pr_long", sampler, spectrograms, seeds, max_batch, device, mode, pool, flat=False)
 
 
 def spectrogram_inpainting_long(sampler, files: Sequence[torch.Tensor], masks: Sequence[torch.Tensor], seeds: Optional[Sequence[int]] = None,
                                 max_batch: int = 8, device="cuda", pool: bool = False) -> List[torch.Tensor]:
     """Restore every waveform of ``files`` (any lengths; each masked as a whole in the STFT domain) under its mask [F, T_rec] of ``masks``
     (masks.spectral_mask(audio_len=len(file), ...)) and return the waveforms on ``device``, in the order of ``files``.  Files of equal length
-    go through ONE Sampler.predict_spectrogram_inpainting_long call, so their windows share the two batched passes; every other length is a
-    call of its own.  ``seeds``: one RNG seed per file (file i's result then depends on seeds[i] alone, not on the grouping).
-    Under an active process group (dist.init_distributed; weights made equal with dist.broadcast_parameters first) every rank passes the same
-    files and gets the full results: the windows of each pass are shared out over the ranks and exchanged once per pass, ``max_batch`` is
-    per rank, and ``seeds`` = None means dist.item_seeds(0, 0, len(files)).
+    go through ONE Sampler.predict_spectrogram_inpainting_long call.  Grouping, seeds and process groups as ``_long_groups`` states.
     ``pool`` = True is refused: aid_stft_mask_observed reads one recording-shaped mask in place, so the windows of files with different
     T_rec cannot share a launch (Sampler.predict_long_pooled says the same)."""
     if pool:
@@ -376,8 +340,8 @@ def spectrogram_inpainting_long(sampler, files: Sequence[torch.Tensor], masks: S
         if masks[i].dim() != 2:
             raise ValueError(f"spectrogram_inpainting_long: mask {i} must be [F, T_rec], got {tuple(masks[i].shape)}")
         return files[i].numel(), tuple(masks[i].shape)
-    return _long_groups("spectrogram_inpainting_long", files, seeds, device, key, lambda y, idx, _, sd: sampler.predict_spectrogram_inpainting_long(
-        y, torch.stack([masks[i].float() for i in idx]).to(device), max_batch=max_batch, seeds=sd))
+    mode = _LongMode("predict_spectrogram_inpainting_long", None, key, lambda y, idx, k: (torch.stack([masks[i].float() for i in idx]).to(device),))
+    return _long_groups("spectrogram_inpainting_long", sampler, files, seeds, max_batch, device, mode)
 
 
 def evaluate_long(refs: Sequence[torch.Tensor], ests: Sequence[torch.Tensor], regions: Optional[Sequence[Optional[torch.Tensor]]] = None,
@@ -402,7 +366,7 @@ def evaluate_long(refs: Sequence[torch.Tensor], ests: Sequence[torch.Tensor], re
                              ("" if regions is None or regions[i] is None else f" and a region of {regions[i].numel()}"))
     names = ("lsd", "snr_db", "si_sdr_db", "max_abs_err", "n_samples", "n_frames")
 
-    def call(r, idx, n, _):
+    def call(r, idx, n, max_batch, seeds):
         e = torch.stack([ests[i].reshape(-1).float() for i in idx]).to(device)
         w = None
         if regions is not None and any(regions[i] is not None for i in idx):
@@ -410,7 +374,8 @@ def evaluate_long(refs: Sequence[torch.Tensor], ests: Sequence[torch.Tensor], re
         res = evaluate(r, e, w, **metric_args)
         return [dict({"index": i, "n": n}, **{k: float(res[k][j]) for k in names}) for j, i in enumerate(idx)]
     # (nothing here draws random numbers: the placeholder seeds keep _long_groups from asking a process group for some)
-    rows = _long_groups("evaluate_long", refs, [0] * len(refs), device, lambda i: refs[i].numel(), call)
+    mode = _LongMode("evaluate", None, lambda i: refs[i].numel(), lambda r, idx, n: (idx, n))
+    rows = _long_groups("evaluate_long", types.SimpleNamespace(evaluate=call), refs, [0] * len(refs), None, device, mode)
     summary = {"n_files": len(rows)}
     for k in metrics.METRICS:
         v = sorted(row[k] for row in rows if math.isfinite(row[k]))

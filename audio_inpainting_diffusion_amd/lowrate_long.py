@@ -205,10 +205,9 @@ def lowrate_gather(rec: torch.Tensor, out: torch.Tensor, jobs: torch.Tensor, L: 
     return y, k
 
 
-def check_lowrate_args(y: torch.Tensor, factor, filt_type: str, length, L: int, end: int, max_batch: int, seeds):
-    """The refusals of a bandwidth extension of whole low-rate recordings, all raised before anything is launched -> (rate, N).
-    What can be judged without a GPU is judged first; the device of y last."""
-    rate = rate_of(factor, filt_type)
+def check_lowrate_args(y: torch.Tensor, length, rate: Rate, L: int, end: int, max_batch: int, seeds):
+    """The refusals of a bandwidth extension of whole low-rate recordings after rate_of's, all raised before anything is launched ->
+    (rate, N).  What can be judged without a GPU is judged first; the device of y last."""
     restore.check_rows(y, "low-rate recordings [R, M]", nonempty=True)
     N = check_length(y.shape[1], length, rate)
     lowrate_windows(N, L, end, rate)                                       # (end' in [1, L/2); end' >= 2 (K - 1) with more than one window)
@@ -216,26 +215,24 @@ def check_lowrate_args(y: torch.Tensor, factor, filt_type: str, length, L: int, 
     return rate, N
 
 
-def lowrate_group(y: torch.Tensor, factor, filt_type: str, L: int, end: int, length=None, max_batch: int = 8,
-                  seeds: Optional[Sequence[int]] = None) -> restore.Group:
-    """The part of a bandwidth extension of low-rate recordings that checks, plans and builds: y [R, M] low-rate recordings on the GPU ->
-    restore.Group(out = zeros [R, N], (jobs_A, jobs_B) of lowrate_plan, the aid_lowrate_gather closure).  The ratio is shared by every group
-    of a call (``lowrate_step``, ``lowrate_predict``); the states of a job travel in the gathered rows."""
-    rate, N = check_lowrate_args(y, factor, filt_type, length, L, end, max_batch, seeds)
-    R = y.shape[0]
+def lowrate_group(y: torch.Tensor, checked, rate: Rate, L: int, end: int) -> restore.Group:
+    """The part of a bandwidth extension of low-rate recordings that plans and builds: y [R, M] low-rate recordings on the GPU, (rate, N) of
+    check_lowrate_args -> restore.Group(out = zeros [R, N], (jobs_A, jobs_B) of lowrate_plan, the aid_lowrate_gather closure).  The ratio is
+    shared by every group of a call (``lowrate_step``, ``lowrate_predict``); the states of a job travel in the gathered rows."""
+    R, N = y.shape[0], checked[1]
     out = torch.zeros((R, N), dtype=torch.float32, device=y.device)          # (every sample is owned; pass B's heads and tails lie in ranges pass A owns)
     return restore.Group(out, lowrate_plan(R, N, L, end, rate), lambda table: lowrate_gather(y, out, table, L, rate))
 
 
-def lowrate_step(factor, filt_type: str, L: int, end: int) -> int:
+def lowrate_step(rate: Rate, L: int, end: int) -> int:
     """the aligned step L - end' of the grid at this ratio"""
-    return L - aligned_end(L, end, rate_of(factor, filt_type).orig)
+    return L - aligned_end(L, end, rate.orig)
 
 
-def lowrate_predict(sampler, factor, filt_type: str, L: int, device):
+def lowrate_predict(sampler, rate: Rate, L: int, device):
     """predict(win, c0, c1) of a bandwidth extension of low-rate recordings: ``sampler.predict_resample`` through RateObserved(the ratio's
     tables on ``device``) over rows c0:c1 of the gathered (y, k)"""
-    tables = rate_tables(rate_of(factor, filt_type), device)
+    tables = rate_tables(rate, device)
 
     def predict(win, c0, c1):
         yw, kw = (t[c0:c1] for t in win)
@@ -243,13 +240,16 @@ def lowrate_predict(sampler, factor, filt_type: str, L: int, device):
     return predict
 
 
+restore.long_task(name="bwe_lowrate", method="predict_bwe_lowrate_long", what="restored",
+                  consistency="y + x - A(x) is undefined for an operator that changes the length", guided=None, entries=("length",),
+                  call_args={"factor": restore.REQUIRED, "filt_type": "resample"}, prepare=lambda args, factor, filt_type: rate_of(factor, filt_type),
+                  check=check_lowrate_args, build=lowrate_group, predict=lowrate_predict, step=lowrate_step)
+
+
 def lowrate_passes(sampler, y: torch.Tensor, factor, filt_type: str, L: int, end: int, length=None, max_batch: int = 8,
                    seeds: Optional[Sequence[int]] = None) -> torch.Tensor:
     """The two passes over ``sampler.predict_resample(yw [B, L + Mw], (B, L), RateObserved(tables, kw [B, L + Mw])) -> [B, L]`` with
     B <= max_batch: y [R, M] low-rate recordings on the GPU (rows contiguous, any row stride) -> restored [R, N] at the high rate.  Per pass:
-    one aid_lowrate_gather launch, the sampler calls, one aid_window_scatter launch per call (restore.run_passes, with the aligned step
+    one aid_lowrate_gather launch, the sampler calls, one aid_window_scatter launch per call (restore.run_task, with the aligned step
     L - end').  Recordings and result stay on the GPU.  Seeds as restore.restore_passes."""
-    group = lowrate_group(y, factor, filt_type, L, end, length, max_batch, seeds)
-    restore.run_passes(sampler, group.out, group.passes, lowrate_step(factor, filt_type, L, end), max_batch, seeds,
-                       group.gather, lowrate_predict(sampler, factor, filt_type, L, y.device), L=L)
-    return group.out
+    return restore.run_task(restore.LONG_TASKS["bwe_lowrate"], sampler, rate_of(factor, filt_type), [(y, length)], L, end, max_batch, seeds)[0]

@@ -175,10 +175,17 @@ def pr_gather(rec: torch.Tensor, out: torch.Tensor, jobs: torch.Tensor, L: int, 
     return y, k
 
 
-def check_pr_args(y: torch.Tensor, win_size, hop_size, length, L: int, end: int, max_batch: int, seeds):
-    """The refusals of a phase retrieval of whole recordings, all raised before anything is launched -> (n_fft, hop, N).
+def pr_prepare(args):
+    """What the groups of a call share: (n_fft, hop), phase.check_sizes of win_size / hop_size where predict_pr reads them
+    (sampler.phase_retrieval_sizes), judged before any spectrogram"""
+    from .sampler import phase_retrieval_sizes
+    return phase.check_sizes(*phase_retrieval_sizes(args))
+
+
+def check_pr_args(y: torch.Tensor, length, sizes, L: int, end: int, max_batch: int, seeds):
+    """The refusals of a phase retrieval of whole recordings after phase.check_sizes', all raised before anything is launched -> (n_fft, hop, N).
     What can be judged without a GPU is judged first; the device of y last."""
-    n_fft, hop = phase.check_sizes(win_size, hop_size)
+    n_fft, hop = sizes
     F = n_fft // 2 + 1
     if not (torch.is_tensor(y) and y.dtype == torch.float32 and y.dim() == 3 and y.shape[0] >= 1 and y.shape[1] == F and y.shape[2] >= 1):
         raise _lib.AidError(f"y must be float32 magnitude spectrograms [R, F = {F}, T_rec] (|STFT| with win_size {n_fft}, hop_size {hop}), "
@@ -189,12 +196,12 @@ def check_pr_args(y: torch.Tensor, win_size, hop_size, length, L: int, end: int,
     return n_fft, hop, N
 
 
-def pr_group(y: torch.Tensor, win_size, hop_size, L: int, end: int, length=None, max_batch: int = 8,
-             seeds: Optional[Sequence[int]] = None) -> restore.Group:
-    """The part of a phase retrieval that checks, plans and builds: y [R, F, T_rec] magnitude spectrograms on the GPU (any strides; one copy
-    unless T_rec has unit stride) -> restore.Group(out = zeros [R, N], (jobs_A, jobs_B) of pr_plan, the aid_pr_gather closure).  win_size
-    and hop_size are shared by every group of a call (``pr_predict``); the states of a job travel in the gathered rows."""
-    n_fft, hop, N = check_pr_args(y, win_size, hop_size, length, L, end, max_batch, seeds)
+def pr_group(y: torch.Tensor, checked, sizes, L: int, end: int) -> restore.Group:
+    """The part of a phase retrieval that plans and builds: y [R, F, T_rec] magnitude spectrograms on the GPU (any strides; one copy
+    unless T_rec has unit stride), (n_fft, hop, N) of check_pr_args -> restore.Group(out = zeros [R, N], (jobs_A, jobs_B) of pr_plan, the
+    aid_pr_gather closure).  win_size and hop_size are shared by every group of a call (``pr_predict``); the states of a job travel in the
+    gathered rows."""
+    n_fft, hop, N = checked
     R, F, T_rec = y.shape
     if (T_rec > 1 and y.stride(2) != 1) or y.stride(1) < T_rec or y.stride(0) < (F - 1) * y.stride(1) + T_rec:
         y = y.contiguous()                                                   # (torch.stft hands out [R, F, T] with frames strided: one copy, before pass A)
@@ -202,23 +209,23 @@ def pr_group(y: torch.Tensor, win_size, hop_size, L: int, end: int, length=None,
     return restore.Group(out, pr_plan(R, N, L, end, n_fft, hop), lambda table: pr_gather(y, out, table, L, n_fft, hop))
 
 
-def pr_predict(sampler, n_fft: int, hop: int, L: int):
+def pr_predict(sampler, sizes, L: int, device):
     """predict(win, c0, c1) of a phase retrieval: ``sampler.predict_resample`` through STFTMagObserved over rows c0:c1 of the gathered (y, k)"""
     def predict(win, c0, c1):
         yw, kw = (t[c0:c1] for t in win)
-        return sampler.predict_resample(yw, (c1 - c0, L), STFTMagObserved(n_fft, hop, kw))
+        return sampler.predict_resample(yw, (c1 - c0, L), STFTMagObserved(*sizes, kw))
     return predict
+
+
+restore.long_task(name="pr", method="predict_pr_long", what="restored", consistency="no data-consistency step exists for phase retrieval",
+                  guided="the reference asserts xi > 0", entries=("length",), call_args={}, prepare=pr_prepare, check=check_pr_args, build=pr_group,
+                  predict=pr_predict, step=lambda sizes, L, end: L - aligned_end(L, end, sizes[1]))
 
 
 def pr_passes(sampler, y: torch.Tensor, win_size, hop_size, L: int, end: int, length=None, max_batch: int = 8,
               seeds: Optional[Sequence[int]] = None) -> torch.Tensor:
     """The two passes over ``sampler.predict_resample(yw [B, L + F*Tw], (B, L), STFTMagObserved(win_size, hop_size, kw [B, L + Tw])) -> [B, L]``
     with B <= max_batch: y [R, F, T_rec] magnitude spectrograms on the GPU (any strides; the gather reads them in place when T_rec has unit
-    stride) -> restored [R, N].  Per pass: one aid_pr_gather launch, the sampler
-    calls, one aid_window_scatter launch per call (restore.run_passes, with the aligned step L - end').  Spectrograms and result stay on the
-    GPU.  Seeds as restore.restore_passes."""
-    group = pr_group(y, win_size, hop_size, L, end, length, max_batch, seeds)
-    n_fft, hop = phase.check_sizes(win_size, hop_size)
-    restore.run_passes(sampler, group.out, group.passes, L - aligned_end(L, end, hop), max_batch, seeds,
-                       group.gather, pr_predict(sampler, n_fft, hop, L), L=L)
-    return group.out
+    stride) -> restored [R, N].  Per pass: one aid_pr_gather launch, the sampler calls, one aid_window_scatter launch per call
+    (restore.run_task, with the aligned step L - end').  Spectrograms and result stay on the GPU.  Seeds as restore.restore_passes."""
+    return restore.run_task(restore.LONG_TASKS["pr"], sampler, phase.check_sizes(win_size, hop_size), [(y, length)], L, end, max_batch, seeds)[0]

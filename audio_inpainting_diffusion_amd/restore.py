@@ -17,12 +17,13 @@ autoregressive mode, testing/edm_sampler.py:416).
 ``restore_plan`` is host code (the only part that looks at the mask on the host); ``window_gather`` / ``window_scatter`` launch the
 two HIP kernels of csrc/aid_restore.hip; ``restore_passes`` is the pass code, driven with anything that has ``predict_inpainting``.
 
-This module is also the one home of what the other whole-recording modes share (declip_long.py, bwe_long.py, bwe_declip_long.py, lowrate_long.py,
-phase_long.py, spec_long.py; DESIGN.md, "The window scheme of whole recordings"): ``aligned_end`` / ``trimmed_windows`` / ``every_window_plan`` (the grid
-aligned to a period, the ownership trimmed by an operator's reach, every window a job), ``check_rows`` / ``check_batch`` (the refusals
-every mode raises), ``WindowOperator`` (the base of the window operators) and ``run_passes`` (the pass loop).  ``run_pooled_passes`` is
-that loop over several ``Group`` records, one per recording length: the jobs of all lengths share the chunks of one pooled pass A and one
-pooled pass B; ``run_passes`` is its one-group case.
+This module is also the one home of what the other whole-recording modes share (declip_long.py, bwe_long.py, bwe_iir_long.py, bwe_declip_long.py,
+lowrate_long.py, phase_long.py, spec_long.py, blind_long.py; DESIGN.md, "The window scheme of whole recordings"): ``aligned_end`` / ``trimmed_windows`` /
+``every_window_plan`` (the grid aligned to a period, the ownership trimmed by an operator's reach, every window a job), ``check_rows`` /
+``check_batch`` (the refusals every mode raises), ``WindowOperator`` (the base of the window operators) and ``run_passes`` (the pass loop).
+``run_pooled_passes`` is that loop over several ``Group`` records, one per recording length: the jobs of all lengths share the chunks of one
+pooled pass A and one pooled pass B; ``run_passes`` is its one-group case.  The seven modes that pool are one ``LongTask``
+record each in ``LONG_TASKS``, declared by the mode's module, and ``run_task`` is their one driver, for one length and for many.
 
 Under an active process group (dist.py) ``run_passes`` shares every pass out over the ranks -- contiguous shares, the unchanged seed rule,
 one all-gather of the windows per pass, the whole pass scattered on every rank -- after ``guard_ranks`` has compared what the ranks were
@@ -30,7 +31,7 @@ given (``pass_digest``); host code only, the kernels and the sampler rounds are 
 """
 from __future__ import annotations
 
-from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -183,19 +184,6 @@ def window_scatter(x: torch.Tensor, out: torch.Tensor, jobs: torch.Tensor):
         raise _lib.AidError(f"window_scatter: x must be contiguous [J = {J}, L], got {tuple(x.shape)}")
     if J:
         _lib.call("aid_window_scatter", _lib.WindowScatterParams(x.data_ptr(), out.data_ptr(), jobs.data_ptr(), J, out.shape[0], x.shape[1], out.shape[1], out.stride(0)))
-
-
-def check_restore_args(y: torch.Tensor, mask: torch.Tensor, L: int, end: int, max_batch: int, seeds) -> torch.Tensor:
-    """The refusals of a restoration, all raised before anything is launched -> the mask as [1|R, N].  What can be judged without a GPU is
-    judged first; the device of y last."""
-    check_rows(y, "recordings [R, N]")
-    if mask.dim() == 1:
-        mask = mask.reshape(1, -1)
-    if mask.dim() != 2 or mask.shape[1] != y.shape[1] or mask.shape[0] not in (1, y.shape[0]):
-        raise _lib.AidError(f"mask {tuple(mask.shape)} does not match recordings {tuple(y.shape)} (y [R, N], mask [1, N] or [R, N])")
-    restore_windows(y.shape[1], L, end)                               # (end in [1, L/2))
-    check_batch(y, max_batch, seeds, "restoration of whole recordings")
-    return mask
 
 
 def check_rows(y, what: str, nonempty: bool = False) -> None:
@@ -450,20 +438,95 @@ def run_passes(sampler, out: torch.Tensor, passes: Sequence[Sequence[Job]], step
     run_pooled_passes(sampler, [Group(out, passes, gather)], step, max_batch, seeds, predict, L)
 
 
-def restore_group(y: torch.Tensor, mask: torch.Tensor, L: int, end: int, max_batch: int = 8, seeds: Optional[Sequence[int]] = None) -> Group:
-    """The part of a restoration that checks, plans and builds: y [R, N] recordings on the GPU (rows contiguous, any row stride), mask
-    [1|R, N] -> Group(out = a copy of y, (jobs_A, jobs_B) of restore_plan, the aid_window_gather closure).  The plan is made on the host from
-    the mask; the mask goes to the GPU only when there is a job."""
-    mask = check_restore_args(y, mask, L, end, max_batch, seeds)
+class LongTask(NamedTuple):
+    """One whole-recording mode, as everything that drives it sees it: Sampler.predict_*_long and Sampler.predict_long_pooled (through
+    Sampler._long), the module's ``*_passes`` function (through ``run_task``) and harness.py.  Each mode module declares its record with
+    ``long_task`` next to the functions the record names; nothing else knows a mode."""
+    name: str                                        # the task of predict_long_pooled, e.g. "bwe_iir"
+    method: str                                      # the Sampler method, named in the refusals, e.g. "predict_bwe_iir_long"
+    what: str                                        # "restored" / "declipped": what the rid refusal says the method returns
+    consistency: Optional[str]                       # why tester.data_consistency in use is refused; None: it is served
+    guided: Optional[str]                            # the tail of the refusal of xi <= 0; None: xi = 0 is served
+    entries: Tuple[str, ...]                         # the names of a group's entries after y, in the order of the method's parameters
+    call_args: Dict[str, object]                     # the arguments all groups of a call share: name -> default, REQUIRED where there is none
+    prepare: Callable                                # prepare(sampler_args, **call_args) -> state: what the groups share, judged before any group
+    check: Callable                                  # check(y, *entries, state, L, end, max_batch, seeds) -> checked: the refusals, all before any launch
+    build: Callable                                  # build(y, checked, state, L, end) -> Group, from what ``check`` returned; it validates nothing
+    predict: Callable                                # predict(sampler, state, L, device) -> predict(win, c0, c1), one for all groups
+    step: Callable                                   # step(state, L, end) -> the distance between window starts
+
+
+REQUIRED = object()                                  # the default of a call argument that has none
+LONG_TASKS: Dict[str, LongTask] = {}
+
+
+def long_task(**fields) -> None:
+    """Declare a mode: its record, entered in LONG_TASKS under its name."""
+    LONG_TASKS[fields["name"]] = LongTask(**fields)
+
+
+def plain_step(state, L: int, end: int) -> int:
+    """``step`` of a mode whose grid needs no alignment"""
+    return L - end
+
+
+def run_task(task: LongTask, sampler, state, groups, L: int, end: int, max_batch: int = 8, seeds=None, ready: Optional[Callable] = None) -> List[torch.Tensor]:
+    """The one driver of the whole-recording modes, for one length and for many: ``groups`` holds per set of equal-length recordings
+    (y, *task.entries) -- a bare tensor is (y,), a missing entry None -- and ``state`` is task.prepare's.  In this order: ``task.check`` of
+    every group, the seed count over all groups, the one-device refusal, ``ready()`` (Sampler._check_model), and only then ``task.build`` of
+    every group from what its check returned, and run_pooled_passes -> one [R_g, N_g] per group.  ``seeds``: one per recording over all
+    groups in order; a single group is handed the list as it is, so that a list of the wrong length is refused where the plain methods
+    refuse it.  Without a job and without a process group nothing is launched and the copies come back (``no_jobs``)."""
+    width = 1 + len(task.entries)
+    groups = [((tuple(g) if isinstance(g, (tuple, list)) else (g,)) + (None,) * width)[:width] for g in groups]
+    device = next((g[0].device for g in groups if torch.is_tensor(g[0])), None)
+    bounds = [0]
+    for g in groups:
+        bounds.append(bounds[-1] + (g[0].shape[0] if torch.is_tensor(g[0]) and g[0].dim() >= 1 else 0))
+    share = len(groups) > 1 and seeds is not None
+    checked = [task.check(*g, state, L, end, max_batch, seeds[bounds[i]:bounds[i + 1]] if share else seeds) for i, g in enumerate(groups)]
+    if seeds is not None and len(seeds) != bounds[-1]:
+        raise _lib.AidError(f"{len(seeds)} seeds for {bounds[-1]} recordings")
+    if any(torch.is_tensor(g[0]) and g[0].device != device for g in groups):
+        raise _lib.AidError("predict_long_pooled: the recordings of all groups must be on one device")
+    if ready is not None:
+        ready()
+    built = [task.build(g[0], c, state, L, end)._replace(files=range(bounds[i], bounds[i + 1])) for i, (g, c) in enumerate(zip(groups, checked))]
+    if not no_jobs(*(jobs for b in built for jobs in b.passes)):
+        run_pooled_passes(sampler, built, task.step(state, L, end), max_batch, seeds, task.predict(sampler, state, L, device), L=L)
+    return [b.out for b in built]
+
+
+def check_restore_args(y: torch.Tensor, mask: torch.Tensor, state, L: int, end: int, max_batch: int, seeds) -> torch.Tensor:
+    """The refusals of a restoration, all raised before anything is launched -> the mask as [1|R, N].  What can be judged without a GPU is
+    judged first; the device of y last."""
+    check_rows(y, "recordings [R, N]")
+    if mask.dim() == 1:
+        mask = mask.reshape(1, -1)
+    if mask.dim() != 2 or mask.shape[1] != y.shape[1] or mask.shape[0] not in (1, y.shape[0]):
+        raise _lib.AidError(f"mask {tuple(mask.shape)} does not match recordings {tuple(y.shape)} (y [R, N], mask [1, N] or [R, N])")
+    restore_windows(y.shape[1], L, end)                               # (end in [1, L/2))
+    check_batch(y, max_batch, seeds, "restoration of whole recordings")
+    return mask
+
+
+def restore_group(y: torch.Tensor, mask: torch.Tensor, state, L: int, end: int) -> Group:
+    """The part of a restoration that plans and builds: y [R, N] recordings on the GPU (rows contiguous, any row stride), the mask
+    [1|R, N] of check_restore_args -> Group(out = a copy of y, (jobs_A, jobs_B) of restore_plan, the aid_window_gather closure).  The plan
+    is made on the host from the mask; the mask goes to the GPU only when there is a job."""
     jobs_A, jobs_B, _ = restore_plan(mask, L, end, y.shape[0])
     out = y.clone(memory_format=torch.contiguous_format)
     dmask = mask.to(y.device, torch.float32).contiguous() if jobs_A or jobs_B else None
     return Group(out, (jobs_A, jobs_B), lambda table: window_gather(y, out, dmask, table, L))    # (pass B reads what pass A scattered)
 
 
-def restore_predict(sampler):
+def restore_predict(sampler, state, L: int, device):
     """predict(win, c0, c1) of a restoration: ``sampler.predict_inpainting`` over rows c0:c1 of the gathered (y, m)"""
     return lambda win, c0, c1: sampler.predict_inpainting(win[0][c0:c1], win[1][c0:c1])
+
+
+long_task(name="inpainting", method="predict_inpainting_long", what="restored", consistency=None, guided=None, entries=("mask",), call_args={},
+          prepare=lambda args: None, check=check_restore_args, build=restore_group, predict=restore_predict, step=plain_step)
 
 
 def restore_passes(sampler, y: torch.Tensor, mask: torch.Tensor, L: int, end: int, max_batch: int = 8, seeds: Optional[Sequence[int]] = None) -> torch.Tensor:
@@ -471,7 +534,4 @@ def restore_passes(sampler, y: torch.Tensor, mask: torch.Tensor, L: int, end: in
     (rows contiguous, any row stride), mask [1|R, N] -> restored [R, N].  Per pass: one gather launch, the sampler calls, one scatter launch per
     call.  Recordings, mask and result stay on the GPU; the plan is made on the host from the mask before pass A.  ``seeds`` [R]: the job of
     window w of recording r runs with ``sampler.seeds = [seeds[r] * 65536 + w, ...]`` (None: sampler.seeds = None, the global generator)."""
-    group = restore_group(y, mask, L, end, max_batch, seeds)
-    if not no_jobs(*group.passes):
-        run_passes(sampler, group.out, group.passes, L - end, max_batch, seeds, group.gather, restore_predict(sampler), L=L)
-    return group.out
+    return run_task(LONG_TASKS["inpainting"], sampler, None, [(y, mask)], L, end, max_batch, seeds)[0]

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import bwe_declip_long, bwe_iir_long, bwe_long, declip_long, lowrate_long, phase_long, restore    # noqa: F401  (each declares its mode in restore.LONG_TASKS)
 from .degrade import Decimate, FIRFilter, HardClip, IIRFilter, SincResample
 from .phase import STFTMagnitude, observation_shape
 from .stft import SpectralMask
@@ -546,6 +547,17 @@ class Sampler:
         L = int(self.args.exp.audio_len)
         return L, int(autoregressive_overlap(self.args) * L)
 
+    def _long(self, name, groups, max_batch, seeds, **call_args):
+        """Run the whole-recording mode ``name`` (its record in restore.LONG_TASKS) over ``groups``, one set of equal-length recordings each
+        -> one result per group.  What every predict_*_long method and predict_long_pooled are: the refusals of ``_long_grid``, the refusal
+        of xi <= 0 where the mode is guided only, the record's ``prepare`` of what the groups share, then restore.run_task -- every group
+        checked, ``_check_model``, every group built, the pooled passes.  All refusals are raised before anything is launched."""
+        task = restore.LONG_TASKS[name]
+        L, end = self._long_grid(task.method, task.what, task.consistency)
+        if task.guided and not self.xi > 0:
+            raise _lib.AidError(f"{task.method} needs reconstruction guidance: tester.posterior_sampling.xi must be > 0 ({task.guided})")
+        return restore.run_task(task, self, task.prepare(self.args, **call_args), groups, L, end, max_batch, seeds, ready=self._check_model)
+
     def predict_inpainting_long(self, y, mask, max_batch=8, seeds=None):
         """Restore whole recordings y[R, N] -- N any length, gaps wherever mask[1|R, N] is 0 -> [R, N] on y.device (restore.py).  Windows of
         L = args.exp.audio_len samples on the autoregressive grid (end = int(overlap * L) shared samples, 1 <= end < L/2); the even windows that
@@ -557,11 +569,7 @@ class Sampler:
         calls with the same y, mask and seeds and gets the full [R, N]: rank k runs dist.shard_range of each round's windows in chunks of at most
         ``max_batch`` (per rank), one dist.gather_outputs per round brings all windows to every rank, and each rank scatters the whole round
         (restore.run_passes).  ``seeds`` = None is then refused, and ranks that were given different work raise before anything is launched."""
-        from . import restore
-        L, end = self._long_grid("predict_inpainting_long")
-        mask = restore.check_restore_args(y, mask, L, end, max_batch, seeds)
-        self._check_model()
-        return restore.restore_passes(self, y, mask, L, end, max_batch, seeds)
+        return self._long("inpainting", [(y, mask)], max_batch, seeds)[0]
 
     def predict_declipping_long(self, y, clip_value, max_batch=8, seeds=None):
         """Declip whole recordings y[R, N] -- N any length, clipped at +-clip_value (a float, or R floats: one level per recording; rounded to
@@ -573,10 +581,7 @@ class Sampler:
         clipped sample cost nothing and keep the recording's samples.
         Under an active process group the windows of each pass are shared out over the ranks as predict_inpainting_long states: the same
         arguments and weights (dist.broadcast_parameters) on every rank, ``seeds`` required, ``max_batch`` per rank, the full result on every rank."""
-        from . import declip_long
-        L, end = self._long_grid("predict_declipping_long", "declipped")
-        self._check_model()
-        return declip_long.declip_passes(self, y, clip_value, L, end, max_batch, seeds)      # (validates its arguments before anything is launched)
+        return self._long("declipping", [(y, clip_value)], max_batch, seeds)[0]
 
     def predict_bwe_long(self, y, filt, filt_type, max_batch=8, seeds=None):
         """Bandwidth-extend whole recordings y[R, N] -- N any length, low-passed as a whole with the FIR taps ``filt`` ([K], [1, K] or [1, 1, K],
@@ -591,11 +596,7 @@ class Sampler:
         exists only at a low sample rate ("decimate", "resample") goes through predict_bwe_lowrate_long, whose grid is aligned to the input period.
         Under an active process group the windows of each pass are shared out over the ranks as predict_inpainting_long states: the same
         arguments and weights (dist.broadcast_parameters) on every rank, ``seeds`` required, ``max_batch`` per rank, the full result on every rank."""
-        from . import bwe_long
-        L, end = self._long_grid("predict_bwe_long")
-        bwe_long.check_bwe_args(y, filt, filt_type, L, end, max_batch, seeds)
-        self._check_model()
-        return bwe_long.bwe_passes(self, y, filt, filt_type, L, end, max_batch, seeds)
+        return self._long("bwe", [(y,)], max_batch, seeds, filt=filt, filt_type=filt_type)[0]
 
     def predict_blind_bwe_long(self, y, probes=4, max_batch=8, seeds=None, frozen_taps=None):
         """Blind bandwidth extension of whole recordings y[R, N] -- N any length, each low-passed as a whole by an UNKNOWN zero-phase low-pass
@@ -643,11 +644,7 @@ class Sampler:
         "biquad" DEPARTS from predict_bwe "biquad": torchaudio clamps the filtered signal to [-1, 1]; here a recording with a sample |y| >= 1 is
         refused (the clamp acted, the recording no longer satisfies the recursion) and the window operator is the linear filter, whereas
         predict_bwe "biquad" also drops the gradient where the model's own filtered estimate leaves [-1, 1]."""
-        from . import bwe_iir_long
-        L, end = self._long_grid("predict_bwe_iir_long")
-        bwe_iir_long.check_bwe_iir_args(y, filt, filt_type, L, end, max_batch, seeds)
-        self._check_model()
-        return bwe_iir_long.bwe_iir_passes(self, y, filt, filt_type, L, end, max_batch, seeds)
+        return self._long("bwe_iir", [(y,)], max_batch, seeds, filt=filt, filt_type=filt_type)[0]
 
     def predict_bwe_declip_long(self, y, filt, filt_type, clip_value=None, mask=None, max_batch=8, seeds=None):
         """Bandwidth-extend whole recordings y[R, N] that are also clipped and have dropouts -- N any length -> [R, N] on y.device
@@ -665,11 +662,7 @@ class Sampler:
         launched, naming the recording and the window.
         Under an active process group the windows of each pass are shared out over the ranks as predict_inpainting_long states: the same
         arguments and weights (dist.broadcast_parameters) on every rank, ``seeds`` required, ``max_batch`` per rank, the full result on every rank."""
-        from . import bwe_declip_long
-        L, end = self._long_grid("predict_bwe_declip_long", consistency=bwe_declip_long.NO_PROJECTION)
-        bwe_declip_long.check_bwe_declip_args(y, filt, filt_type, clip_value, mask, L, end, max_batch, seeds)
-        self._check_model()
-        return bwe_declip_long.bwe_declip_passes(self, y, filt, filt_type, clip_value, mask, L, end, max_batch, seeds)
+        return self._long("bwe_declip", [(y, clip_value, mask)], max_batch, seeds, filt=filt, filt_type=filt_type)[0]
 
     def predict_bwe_lowrate_long(self, y, factor, filt_type="resample", length=None, max_batch=8, seeds=None):
         """Bandwidth-extend whole recordings that exist only at a low sample rate: y[R, M] on the GPU -> [R, N] at the high rate, N any length
@@ -685,11 +678,7 @@ class Sampler:
         operator that changes the length).
         Under an active process group the windows of each pass are shared out over the ranks as predict_inpainting_long states: the same
         arguments and weights (dist.broadcast_parameters) on every rank, ``seeds`` required, ``max_batch`` per rank, the full result on every rank."""
-        from . import lowrate_long
-        L, end = self._long_grid("predict_bwe_lowrate_long", consistency="y + x - A(x) is undefined for an operator that changes the length")
-        lowrate_long.check_lowrate_args(y, factor, filt_type, length, L, end, max_batch, seeds)
-        self._check_model()
-        return lowrate_long.lowrate_passes(self, y, factor, filt_type, L, end, length, max_batch, seeds)
+        return self._long("bwe_lowrate", [(y, length)], max_batch, seeds, factor=factor, filt_type=filt_type)[0]
 
     def predict_pr_long(self, y, length=None, max_batch=8, seeds=None):
         """Retrieve the phase of whole recordings known only by their STFT magnitude: y[R, F, T_rec] on the GPU (|STFT| as predict_pr takes it:
@@ -707,14 +696,7 @@ class Sampler:
         Guidance only: xi <= 0, rid and tester.data_consistency in use are refused.
         Under an active process group the windows of each pass are shared out over the ranks as predict_inpainting_long states: the same
         arguments and weights (dist.broadcast_parameters) on every rank, ``seeds`` required, ``max_batch`` per rank, the full result on every rank."""
-        from . import phase_long
-        L, end = self._long_grid("predict_pr_long", consistency="no data-consistency step exists for phase retrieval")
-        if not self.xi > 0:
-            raise _lib.AidError("predict_pr_long needs reconstruction guidance: tester.posterior_sampling.xi must be > 0 (the reference asserts xi > 0)")
-        win, hop = phase_retrieval_sizes(self.args)
-        phase_long.check_pr_args(y, win, hop, length, L, end, max_batch, seeds)
-        self._check_model()
-        return phase_long.pr_passes(self, y, win, hop, L, end, length, max_batch, seeds)
+        return self._long("pr", [(y, length)], max_batch, seeds)[0]
 
     def predict_spectrogram_inpainting_long(self, y, mask, max_batch=8, seeds=None):
         """Restore whole recordings whose spectrogram was masked: y[R, N] on the GPU -- N any length, y = the reference's apply_spectral_mask of
@@ -739,54 +721,6 @@ class Sampler:
 
     POOLED_TASKS = ("inpainting", "declipping", "bwe", "bwe_iir", "bwe_declip", "bwe_lowrate", "pr")
 
-    def _pooled_task(self, task, device, filt=None, filt_type=None, factor=None):
-        """(check(group, max_batch, seeds), build(group, max_batch, seeds) -> restore.Group, predict(), step, L) of predict_long_pooled: per
-        task the refusals of the matching predict_*_long before its arguments are judged, its check_*_args, its group builder, and the one
-        predict closure (made by ``predict()``, after the checks) and step that the groups of a call share (the taps, the ratio, win_size / hop_size)."""
-        from . import bwe_declip_long, bwe_iir_long, bwe_long, declip_long, lowrate_long, phase_long, restore
-        if task == "inpainting":
-            L, end = self._long_grid("predict_inpainting_long")
-            return (lambda g, mb, sd: restore.check_restore_args(g[0], g[1], L, end, mb, sd),
-                    lambda g, mb, sd: restore.restore_group(g[0], g[1], L, end, mb, sd), lambda: restore.restore_predict(self), L - end, L)
-        if task == "declipping":
-            L, end = self._long_grid("predict_declipping_long", "declipped")
-            return (lambda g, mb, sd: declip_long.check_declip_args(g[0], g[1], L, end, mb, sd),
-                    lambda g, mb, sd: declip_long.declip_group(g[0], g[1], L, end, mb, sd), lambda: declip_long.declip_predict(self, L), L - end, L)
-        if task == "bwe":
-            L, end = self._long_grid("predict_bwe_long")
-            return (lambda g, mb, sd: bwe_long.check_bwe_args(g[0], filt, filt_type, L, end, mb, sd),
-                    lambda g, mb, sd: bwe_long.bwe_group(g[0], filt, filt_type, L, end, mb, sd),
-                    lambda: bwe_long.bwe_predict(self, filt, L, device), L - end, L)
-        if task == "bwe_iir":
-            L, end = self._long_grid("predict_bwe_iir_long")
-            shared = []                                                            # (the one predict closure, made after the checks; it holds the one table)
-
-            def predict():
-                if not shared:
-                    shared.append(bwe_iir_long.bwe_iir_predict(self, filt, filt_type, L, device))
-                return shared[0]
-            return (lambda g, mb, sd: bwe_iir_long.check_bwe_iir_args(g[0], filt, filt_type, L, end, mb, sd),
-                    lambda g, mb, sd: bwe_iir_long.bwe_iir_group(g[0], filt, filt_type, L, end, mb, sd, table=predict().table), predict, L - end, L)
-        if task == "bwe_declip":
-            L, end = self._long_grid("predict_bwe_declip_long", consistency=bwe_declip_long.NO_PROJECTION)
-            return (lambda g, mb, sd: bwe_declip_long.check_bwe_declip_args(g[0], filt, filt_type, g[1], g[2], L, end, mb, sd),
-                    lambda g, mb, sd: bwe_declip_long.bwe_declip_group(g[0], filt, filt_type, g[1], g[2], L, end, mb, sd),
-                    lambda: bwe_declip_long.bwe_declip_predict(self, filt, L, device), L - end, L)
-        if task == "bwe_lowrate":
-            L, end = self._long_grid("predict_bwe_lowrate_long", consistency="y + x - A(x) is undefined for an operator that changes the length")
-            ft = "resample" if filt_type is None else filt_type
-            lowrate_long.rate_of(factor, ft)                                       # (the ratio is judged first, as check_lowrate_args does)
-            return (lambda g, mb, sd: lowrate_long.check_lowrate_args(g[0], factor, ft, g[1], L, end, mb, sd),
-                    lambda g, mb, sd: lowrate_long.lowrate_group(g[0], factor, ft, L, end, g[1], mb, sd),
-                    lambda: lowrate_long.lowrate_predict(self, factor, ft, L, device), lowrate_long.lowrate_step(factor, ft, L, end), L)
-        L, end = self._long_grid("predict_pr_long", consistency="no data-consistency step exists for phase retrieval")
-        if not self.xi > 0:
-            raise _lib.AidError("predict_pr_long needs reconstruction guidance: tester.posterior_sampling.xi must be > 0 (the reference asserts xi > 0)")
-        win, hop = phase_retrieval_sizes(self.args)
-        return (lambda g, mb, sd: phase_long.check_pr_args(g[0], win, hop, g[1], L, end, mb, sd),
-                lambda g, mb, sd: phase_long.pr_group(g[0], win, hop, L, end, g[1], mb, sd),
-                lambda: phase_long.pr_predict(self, win, hop, L), L - restore.aligned_end(L, end, hop), L)
-
     def predict_long_pooled(self, task, groups, max_batch=8, seeds=None, **task_args):
         """Whole recordings of DIFFERENT lengths in shared passes: ``task`` is "inpainting", "declipping", "bwe", "bwe_iir", "bwe_declip", "bwe_lowrate" or "pr", and every
         entry of ``groups`` is what the matching predict_*_long takes for one set of equal-length recordings -- (y, mask), (y, clip_value), y, y,
@@ -801,35 +735,16 @@ class Sampler:
         cannot share a launch.
         Under an active process group the pooled windows of each pass are shared out over the ranks (one guard over all groups, one exchange
         per pass); ``seeds`` is then required."""
-        from . import restore
         if task == "spectrogram_inpainting":
             raise _lib.AidError("predict_long_pooled does not cover spectrogram inpainting: aid_stft_mask_observed reads one recording-shaped "
                                 "mask [F, T_rec] in place, so the windows of recordings with different T_rec cannot share a launch "
                                 "(call predict_spectrogram_inpainting_long per length)")
         if task not in self.POOLED_TASKS:
             raise NotImplementedError(f"predict_long_pooled: unknown task {task!r} (one of {', '.join(self.POOLED_TASKS)})")
-        allowed = {"bwe": ("filt", "filt_type"), "bwe_iir": ("filt", "filt_type"), "bwe_declip": ("filt", "filt_type"),
-                   "bwe_lowrate": ("factor", "filt_type")}.get(task, ())
-        if set(task_args) - set(allowed) or (task in ("bwe", "bwe_iir", "bwe_declip") and set(task_args) != set(allowed)) or (task == "bwe_lowrate" and "factor" not in task_args):
+        allowed = restore.LONG_TASKS[task].call_args
+        if set(task_args) - set(allowed) or any(v is restore.REQUIRED and k not in task_args for k, v in allowed.items()):
             raise TypeError(f"predict_long_pooled({task!r}) takes the task arguments ({', '.join(allowed)}), got ({', '.join(task_args)})")
-        width = 3 if task == "bwe_declip" else 2
-        groups = [tuple(g) + (None,) * (width - len(g)) if isinstance(g, (tuple, list)) else (g,) + (None,) * (width - 1) for g in groups]
-        device = next((g[0].device for g in groups if torch.is_tensor(g[0])), None)
-        check, build, predict, step, L = self._pooled_task(task, device, **task_args)
-        bounds = [0]
-        for g in groups:
-            bounds.append(bounds[-1] + (g[0].shape[0] if torch.is_tensor(g[0]) and g[0].dim() >= 1 else 0))
-        per = [None if seeds is None else [int(s) for s in seeds[bounds[i]:bounds[i + 1]]] for i in range(len(groups))]
-        for g, sd in zip(groups, per):
-            check(g, max_batch, sd)
-        if seeds is not None and len(seeds) != bounds[-1]:
-            raise _lib.AidError(f"{len(seeds)} seeds for {bounds[-1]} recordings")
-        if any(torch.is_tensor(g[0]) and g[0].device != device for g in groups):
-            raise _lib.AidError("predict_long_pooled: the recordings of all groups must be on one device")
-        self._check_model()
-        built = [build(g, max_batch, sd)._replace(files=range(bounds[i], bounds[i + 1])) for i, (g, sd) in enumerate(zip(groups, per))]
-        restore.run_pooled_passes(self, built, step, max_batch, seeds, predict(), L=L)
-        return [b.out for b in built]
+        return self._long(task, groups, max_batch, seeds, **{**allowed, **task_args})
 
     # ---- the remaining public methods of the reference class (its testers never call them; kept so that code written against
     # ---- testing.edm_sampler_inpainting.Sampler finds every name).  They run outside the sampling loop. ------------------------------

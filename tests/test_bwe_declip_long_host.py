@@ -164,9 +164,9 @@ def test_every_refusal_is_raised_before_any_launch(monkeypatch):
         with pytest.raises(_lib.AidError, match="seeds"):
             smp.predict_bwe_declip_long(y, taps, "firwin", seeds=bad)
     with pytest.raises(_lib.AidError, match="seeds"):
-        bwe_declip_long.check_bwe_declip_args(y, taps, "firwin", 0.5, None, L, end, 8, [1])
+        bwe_declip_long.check_bwe_declip_args(y, 0.5, None, bwe_declip_long.bwe_declip_prepare(None, taps, "firwin"), L, end, 8, [1])
     with pytest.raises(_lib.AidError, match="GPU only"):
-        bwe_declip_long.check_bwe_declip_args(y, taps, "firwin", 0.5, None, L, end, 8, [1, 2])
+        bwe_declip_long.check_bwe_declip_args(y, 0.5, None, bwe_declip_long.bwe_declip_prepare(None, taps, "firwin"), L, end, 8, [1, 2])
     # seeds = None under a process group
     monkeypatch.setattr(dist, "_active", lambda: True)
     with pytest.raises(_lib.AidError, match="under a process group needs seeds") as e:
@@ -184,11 +184,11 @@ def test_check_returns_the_taps_the_levels_and_the_mask_rows(monkeypatch):
     y = torch.zeros(3, N)
     calls = []
     monkeypatch.setattr(restore, "check_batch", lambda *a: calls.append(a))  # (the device of y, judged last)
-    taps, levels, mask = bwe_declip_long.check_bwe_declip_args(y, torch.ones(1, 1, 9), "firwin", None, None, L, end, 8, None)
+    taps, levels, mask = bwe_declip_long.check_bwe_declip_args(y, None, None, bwe_declip_long.bwe_declip_prepare(None, torch.ones(1, 1, 9), "firwin"), L, end, 8, None)
     assert taps.shape == (9,) and levels.dtype == np.float32 and levels.tolist() == [math.inf] * 3 and mask is None
-    taps, levels, mask = bwe_declip_long.check_bwe_declip_args(y, torch.ones(9), "firwin", 0.1, torch.ones(N), L, end, 8, None)
+    taps, levels, mask = bwe_declip_long.check_bwe_declip_args(y, 0.1, torch.ones(N), bwe_declip_long.bwe_declip_prepare(None, torch.ones(9), "firwin"), L, end, 8, None)
     assert levels.tolist() == [np.float32(0.1)] * 3 and mask.shape == (1, N)
-    _, levels, mask = bwe_declip_long.check_bwe_declip_args(y, torch.ones(9), "firwin_hpf", [0.1, 0.2, 0.3], torch.ones(3, N), L, end, 8, None)
+    _, levels, mask = bwe_declip_long.check_bwe_declip_args(y, [0.1, 0.2, 0.3], torch.ones(3, N), bwe_declip_long.bwe_declip_prepare(None, torch.ones(9), "firwin_hpf"), L, end, 8, None)
     assert np.array_equal(levels, np.array([0.1, 0.2, 0.3], dtype=np.float32)) and mask.shape == (3, N)
     assert len(calls) == 3
 

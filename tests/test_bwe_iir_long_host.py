@@ -265,9 +265,9 @@ def test_every_refusal_is_raised_before_any_launch_and_in_order(monkeypatch):
     with pytest.raises(_lib.AidError, match="rid"):
         _stub_sampler(rid=True)[0].predict_bwe_iir_long(y, filt, "cheby1")
     with pytest.raises(_lib.AidError, match="seeds"):
-        bwe_iir_long.check_bwe_iir_args(y, filt, "cheby1", L, end, 8, [1])
+        bwe_iir_long.check_bwe_iir_args(y, bwe_iir_long.bwe_iir_prepare(None, filt, "cheby1"), L, end, 8, [1])
     with pytest.raises(_lib.AidError, match="GPU only"):
-        bwe_iir_long.check_bwe_iir_args(y, filt, "cheby1", L, end, 8, [1, 2])
+        bwe_iir_long.check_bwe_iir_args(y, bwe_iir_long.bwe_iir_prepare(None, filt, "cheby1"), L, end, 8, [1, 2])
     assert launched == [] and smp.seeds == [5] and smp.y is None and smp.spectral is None and smp.n_evals == 0
     # the FIR mode still refuses an IIR filter, in one sentence that names the new method
     with pytest.raises(_lib.AidError, match="IIR filter carries state") as e:

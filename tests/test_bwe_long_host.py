@@ -173,9 +173,9 @@ def test_every_refusal_is_raised_before_any_launch(monkeypatch):
             _stub_sampler(overlap=ov)[0].predict_bwe_long(y, taps, "firwin")
     # the device of y is judged last: a host y with any other fault is refused for that fault
     with pytest.raises(_lib.AidError, match="seeds"):
-        bwe_long.check_bwe_args(y, taps, "firwin", L, end, 8, [1])
+        bwe_long.check_bwe_args(y, bwe_long.bwe_prepare(None, taps, "firwin"), L, end, 8, [1])
     with pytest.raises(_lib.AidError, match="GPU only"):
-        bwe_long.check_bwe_args(y, taps, "firwin", L, end, 8, [1, 2])
+        bwe_long.check_bwe_args(y, bwe_long.bwe_prepare(None, taps, "firwin"), L, end, 8, [1, 2])
     assert launched == [] and smp.seeds == [5] and smp.y is None and smp.spectral is None and smp.n_evals == 0
 
 

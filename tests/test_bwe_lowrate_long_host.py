@@ -244,8 +244,8 @@ def test_every_refusal_is_raised_before_any_launch(monkeypatch):
     refused(r"2 \(K - 1\)", lambda: _stub_sampler(overlap=0.01)[0].predict_bwe_lowrate_long(y, 1.47))     # end' < 328, more than one window
     refused("GPU only", lambda: _stub_sampler(overlap=0.01)[0].predict_bwe_lowrate_long(y[:, :100], 1.47))   # one window: any K (refused for the device alone)
     # the device of y is judged last: a host y with any other fault is refused for that fault
-    refused("seeds", lambda: lowrate_long.check_lowrate_args(y, 2, "resample", None, L, end, 8, [1]))
-    refused("GPU only", lambda: lowrate_long.check_lowrate_args(y, 2, "resample", None, L, end, 8, [1, 2]))
+    refused("seeds", lambda: lowrate_long.check_lowrate_args(y, None, lowrate_long.rate_of(2, "resample"), L, end, 8, [1]))
+    refused("GPU only", lambda: lowrate_long.check_lowrate_args(y, None, lowrate_long.rate_of(2, "resample"), L, end, 8, [1, 2]))
     assert all(s.count(". ") == 0 and not s.rstrip().endswith(".") for s in sentences), [s for s in sentences if s.count(". ")]    # one sentence each
     assert launched == [] and smp.seeds == [5] and smp.y is None and smp.spectral is None and smp.n_evals == 0
 

@@ -1,4 +1,5 @@
-"""Host tests of what the whole-recording modes share (restore.py): the max_batch refusal of the six Sampler.predict_*_long methods and
+"""Host tests of what the whole-recording modes share (restore.py): the max_batch refusal of Sampler.predict_*_long, mode by mode (the
+refusals of the seven pooled modes side by side: test_long_tasks_host.py), and
 ``rows(lo, hi)`` of the base class of the window operators.  No GPU."""
 import pytest
 import torch

@@ -187,8 +187,8 @@ def test_every_refusal_is_raised_before_any_launch(monkeypatch):
     refused(r"2 \(K - 1\) = 510", lambda: _stub_sampler(overlap=0.1)[0].predict_pr_long(y))                 # end' < 510, more than one window
     refused("GPU only", lambda: _stub_sampler(overlap=0.1)[0].predict_pr_long(y[:, :, :1 + L // hop], length=L))      # one window: any n_fft (refused for the device alone)
     # the device of y is judged last: a host y with any other fault is refused for that fault
-    refused("seeds", lambda: phase_long.check_pr_args(y, win, hop, None, L, end, 8, [1]))
-    refused("GPU only", lambda: phase_long.check_pr_args(y, win, hop, None, L, end, 8, [1, 2]))
+    refused("seeds", lambda: phase_long.check_pr_args(y, None, phase_long.phase.check_sizes(win, hop), L, end, 8, [1]))
+    refused("GPU only", lambda: phase_long.check_pr_args(y, None, phase_long.phase.check_sizes(win, hop), L, end, 8, [1, 2]))
     assert all(s.count(". ") == 0 and not s.rstrip().endswith(".") for s in sentences), [s for s in sentences if s.count(". ")]    # one sentence each
     assert launched == [] and smp.seeds == [5] and smp.y is None and smp.spectral is None and smp.n_evals == 0
 
