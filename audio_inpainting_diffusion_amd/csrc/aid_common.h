@@ -8,6 +8,7 @@
 
 void aid_set_error(const char* msg);
 void aid_note_kernel(const char* name);   // aid_capi.hip: records which device kernel an entry point dispatched to
+const float* aid_zero_page();             // aid_capi.hip: 256 bytes of zeros in device memory; nullptr with the error set when the lookup fails
 
 // Checks the launch that just happened; returns AID_E_LAUNCH from the enclosing function on failure.
 #define AID_CHECK_LAUNCH()                                   \

@@ -16,21 +16,18 @@
 //   MFMA: v_mfma_f32_32x32x2_f32, A = W[32 cout][2 ci], B = X[2 ci][32 t]; both operands are conflict-free
 //   ds_read_b32 (lanes 0-31 consecutive floats; the two half-waves read different ci).
 //   Epilogue (registers -> global): y = alpha * (res_scale*res + acc*out_scale[b,co])  or the dGELU form (epi=1).
+//   Geometry record, tile origin, row table and that epilogue are the shared frame of aid_conv_tile.h (the direct-to-LDS
+//   kernels use the same); the split-K store of raw partial sums stays here, in front of it.
 //
 //   fp32 MFMA is exact fp32 FMA arithmetic (cdna_hip_programming.md section 3), so parity with the reference's
 //   F.conv2d is limited only by summation order.
-#include "aid_common.h"
-#include "aid_mfma_dma.h"
+#include "aid_conv_tile.h"
 #include "aid_conv1x1_plan.h"
 #include <stdlib.h>
 
 struct ConvDev {
     aid_conv2d_params p;
-    int tt_log2;      // log2(TT)
-    int rows_log2;    // log2(ROWS)
-    int tiles_t;      // ceil(T / TT)
-    int nrows;        // B*F
-    int nchunks;      // ceil(Cin / KC)
+    ConvTileGeo g;    // plain 2-D grid (per_xcd = 0)
     int splits, cps;  // split-K: blockIdx.z owns chunks [z*cps, min(nchunks, (z+1)*cps)); splits = 1: whole K, normal epilogue
     float* ws;        // [splits][B][Cout][F][T] partial sums when splits > 1
 };
@@ -61,8 +58,8 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_mfma_kernel(const ConvDev
     static_assert(KSTEPS % NSLOT == 0 && NSLOT >= 2, "k-steps must split evenly into >= 2 slots");
 
     const aid_conv2d_params& p = a.p;
-    const int TT = 1 << a.tt_log2;
-    const int ROWS = 1 << a.rows_log2;
+    const int TT = 1 << a.g.tt_log2;
+    const int ROWS = 1 << a.g.rows_log2;
     const int TTP = TT + 2 * PADL;
     const int XSZ = KC * ROWS * KH * TTP;
     constexpr int WSZ = TAPS * KC * M_BLK;
@@ -77,23 +74,13 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_mfma_kernel(const ConvDev
     const int wm = wave / WGN;
     const int wn = wave % WGN;
 
-    const int tile_t = blockIdx.x % a.tiles_t;
-    const int rg = blockIdx.x / a.tiles_t;
-    const int row0 = rg << a.rows_log2;
-    const int t0 = tile_t << a.tt_log2;
-    const int m0 = blockIdx.y * M_BLK;
-
-    for (int r = tid; r < ROWS; r += NTHREADS) {
-        const int rid = row0 + r;
-        int b = -1, f = 0;
-        if (rid < a.nrows) { b = rid / p.F; f = rid - b * p.F; }
-        rowinfo[2 * r] = b;
-        rowinfo[2 * r + 1] = f;
-    }
-    __syncthreads();
+    ConvTileOrigin o;
+    if (!conv_tile_origin<M_BLK>(a.g, o)) return;
+    conv_tile_rows<NTHREADS>(a.g, p.F, o.row0, rowinfo);
+    const int t0 = o.t0, m0 = o.m0;
 
     // ---- per-thread staging descriptors (constant over the K loop) ------------------------------------------
-    const int tq_log2 = a.tt_log2 - 2;
+    const int tq_log2 = a.g.tt_log2 - 2;
     int64_t xg[XQ];      // global element offset without the channel term, -1 = out of range
     int xlds[XQ];        // LDS float offset inside the X tile
     int xci[XQ];         // channel within the chunk
@@ -106,7 +93,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_mfma_kernel(const ConvDev
         const int kh = s % KH;
         const int s2 = s / KH;
         const int rr = s2 & (ROWS - 1);
-        const int ci = s2 >> a.rows_log2;
+        const int ci = s2 >> a.g.rows_log2;
         const int b = rowinfo[2 * rr];
         const int fi = rowinfo[2 * rr + 1] + (kh - KH / 2) * p.dilF;
         const int t = t0 + 4 * tq;
@@ -129,7 +116,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_mfma_kernel(const ConvDev
             const int kh = s % KH;
             const int s2 = s / KH;
             const int rr = s2 & (ROWS - 1);
-            const int ci = s2 >> a.rows_log2;
+            const int ci = s2 >> a.g.rows_log2;
             const int b = rowinfo[2 * rr];
             const int fi = rowinfo[2 * rr + 1] + (kh - KH / 2) * p.dilF;
             const int t = side ? (t0 + TT) : (t0 - 1);
@@ -159,7 +146,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_mfma_kernel(const ConvDev
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
         const int n = (wn * NT + j) * 32 + (lane & 31);
-        const int rr = n >> a.tt_log2;
+        const int rr = n >> a.g.tt_log2;
         const int tt = n & (TT - 1);
         xoff[j] = rr * KH * TTP + tt + XOFF;
     }
@@ -225,7 +212,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_mfma_kernel(const ConvDev
             const int kh = s % KH;
             const int s2 = s / KH;
             const int rr = s2 & (ROWS - 1);
-            const int ci = s2 >> a.rows_log2;
+            const int ci = s2 >> a.g.rows_log2;
             const int b = rowinfo[2 * rr];
             const int fi = rowinfo[2 * rr + 1] + (kh - KH / 2) * p.dilF;
             const int t = side ? (t0 + TT) : (t0 - 1);
@@ -242,7 +229,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_mfma_kernel(const ConvDev
 
     // ---- prologue: first chunk of this workgroup's K range -> buffer 0 ------------------------------------------------
     const int cb = (int)blockIdx.z * a.cps;
-    const int nloc = (a.nchunks - cb < a.cps) ? (a.nchunks - cb) : a.cps;
+    const int nloc = (a.g.nchunks - cb < a.cps) ? (a.g.nchunks - cb) : a.cps;
     issue_loads(cb * KC);
     write_slot(smem, smem + XSZ, -1);
     if (KW > 1 && !halo_fast) halo_slow(smem, cb * KC);
@@ -301,57 +288,23 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_mfma_kernel(const ConvDev
     }
 
     // ---- epilogue --------------------------------------------------------------------------------------------
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        const int n = (wn * NT + j) * 32 + (lane & 31);
-        const int rr = n >> a.tt_log2;
-        const int tt = n & (TT - 1);
-        const int b = rowinfo[2 * rr];
-        const int f = rowinfo[2 * rr + 1];
-        const int t = t0 + tt;
-        if (b < 0 || t >= p.T) continue;
-        if (a.splits > 1) {                              // split-K: raw partial sums, reduced by conv_splitk_reduce_kernel
-            const int64_t ft = (int64_t)p.F * p.T;
-            float* wsb = a.ws + (((int64_t)blockIdx.z * p.B + b) * p.Cout) * ft + (int64_t)f * p.T + t;
-#pragma unroll
-            for (int i = 0; i < MT; ++i) {
-                const int mbase = m0 + (wm * MT + i) * 32 + 4 * (lane >> 5);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int m = mbase + (r & 3) + 8 * (r >> 2);
-                    if (m < p.Cout) wsb[(int64_t)m * ft] = acc[i][j][r];
-                }
-            }
-            continue;
-        }
-        const int64_t ybase = (int64_t)b * p.y.sB + (int64_t)f * p.y.sF + t;
-        const int64_t rbase = p.res.p ? ((int64_t)b * p.res.sB + (int64_t)f * p.res.sF + t) : 0;
-        const int64_t abase = p.aux.p ? ((int64_t)b * p.aux.sB + (int64_t)f * p.aux.sF + t) : 0;
+    // split-K: raw partial sums of position tile j, reduced by conv_splitk_reduce_kernel
+    auto splitk_store = [&](int j, int b, int f, int t) {
+        if (a.splits <= 1) return false;
+        const int64_t ft = (int64_t)p.F * p.T;
+        float* wsb = a.ws + (((int64_t)blockIdx.z * p.B + b) * p.Cout) * ft + (int64_t)f * p.T + t;
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
-            // gather phase first (res / aux / gate), then compute + store: res may alias y (gradient accumulation),
-            // so the compiler would otherwise serialise load -> store element by element (16 dependent round trips)
-            float rv[16], uv[16], sv[16];
             const int mbase = m0 + (wm * MT + i) * 32 + 4 * (lane >> 5);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int m = mbase + (r & 3) + 8 * (r >> 2);
-                const bool ok = m < p.Cout;
-                rv[r] = (ok && p.res.p) ? p.res.p[rbase + (int64_t)m * p.res.sC] : 0.f;
-                sv[r] = (ok && p.out_scale) ? p.out_scale[(int64_t)b * p.out_scale_ld + m] : 1.f;
-                uv[r] = (ok && p.epi == 1) ? p.aux.p[abase + (int64_t)m * p.aux.sC] * p.aux_scale[(int64_t)b * p.aux_scale_ld + m] : 0.f;
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = mbase + (r & 3) + 8 * (r >> 2);
-                if (m >= p.Cout) continue;
-                float v = acc[i][j][r] * sv[r];
-                if (p.epi == 1) v *= aid_dgelu(uv[r]);
-                v += p.res_scale * rv[r];
-                p.y.p[ybase + (int64_t)m * p.y.sC] = p.alpha * v;
+                if (m < p.Cout) wsb[(int64_t)m * ft] = acc[i][j][r];
             }
         }
-    }
+        return true;
+    };
+    conv_tile_epilogue<MT, NT, WGM, WGN>(p, a.g, o, rowinfo, wave, acc, splitk_store);
 }
 
 // y = alpha * (res_scale*res + out_scale * sum_z ws[z])  -- fixed summation order: deterministic
@@ -404,20 +357,13 @@ static int launch_cfg(const aid_conv2d_params* p, hipStream_t st, int splits = 1
     constexpr int N_BLK = 32 * NT * WGN;
     ConvDev a;
     a.p = *p;
-    int TT = aid_pow2ceil(p->T);
-    if (TT > N_BLK) TT = N_BLK;
-    if (TT < 4) TT = 4;
-    a.tt_log2 = aid_ilog2(TT);
-    const int ROWS = N_BLK / TT;
-    a.rows_log2 = aid_ilog2(ROWS);
-    a.tiles_t = aid_cdiv(p->T, TT);
-    a.nrows = p->B * p->F;
-    a.nchunks = aid_cdiv(p->Cin, KC);
-    a.cps = aid_cdiv(a.nchunks, splits);
-    a.splits = aid_cdiv(a.nchunks, a.cps);               // (no empty K ranges)
+    dim3 grid;
+    (void)conv_tile_geo(&a.g, &grid, p, N_BLK, M_BLK, KC, N_BLK, 4, false);      // TT >= 4; no row limit (the row table is dynamic LDS)
+    const int TT = 1 << a.g.tt_log2, ROWS = 1 << a.g.rows_log2;
+    a.cps = aid_cdiv(a.g.nchunks, splits);
+    a.splits = aid_cdiv(a.g.nchunks, a.cps);             // (no empty K ranges)
     a.ws = p->ws;
-    const int rgroups = aid_cdiv(a.nrows, ROWS);
-    dim3 grid((unsigned)(rgroups * a.tiles_t), (unsigned)(p->Cout_pad / M_BLK), (unsigned)a.splits);
+    grid.z = (unsigned)a.splits;
     const size_t lds = sizeof(float) * 2 * ((size_t)KC * ROWS * KH * (TT + (KW > 1 ? 8 : 0)) + (size_t)KH * KW * KC * M_BLK) +
                        sizeof(int) * 2 * ROWS;
     AID_REQUIRE(lds <= 160 * 1024, "aid_conv2d: LDS tile too large");

@@ -11,8 +11,9 @@
 //   * a lane's NT = 2 position tiles are INTERLEAVED (tile j = positions 2n + j), so the B fragments of both tiles are ONE
 //     conflict-free ds_read_b64 and the epilogue stores float2.
 // Per-(b,ci) prologue scale (in_scale) is applied to the A fragment (a tile never straddles two samples: host-checked).
-#include "aid_common.h"
-#include "aid_mfma_dma.h"
+// Geometry record, tile origin (XCD-aware order) and row table are the shared frame of aid_conv_tile.h; the pieces (two K segments),
+// the K loop and the float2 epilogue are this kernel's own.
+#include "aid_conv_tile.h"
 #include "aid_conv1x1_plan.h"
 #include <type_traits>
 
@@ -22,14 +23,11 @@ bool aid_conv_splitk_scratch_ok(const aid_conv2d_params* p, int S);
 struct C11Dev {
     aid_conv2d_params p;
     const float* zero;
-    int tt_log2, rows_log2, tiles_t, nrows, nchunks;
-    int nx, ny, per_xcd;
+    ConvTileGeo g;             // XCD-aware 1-D grid (x); blockIdx.y is the K split
     int nch1;                  // chunks served by p.x (all of them unless p.x2 is given: then chunks >= nch1 read channels of p.x2)
     int splits, cps;           // split-K (grid-starved GEMMs: the qk projections, N = B*T columns only): blockIdx.y walks `splits` ranges of
     float* ws;                 // `cps` chunks; raw partial sums go to ws[z][B][Cout][F][T], reduced in a fixed order by aid_conv_splitk_reduce
 };
-
-__device__ float4 g_aid_zero_page_c11[16];
 
 // MT m-tiles (32 cout) x 2 interleaved position tiles per wave; WGM x WGN waves; N_BLK = 64 * WGN positions
 template <int MT, int WGM, int WGN, int RMAX, int KC, int MINW>
@@ -51,8 +49,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv11_dma_kernel(const 
     static_assert(N_BLK % 256 == 0 && WSZ % 256 == 0, "whole 1-KiB pieces");
 
     const aid_conv2d_params& p = a.p;
-    const int TT = 1 << a.tt_log2;
-    const int ROWS = 1 << a.rows_log2;
+    const int TT = 1 << a.g.tt_log2;
 
     __shared__ __attribute__((aligned(16))) float sbuf0[BUFSZ];
     __shared__ __attribute__((aligned(16))) float sbuf1[BUFSZ];
@@ -64,25 +61,10 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv11_dma_kernel(const 
     const int wm = wave / WGN;
     const int wn = wave % WGN;
 
-    // XCD-aware tile order (see conv53_wino4_kernel): one contiguous (row-group, Cout-tile) range per XCD, Cout tile fastest
-    const int Lt = (blockIdx.x & 7) * a.per_xcd + (blockIdx.x >> 3);
-    if (Lt >= a.nx * a.ny) return;
-    const int bx = Lt / a.ny;
-    const int by = Lt - bx * a.ny;
-    const int tile_t = bx % a.tiles_t;
-    const int rg = bx / a.tiles_t;
-    const int row0 = rg << a.rows_log2;
-    const int t0 = tile_t << a.tt_log2;
-    const int m0 = by * M_BLK;
-
-    for (int r = tid; r < ROWS; r += NTHREADS) {
-        const int rid = row0 + r;
-        int b = -1, f = 0;
-        if (rid < a.nrows) { b = rid / p.F; f = rid - b * p.F; }
-        rowinfo[2 * r] = b;
-        rowinfo[2 * r + 1] = f;
-    }
-    __syncthreads();
+    ConvTileOrigin o;                                    // XCD-aware tile order: one contiguous (row-group, Cout-tile) range per XCD, Cout tile fastest
+    if (!conv_tile_origin<M_BLK>(a.g, o)) return;
+    conv_tile_rows<NTHREADS>(a.g, p.F, o.row0, rowinfo);
+    const int tile_t = o.tile_t, row0 = o.row0, t0 = o.t0, m0 = o.m0;
 
     // ---- DMA piece descriptors ---------------------------------------------------------------------------------------
     const float* psrc[PPW];
@@ -96,7 +78,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv11_dma_kernel(const 
         if (pc < NXP) {
             const int ci = pc / (N_BLK / 256), sub = pc % (N_BLK / 256);
             const int n = sub * 256 + 4 * lane;
-            const int rr = n >> a.tt_log2, tt = n & (TT - 1);
+            const int rr = n >> a.g.tt_log2, tt = n & (TT - 1);
             const int b = rowinfo[2 * rr];
             const int f = rowinfo[2 * rr + 1];
             plds[i] = ci * N_BLK + sub * 256;
@@ -157,7 +139,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv11_dma_kernel(const 
     };
 
     const int ch_lo = blockIdx.y * a.cps;                            // this workgroup's K range (the whole K unless split)
-    const int ch_hi = min(a.nchunks, ch_lo + a.cps);
+    const int ch_hi = min(a.g.nchunks, ch_lo + a.cps);
     issue_dma(ch_lo, sbuf0);
     load_scales(ch_lo, 0);
     __syncthreads();
@@ -196,7 +178,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv11_dma_kernel(const 
 
     // ---- epilogue: two consecutive positions per lane and output channel ---------------------------------------------
     const int n = wn * 64 + 2 * (lane & 31);
-    const int rr = n >> a.tt_log2, tt = n & (TT - 1);
+    const int rr = n >> a.g.tt_log2, tt = n & (TT - 1);
     const int b = rowinfo[2 * rr];
     const int f = rowinfo[2 * rr + 1];
     const int t = t0 + tt;
@@ -289,7 +271,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv11_dma_kernel(const 
                             if (mrow < p.Cout && mrow / cpg == grp) sacc += red[((w * 2 + h) * MT + i) * 4 + q];
                         }
             const int bt = rowinfo[0];
-            const int ptile = ((row0 - bt * p.F) >> a.rows_log2) * a.tiles_t + tile_t;
+            const int ptile = ((row0 - bt * p.F) >> a.g.rows_log2) * a.g.tiles_t + tile_t;
             p.dot_ws[((int64_t)bt * 8 + grp) * p.dot_n + ptile] = (double)sacc;
         }
     }
@@ -297,28 +279,23 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv11_dma_kernel(const 
 
 template <int MT, int WGM, int WGN, int RMAX, int KC, int MINW>
 static int launch_c11(const aid_conv2d_params* p, hipStream_t st, const C11Plan& pl) {
-    static const float* zero = nullptr;
-    if (!zero) {
-        void* z = nullptr;
-        if (hipGetSymbolAddress(&z, HIP_SYMBOL(g_aid_zero_page_c11)) != hipSuccess) { aid_set_error("aid_conv2d: zero page lookup failed"); return AID_E_LAUNCH; }
-        zero = (const float*)z;
-    }
     C11Dev a;
     a.p = *p;
-    a.zero = zero;
-    a.tt_log2 = aid_ilog2(pl.TT);
-    a.rows_log2 = aid_ilog2(pl.ROWS);
-    a.tiles_t = pl.tiles_t;
-    a.nrows = pl.nrows;
-    a.nchunks = pl.nchunks;
+    a.zero = aid_zero_page();
+    if (!a.zero) return AID_E_LAUNCH;
+    a.g.tt_log2 = aid_ilog2(pl.TT);
+    a.g.rows_log2 = aid_ilog2(pl.ROWS);
+    a.g.tiles_t = pl.tiles_t;
+    a.g.nrows = pl.nrows;
+    a.g.nchunks = pl.nchunks;
     a.nch1 = pl.nch1;
-    a.nx = pl.nx;
-    a.ny = pl.ny;
-    a.per_xcd = (int)(((int64_t)a.nx * a.ny + 7) / 8);
+    a.g.nx = pl.nx;
+    a.g.ny = pl.ny;
+    a.g.per_xcd = (int)(((int64_t)a.g.nx * a.g.ny + 7) / 8);
     a.cps = pl.kps / KC;
-    a.splits = aid_cdiv(a.nchunks, a.cps);
+    a.splits = aid_cdiv(a.g.nchunks, a.cps);
     a.ws = (float*)p->ws;
-    hipLaunchKernelGGL((conv11_dma_kernel<MT, WGM, WGN, RMAX, KC, MINW>), dim3((unsigned)(8 * a.per_xcd), (unsigned)a.splits), dim3(64 * WGM * WGN), 0, st, a);
+    hipLaunchKernelGGL((conv11_dma_kernel<MT, WGM, WGN, RMAX, KC, MINW>), dim3((unsigned)(8 * a.g.per_xcd), (unsigned)a.splits), dim3(64 * WGM * WGN), 0, st, a);
     AID_CHECK_LAUNCH();
     aid_note_kernel(a.splits > 1 ? "conv11_dma_kernel+splitk" : "conv11_dma_kernel");
     if (a.splits > 1) return aid_conv_splitk_reduce(p, (const float*)p->ws, a.splits, st);

@@ -11,12 +11,14 @@
 //   conv53_wino8r_kernel : F(8,3) on the same row-shared body (wino4r_tile_body<..., WM = 8>): 64 x 512 tiles, 160 accumulators per lane -- the dominant kernel
 //   conv53_wino8r_ks_kernel : its K-group instance for launches of at most one tile per CU (small batches): eight waves on one tile, two K groups, sum through LDS
 //   conv53_wino4r_ks_kernel : the same for F(4,3) on the T <= 32 tile shapes
+// The two older kernels (conv53_wino4_kernel, conv53_wino4v_kernel) stand on the shared tile frame of aid_conv_tile.h: geometry record, tile origin in
+// the XCD-aware order, row table, weight-piece descriptors and the F(4,3) epilogue (wino4_tile_epilogue); conv53_wino4_kernel also takes its x pieces,
+// halos and issue_dma / write_halo from there (ConvTileStage, as conv53_dma_kernel).  Their K loops, LDS buffers and operand addresses are here.
 // The four row-shared kernels are entries over wino4r_tile_body (AID_W4R_ENTRY: one family, or the 64 + 32 pair of a 96-channel layer in one grid).
 // Host side: the tile geometry of a row-shared launch is ONE WinoRPlan (aid_wino_plan.h); launch_wino_r() launches from it, and wino_form_choice() /
 // aid_conv2d_wino_form() (which form takes a launch), the K-group and split-K rules and the aid_conv2d_* host queries (fin_mode support, split-K
 // scratch, statistics and dot partial counts) read the same plan.
-#include "aid_common.h"
-#include "aid_mfma_dma.h"
+#include "aid_conv_tile.h"
 #include "aid_wino8.h"
 #include "aid_fin.h"
 #include "aid_wino_plan.h"
@@ -26,11 +28,8 @@
 struct ConvWinoDev {
     aid_conv2d_params p;
     const float* zero;
-    int tt_log2, rows_log2, tiles_t, nrows, nchunks;
-    int nx, ny, per_xcd;      // F(4,3) kernel: 1-D grid of 8*per_xcd workgroups, swizzled per XCD (see the kernel); per_xcd = 0: plain 2-D grid
+    ConvTileGeo g;            // 1-D grid of 8*per_xcd workgroups in the XCD-aware order (conv_tile_origin)
 };
-
-__device__ float4 g_aid_zero_page_w[16];   // (device symbols are per translation unit without -fgpu-rdc)
 
 // ---- F(4,3): 6 products per 4 outputs (2x fewer MFMAs than direct).  tau now indexes GROUPS of 4 output samples:
 //   V = B^T d (d = 6 samples 4g-1 .. 4g+4):  V0 = 4d0-5d2+d4, V1 = (d3+d4)-4(d1+d2), V2 = (d4-d3)+4(d1-d2),
@@ -43,27 +42,14 @@ template <int MT, int NTT, int WGM, int WGN, int RMAX, int KC, int MINW>
 __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv53_wino4_kernel(const ConvWinoDev a) {
     constexpr int KH = 5, NXI = 6, TAPS = NXI * KH;     // 30 transformed taps
     constexpr int NW = WGM * WGN;
-    constexpr int NTHREADS = 64 * NW;
     constexpr int M_BLK = 32 * MT * WGM;
     constexpr int N_BLK = 128 * NTT * WGN;              // output samples per tile
-    constexpr int HALO = 2 * RMAX;
-    constexpr int XB = N_BLK + HALO;
-    constexpr int XSZ = KC * KH * XB;
-    constexpr int WROW = (M_BLK % 64 == 0) ? M_BLK : ((M_BLK + 63) / 64) * 64;
-    constexpr int WSZ_RAW = TAPS * KC * WROW;
-    constexpr int WSZ = ((WSZ_RAW + 255) / 256) * 256;
-    constexpr int BUFSZ = XSZ + WSZ;
-    constexpr int NXP = KC * KH * (N_BLK / 256);
-    constexpr int NWP = WSZ / 256;
-    constexpr int NP = NXP + NWP;
-    constexpr int PPW = (NP + NW - 1) / NW;
-    constexpr int HQ = (2 * KC * KH * RMAX + NTHREADS - 1) / NTHREADS;
+    using Stage = ConvTileStage<TAPS, KC, M_BLK, N_BLK, RMAX, NW>;     // the LDS image of a buffer and its DMA pieces, as conv53_dma_kernel (aid_conv_tile.h)
+    constexpr int XB = Stage::XB, XSZ = Stage::XSZ, WROW = Stage::WROW, BUFSZ = Stage::BUFSZ;
     constexpr int NSTEP = KH * (KC / 2);                // (kh, ci-pair) steps per chunk, 4*MT*NTT MFMAs each
-    static_assert(N_BLK % 256 == 0, "x tile must be whole 1-KiB pieces");
 
     const aid_conv2d_params& p = a.p;
-    const int TT = 1 << a.tt_log2;
-    const int ROWS = 1 << a.rows_log2;
+    const int TT = 1 << a.g.tt_log2;
 
     // Two STATIC buffers (not one dynamic array): distinct LDS objects carry alias scopes after LDS lowering, so the
     // waitcnt pass knows the ds_reads of chunk c cannot touch the buffer the direct-to-LDS loads of chunk c+1 write,
@@ -79,87 +65,15 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv53_wino4_kernel(cons
     const int wm = wave / WGN;
     const int wn = wave % WGN;
 
-    // XCD-aware tile order.  Hardware deals consecutive workgroup ids round-robin to the 8 XCDs (each with its own L2).
-    // Logical tile L = xcd * per_xcd + (id / 8): every XCD walks ONE contiguous range of (row-group, m-tile) pairs, m-tile
-    // fastest, so the Cout tiles of the same activations and the row groups that share dilated rows meet in the same L2.
-    int bx = blockIdx.x, by = blockIdx.y;
-    if (a.per_xcd > 0) {
-        const int Lt = (blockIdx.x & 7) * a.per_xcd + (blockIdx.x >> 3);
-        if (Lt >= a.nx * a.ny) return;
-        bx = Lt / a.ny;
-        by = Lt - bx * a.ny;
-    }
-    const int tile_t = bx % a.tiles_t;
-    const int rg = bx / a.tiles_t;
-    const int row0 = rg << a.rows_log2;
-    const int t0 = tile_t << a.tt_log2;
-    const int m0 = by * M_BLK;
+    ConvTileOrigin o;
+    if (!conv_tile_origin<M_BLK>(a.g, o)) return;
+    conv_tile_rows<64 * NW>(a.g, p.F, o.row0, rowinfo);
 
-    for (int r = tid; r < ROWS; r += NTHREADS) {
-        const int rid = row0 + r;
-        int b = -1, f = 0;
-        if (rid < a.nrows) { b = rid / p.F; f = rid - b * p.F; }
-        rowinfo[2 * r] = b;
-        rowinfo[2 * r + 1] = f;
-    }
-    __syncthreads();
-
-    // ---- DMA piece descriptors (identical scheme to conv53_dma_kernel; weights use the 20-tap Winograd pack) ----
-    const float* psrc[PPW];
-    int pstride[PPW], plds[PPW];
-#pragma unroll
-    for (int i = 0; i < PPW; ++i) {
-        const int pc = wave + i * NW;
-        psrc[i] = a.zero; pstride[i] = 0; plds[i] = -1;
-        if (pc < NXP) {
-            const int blk = pc / (N_BLK / 256), sub = pc % (N_BLK / 256);
-            const int ci = blk / KH, kh = blk % KH;
-            const int n = sub * 256 + 4 * lane;
-            const int rr = n >> a.tt_log2, tt = n & (TT - 1);
-            const int b = rowinfo[2 * rr];
-            const int fi = rowinfo[2 * rr + 1] + (kh - KH / 2) * p.dilF;
-            plds[i] = blk * XB + sub * 256;
-            if (b >= 0 && fi >= 0 && fi < p.F && t0 + tt < p.T) {
-                psrc[i] = p.x.p + (int64_t)b * p.x.sB + (int64_t)ci * p.x.sC + (int64_t)fi * p.x.sF + t0 + tt;
-                pstride[i] = (int)(KC * p.x.sC);
-            }
-        } else if (pc < NP) {
-            const int wp_ = pc - NXP;
-            const int e = wp_ * 256 + 4 * lane;
-            const int row = e / WROW, col = e % WROW;
-            const int tap = row / KC, ci = row % KC;
-            plds[i] = XSZ + wp_ * 256;
-            if (col < M_BLK && e < WSZ_RAW) {
-                psrc[i] = p.wp_wino + ((int64_t)tap * p.Cin_pad + ci) * p.Cout_pad + m0 + col;
-                pstride[i] = KC * p.Cout_pad;
-            }
-        }
-    }
-    const int nhalo = 2 * KC * KH * ROWS;
-    const float* hsrc[HQ];
-    int hstride[HQ], hlds[HQ];
-#pragma unroll
-    for (int i = 0; i < HQ; ++i) {
-        const int h = tid + i * NTHREADS;
-        hsrc[i] = a.zero; hstride[i] = 0; hlds[i] = -1;
-        if (h < nhalo) {
-            const int side = h & 1;
-            const int rr = (h >> 1) & (ROWS - 1);
-            const int blk = (h >> 1) >> a.rows_log2;
-            const int ci = blk / KH, kh = blk % KH;
-            const int b = rowinfo[2 * rr];
-            const int fi = rowinfo[2 * rr + 1] + (kh - KH / 2) * p.dilF;
-            const int t = side ? (t0 + TT) : (t0 - 1);
-            hlds[i] = blk * XB + N_BLK + rr * 2 + side;
-            if (b >= 0 && fi >= 0 && fi < p.F && t >= 0 && t < p.T) {
-                hsrc[i] = p.x.p + (int64_t)b * p.x.sB + (int64_t)ci * p.x.sC + (int64_t)fi * p.x.sF + t;
-                hstride[i] = (int)(KC * p.x.sC);
-            }
-        }
-    }
+    Stage st;                                            // piece and halo descriptors; the weights come from the 30-tap Winograd pack
+    st.init(p, p.wp_wino, a.zero, a.g, rowinfo, o.t0, o.m0, wave);
     // ---- operand addresses -----------------------------------------------------------------------------------------
     const int half = lane >> 5;
-    const int ttau_log2 = a.tt_log2 - 2;                 // groups per row = TT/4
+    const int ttau_log2 = a.g.tt_log2 - 2;                 // groups per row = TT/4
     int vD0[NTT], vD12[NTT], vD3[NTT];                   // float offsets of d0 | (d1..d4) | d5 inside a (ci,kh) block
 #pragma unroll
     for (int j = 0; j < NTT; ++j) {
@@ -184,34 +98,16 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv53_wino4_kernel(cons
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[i][j][x][r] = 0.f;
 
-    float hv[HQ];
-    auto issue_dma = [&](int ch, float* buf) {
-#pragma unroll
-        for (int i = 0; i < PPW; ++i) {
-            if (plds[i] >= 0) {
-                const float* src = psrc[i] + (int64_t)ch * pstride[i];
-                AID_GLDS16(src, buf + plds[i]);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < HQ; ++i) hv[i] = hsrc[i][(int64_t)ch * hstride[i]];
-    };
-    auto write_halo = [&](float* buf) {
-#pragma unroll
-        for (int i = 0; i < HQ; ++i)
-            if (hlds[i] >= 0) buf[hlds[i]] = hv[i];
-    };
-
-    issue_dma(0, sbuf0);
-    write_halo(sbuf0);
+    st.issue_dma(0, sbuf0);
+    st.write_halo(sbuf0);
     __syncthreads();
 
     auto chunk = [&](auto curc, int ch) {
         constexpr int cur = decltype(curc)::value;
         const float* Bf = cur ? sbuf1 : sbuf0;
         float* Nx = cur ? sbuf0 : sbuf1;
-        const bool more = (ch + 1) < a.nchunks;
-        if (more) issue_dma(ch + 1, Nx);
+        const bool more = (ch + 1) < a.g.nchunks;
+        if (more) st.issue_dma(ch + 1, Nx);
         // raw samples of step s+1 are fetched while the MFMAs of step s run
         float d0[2][NTT], d3[2][NTT];
         float4 d12[2][NTT];
@@ -253,107 +149,16 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv53_wino4_kernel(cons
                         acc[i][j][x] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[bq][i][x], V[x], acc[i][j][x], 0, 0, 0);
             }
         }
-        if (more) write_halo(Nx);
+        if (more) st.write_halo(Nx);
         __syncthreads();
     };
-    for (int ch = 0; ch < a.nchunks; ch += 2) {
+    for (int ch = 0; ch < a.g.nchunks; ch += 2) {
         chunk(std::integral_constant<int, 0>{}, ch);
-        if (ch + 1 < a.nchunks) chunk(std::integral_constant<int, 1>{}, ch + 1);
+        if (ch + 1 < a.g.nchunks) chunk(std::integral_constant<int, 1>{}, ch + 1);
     }
     __builtin_amdgcn_s_setprio(0);
 
-    // ---- epilogue: output transform, then gate / dGELU / residual, four samples per lane -------------------------------
-    float dsum[MT][4];                                   // <y, aux> per block of 4 rows (dot_ws)
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) dsum[i][q] = 0.f;
-#pragma unroll
-    for (int j = 0; j < NTT; ++j) {
-        const int nt = (wn * NTT + j) * 32 + (lane & 31);
-        const int rr = nt >> ttau_log2, tau = nt & ((TT >> 2) - 1);
-        const int b = rowinfo[2 * rr];
-        const int f = rowinfo[2 * rr + 1];
-        const int t = t0 + 4 * tau;
-        if (b < 0 || t >= p.T) continue;                 // T % 4 == 0: the four samples are in range together
-        const int64_t ybase = (int64_t)b * p.y.sB + (int64_t)f * p.y.sF + t;
-        const int64_t rbase = p.res.p ? ((int64_t)b * p.res.sB + (int64_t)f * p.res.sF + t) : 0;
-        const int64_t abase = p.aux.p ? ((int64_t)b * p.aux.sB + (int64_t)f * p.aux.sF + t) : 0;
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-            const int mbase = m0 + (wm * MT + i) * 32 + 4 * (lane >> 5);
-#pragma unroll
-            for (int r0 = 0; r0 < 16; r0 += 4) {         // batches of 4 rows: gather, then compute + store
-                float4 rv[4], ur[4];                      // residual, raw aux (scaled by `as` when the dGELU is evaluated)
-                float sv[4], as[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int r = r0 + q;
-                    const int m = mbase + (r & 3) + 8 * (r >> 2);
-                    const bool ok = m < p.Cout;
-                    rv[q] = (ok && p.res.p) ? *reinterpret_cast<const float4*>(p.res.p + rbase + (int64_t)m * p.res.sC) : make_float4(0.f, 0.f, 0.f, 0.f);
-                    sv[q] = (ok && p.out_scale) ? p.out_scale[(int64_t)b * p.out_scale_ld + m] : 1.f;
-                    if (ok && p.epi == 1) {
-                        as[q] = p.aux_scale[(int64_t)b * p.aux_scale_ld + m];
-                        ur[q] = *reinterpret_cast<const float4*>(p.aux.p + abase + (int64_t)m * p.aux.sC);
-                    } else { as[q] = 0.f; ur[q] = make_float4(0.f, 0.f, 0.f, 0.f); }
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int r = r0 + q;
-                    const int m = mbase + (r & 3) + 8 * (r >> 2);
-                    if (m >= p.Cout) continue;
-                    const float M0 = acc[i][j][0][r], M1 = acc[i][j][1][r], M2 = acc[i][j][2][r], M3 = acc[i][j][3][r],
-                                M4 = acc[i][j][4][r], M5 = acc[i][j][5][r];
-                    const float a12 = M1 + M2, s12 = M1 - M2, a34 = M3 + M4, s34 = M3 - M4;
-                    float y0 = (M0 + a12 + a34) * sv[q];
-                    float y1 = (s12 + 2.f * s34) * sv[q];
-                    float y2 = (a12 + 4.f * a34) * sv[q];
-                    float y3 = (s12 + 8.f * s34 + M5) * sv[q];
-                    if (p.epi == 1) { y0 *= aid_dgelu(ur[q].x * as[q]); y1 *= aid_dgelu(ur[q].y * as[q]); y2 *= aid_dgelu(ur[q].z * as[q]); y3 *= aid_dgelu(ur[q].w * as[q]); }
-                    y0 += p.res_scale * rv[q].x; y1 += p.res_scale * rv[q].y; y2 += p.res_scale * rv[q].z; y3 += p.res_scale * rv[q].w;
-                    y0 *= p.alpha; y1 *= p.alpha; y2 *= p.alpha; y3 *= p.alpha;
-                    *reinterpret_cast<float4*>(p.y.p + ybase + (int64_t)m * p.y.sC) = make_float4(y0, y1, y2, y3);
-                    if (p.dot_ws) dsum[i][r0 >> 2] += (y0 * ur[q].x + y1 * ur[q].y) + (y2 * ur[q].z + y3 * ur[q].w);
-                }
-            }
-        }
-    }
-    // ---- optional: <y, aux> per (sample, channel group), one partial per tile (replaces the aid_group_dot pass) -----------
-    if (p.dot_ws) {
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float v = dsum[i][q];
-#pragma unroll
-                for (int off = 16; off >= 1; off >>= 1) v += __shfl_xor(v, off, 32);     // the 32 lanes of a half-wave share their rows
-                dsum[i][q] = v;
-            }
-        float* red = sbuf0;                              // (every wave is past the last chunk's barrier)
-        if ((lane & 31) == 0) {
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) red[((wave * 2 + half) * MT + i) * 4 + q] = dsum[i][q];
-        }
-        __syncthreads();
-        const int cpg = p.Cout >> 3;                     // channels per group (8 groups); M_BLK % cpg == 0 (host-checked)
-        const int g = m0 / cpg + tid;
-        if (tid < M_BLK / cpg && g < 8) {
-            float sacc = 0.f;
-            for (int w = 0; w < NW; ++w)                 // fixed order: deterministic
-                for (int h = 0; h < 2; ++h)
-                    for (int i = 0; i < MT; ++i)
-                        for (int q = 0; q < 4; ++q) {
-                            const int mrow = m0 + ((w / WGN) * MT + i) * 32 + 4 * h + 8 * q;
-                            if (mrow / cpg == g) sacc += red[((w * 2 + h) * MT + i) * 4 + q];
-                        }
-            const int b = rowinfo[0];
-            const int ptile = ((row0 - b * p.F) >> a.rows_log2) * a.tiles_t + tile_t;
-            p.dot_ws[((int64_t)b * 8 + g) * p.dot_n + ptile] = (double)sacc;
-        }
-    }
+    wino4_tile_epilogue<MT, NTT, WGM, WGN>(p, a.g, o, rowinfo, sbuf0, wave, acc);
 }
 
 // ---- F(4,3) with the input transform done by the producer (aid_scale_act(wino=1), x_wino = 1) -----------------------------
@@ -365,7 +170,6 @@ template <int MT, int NTT, int WGM, int WGN, int RMAX, int KC, int MINW>
 __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv53_wino4v_kernel(const ConvWinoDev a) {
     constexpr int KH = 5, NXI = 6, TAPS = NXI * KH;     // 30 transformed taps
     constexpr int NW = WGM * WGN;
-    constexpr int NTHREADS = 64 * NW;
     constexpr int M_BLK = 32 * MT * WGM;
     constexpr int N_BLK = 128 * NTT * WGN;              // output samples per tile
     constexpr int NG = N_BLK / 4;                       // groups of 4 outputs per tile = length of one V plane in LDS
@@ -383,8 +187,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv53_wino4v_kernel(con
     static_assert(XSZ % 256 == 0 && NG % 4 == 0, "whole 1-KiB pieces; a lane's 4 groups stay inside one plane");
 
     const aid_conv2d_params& p = a.p;
-    const int TT = 1 << a.tt_log2;
-    const int ROWS = 1 << a.rows_log2;
+    const int TT = 1 << a.g.tt_log2;
 
     // THREE static buffers and a SPREAD issue: the direct-to-LDS loads of chunk c+2 are issued one or two per k-step
     // while chunk c is multiplied.  Issuing a chunk's ~45 KiB of loads back to back at the top of a chunk (8 waves x 6
@@ -402,32 +205,12 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv53_wino4v_kernel(con
     const int wm = wave / WGN;
     const int wn = wave % WGN;
 
-    // XCD-aware tile order.  Hardware deals consecutive workgroup ids round-robin to the 8 XCDs (each with its own L2).
-    // Logical tile L = xcd * per_xcd + (id / 8): every XCD walks ONE contiguous range of (row-group, m-tile) pairs, m-tile
-    // fastest, so the Cout tiles of the same activations and the row groups that share dilated rows meet in the same L2.
-    int bx = blockIdx.x, by = blockIdx.y;
-    if (a.per_xcd > 0) {
-        const int Lt = (blockIdx.x & 7) * a.per_xcd + (blockIdx.x >> 3);
-        if (Lt >= a.nx * a.ny) return;
-        bx = Lt / a.ny;
-        by = Lt - bx * a.ny;
-    }
-    const int tile_t = bx % a.tiles_t;
-    const int rg = bx / a.tiles_t;
-    const int row0 = rg << a.rows_log2;
-    const int t0 = tile_t << a.tt_log2;
-    const int m0 = by * M_BLK;
+    ConvTileOrigin o;
+    if (!conv_tile_origin<M_BLK>(a.g, o)) return;
+    conv_tile_rows<64 * NW>(a.g, p.F, o.row0, rowinfo);
+    const int t0 = o.t0;
 
-    for (int r = tid; r < ROWS; r += NTHREADS) {
-        const int rid = row0 + r;
-        int b = -1, f = 0;
-        if (rid < a.nrows) { b = rid / p.F; f = rid - b * p.F; }
-        rowinfo[2 * r] = b;
-        rowinfo[2 * r + 1] = f;
-    }
-    __syncthreads();
-
-    // ---- DMA piece descriptors (identical scheme to conv53_dma_kernel; weights use the 20-tap Winograd pack) ----
+    // ---- DMA piece descriptors: x pieces of the Winograd-domain planes (this kernel's own), weight pieces of the 30-tap pack (shared) ----
     const float* psrc[PPW];
     int pstride[PPW], plds[PPW];
 #pragma unroll
@@ -439,7 +222,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv53_wino4v_kernel(con
             const int blk = eg / XB, e = eg % XB;
             const int ci = blk / KH, kh = blk % KH;
             const int xi = e / NG, gq = e % NG;
-            const int rr = gq >> (a.tt_log2 - 2), gl = gq & ((TT >> 2) - 1);
+            const int rr = gq >> (a.g.tt_log2 - 2), gl = gq & ((TT >> 2) - 1);
             const int b = rowinfo[2 * rr];
             const int fi = rowinfo[2 * rr + 1] + (kh - KH / 2) * p.dilF;
             plds[i] = pc * 256;
@@ -448,20 +231,12 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv53_wino4v_kernel(con
                 pstride[i] = (int)(KC * p.x.sC);
             }
         } else if (pc < NP) {
-            const int wp_ = pc - NXP;
-            const int e = wp_ * 256 + 4 * lane;
-            const int row = e / WROW, col = e % WROW;
-            const int tap = row / KC, ci = row % KC;
-            plds[i] = XSZ + wp_ * 256;
-            if (col < M_BLK && e < WSZ_RAW) {
-                psrc[i] = p.wp_wino + ((int64_t)tap * p.Cin_pad + ci) * p.Cout_pad + m0 + col;
-                pstride[i] = KC * p.Cout_pad;
-            }
+            plds[i] = XSZ + (pc - NXP) * 256;
+            conv_tile_wpiece<KC, M_BLK, WROW, WSZ_RAW>(p.wp_wino, p, o.m0, pc - NXP, lane, psrc[i], pstride[i]);
         }
     }
     // ---- operand addresses -----------------------------------------------------------------------------------------
     const int half = lane >> 5;
-    const int ttau_log2 = a.tt_log2 - 2;                 // groups per row = TT/4
     int vB[NTT];                                         // float offset of V[0][group] inside a (ci,kh) block
 #pragma unroll
     for (int j = 0; j < NTT; ++j) vB[j] = half * KH * XB + (wn * NTT + j) * 32 + (lane & 31);
@@ -498,7 +273,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv53_wino4v_kernel(con
     };
 
     issue_all(0, sbuf0);
-    if (a.nchunks > 1) issue_all(1, sbuf1);
+    if (a.g.nchunks > 1) issue_all(1, sbuf1);
     __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();
 
@@ -506,7 +281,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv53_wino4v_kernel(con
         constexpr int cur = decltype(curc)::value;
         const float* Bf = cur == 0 ? sbuf0 : (cur == 1 ? sbuf1 : sbuf2);
         float* Nx = cur == 0 ? sbuf2 : (cur == 1 ? sbuf0 : sbuf1);       // buffer (cur + 2) % 3: read during the previous chunk
-        const bool more = (ch + 2) < a.nchunks;
+        const bool more = (ch + 2) < a.g.nchunks;
         // fragments of step s+1 are fetched while the MFMAs of step s run
         float bv[2][NTT][NXI];
         float av[2][MT][NXI];
@@ -554,105 +329,14 @@ __global__ __launch_bounds__(64 * WGM * WGN, MINW) void conv53_wino4v_kernel(con
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
     };
-    for (int ch = 0; ch < a.nchunks; ch += 3) {
+    for (int ch = 0; ch < a.g.nchunks; ch += 3) {
         chunk(std::integral_constant<int, 0>{}, ch);
-        if (ch + 1 < a.nchunks) chunk(std::integral_constant<int, 1>{}, ch + 1);
-        if (ch + 2 < a.nchunks) chunk(std::integral_constant<int, 2>{}, ch + 2);
+        if (ch + 1 < a.g.nchunks) chunk(std::integral_constant<int, 1>{}, ch + 1);
+        if (ch + 2 < a.g.nchunks) chunk(std::integral_constant<int, 2>{}, ch + 2);
     }
     __builtin_amdgcn_s_setprio(0);
 
-    // ---- epilogue: output transform, then gate / dGELU / residual, four samples per lane -------------------------------
-    float dsum[MT][4];                                   // <y, aux> per block of 4 rows (dot_ws)
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) dsum[i][q] = 0.f;
-#pragma unroll
-    for (int j = 0; j < NTT; ++j) {
-        const int nt = (wn * NTT + j) * 32 + (lane & 31);
-        const int rr = nt >> ttau_log2, tau = nt & ((TT >> 2) - 1);
-        const int b = rowinfo[2 * rr];
-        const int f = rowinfo[2 * rr + 1];
-        const int t = t0 + 4 * tau;
-        if (b < 0 || t >= p.T) continue;                 // T % 4 == 0: the four samples are in range together
-        const int64_t ybase = (int64_t)b * p.y.sB + (int64_t)f * p.y.sF + t;
-        const int64_t rbase = p.res.p ? ((int64_t)b * p.res.sB + (int64_t)f * p.res.sF + t) : 0;
-        const int64_t abase = p.aux.p ? ((int64_t)b * p.aux.sB + (int64_t)f * p.aux.sF + t) : 0;
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-            const int mbase = m0 + (wm * MT + i) * 32 + 4 * (lane >> 5);
-#pragma unroll
-            for (int r0 = 0; r0 < 16; r0 += 4) {         // batches of 4 rows: gather, then compute + store
-                float4 rv[4], ur[4];                      // residual, raw aux (scaled by `as` when the dGELU is evaluated)
-                float sv[4], as[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int r = r0 + q;
-                    const int m = mbase + (r & 3) + 8 * (r >> 2);
-                    const bool ok = m < p.Cout;
-                    rv[q] = (ok && p.res.p) ? *reinterpret_cast<const float4*>(p.res.p + rbase + (int64_t)m * p.res.sC) : make_float4(0.f, 0.f, 0.f, 0.f);
-                    sv[q] = (ok && p.out_scale) ? p.out_scale[(int64_t)b * p.out_scale_ld + m] : 1.f;
-                    if (ok && p.epi == 1) {
-                        as[q] = p.aux_scale[(int64_t)b * p.aux_scale_ld + m];
-                        ur[q] = *reinterpret_cast<const float4*>(p.aux.p + abase + (int64_t)m * p.aux.sC);
-                    } else { as[q] = 0.f; ur[q] = make_float4(0.f, 0.f, 0.f, 0.f); }
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int r = r0 + q;
-                    const int m = mbase + (r & 3) + 8 * (r >> 2);
-                    if (m >= p.Cout) continue;
-                    const float M0 = acc[i][j][0][r], M1 = acc[i][j][1][r], M2 = acc[i][j][2][r], M3 = acc[i][j][3][r],
-                                M4 = acc[i][j][4][r], M5 = acc[i][j][5][r];
-                    const float a12 = M1 + M2, s12 = M1 - M2, a34 = M3 + M4, s34 = M3 - M4;
-                    float y0 = (M0 + a12 + a34) * sv[q];
-                    float y1 = (s12 + 2.f * s34) * sv[q];
-                    float y2 = (a12 + 4.f * a34) * sv[q];
-                    float y3 = (s12 + 8.f * s34 + M5) * sv[q];
-                    if (p.epi == 1) { y0 *= aid_dgelu(ur[q].x * as[q]); y1 *= aid_dgelu(ur[q].y * as[q]); y2 *= aid_dgelu(ur[q].z * as[q]); y3 *= aid_dgelu(ur[q].w * as[q]); }
-                    y0 += p.res_scale * rv[q].x; y1 += p.res_scale * rv[q].y; y2 += p.res_scale * rv[q].z; y3 += p.res_scale * rv[q].w;
-                    y0 *= p.alpha; y1 *= p.alpha; y2 *= p.alpha; y3 *= p.alpha;
-                    *reinterpret_cast<float4*>(p.y.p + ybase + (int64_t)m * p.y.sC) = make_float4(y0, y1, y2, y3);
-                    if (p.dot_ws) dsum[i][r0 >> 2] += (y0 * ur[q].x + y1 * ur[q].y) + (y2 * ur[q].z + y3 * ur[q].w);
-                }
-            }
-        }
-    }
-    // ---- optional: <y, aux> per (sample, channel group), one partial per tile (replaces the aid_group_dot pass) -----------
-    if (p.dot_ws) {
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float v = dsum[i][q];
-#pragma unroll
-                for (int off = 16; off >= 1; off >>= 1) v += __shfl_xor(v, off, 32);     // the 32 lanes of a half-wave share their rows
-                dsum[i][q] = v;
-            }
-        float* red = sbuf0;                              // (every wave is past the last chunk's barrier)
-        if ((lane & 31) == 0) {
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) red[((wave * 2 + half) * MT + i) * 4 + q] = dsum[i][q];
-        }
-        __syncthreads();
-        const int cpg = p.Cout >> 3;                     // channels per group (8 groups); M_BLK % cpg == 0 (host-checked)
-        const int g = m0 / cpg + tid;
-        if (tid < M_BLK / cpg && g < 8) {
-            float sacc = 0.f;
-            for (int w = 0; w < NW; ++w)                 // fixed order: deterministic
-                for (int h = 0; h < 2; ++h)
-                    for (int i = 0; i < MT; ++i)
-                        for (int q = 0; q < 4; ++q) {
-                            const int mrow = m0 + ((w / WGN) * MT + i) * 32 + 4 * h + 8 * q;
-                            if (mrow / cpg == g) sacc += red[((w * 2 + h) * MT + i) * 4 + q];
-                        }
-            const int b = rowinfo[0];
-            const int ptile = ((row0 - b * p.F) >> a.rows_log2) * a.tiles_t + tile_t;
-            p.dot_ws[((int64_t)b * 8 + g) * p.dot_n + ptile] = (double)sacc;
-        }
-    }
+    wino4_tile_epilogue<MT, NTT, WGM, WGN>(p, a.g, o, rowinfo, sbuf0, wave, acc);
 }
 
 // ---- F(4,3), Winograd-domain input, ROW-SHARED staging, two workgroups per CU ---------------------------------------------------
@@ -1239,17 +923,6 @@ template <int TT, int NC, int WGM, int NC1 = 0>
 __global__ __launch_bounds__(512, 2) void conv53_wino8r_ks_kernel(const ConvWinoRDev a) { AID_W4R_ENTRY(TT, NC, WGM, 2, 1, 8, 8, 2, NC1, false); }
 #undef AID_W4R_ENTRY
 
-// the device zero page of this translation unit (looked up once); nullptr with the error set when the lookup fails
-static const float* wino_zero_page() {
-    static const float* zero = nullptr;
-    if (!zero) {
-        void* z = nullptr;
-        if (hipGetSymbolAddress(&z, HIP_SYMBOL(g_aid_zero_page_w)) != hipSuccess) { aid_set_error("aid_conv2d: zero page lookup failed"); return nullptr; }
-        zero = (const float*)z;
-    }
-    return zero;
-}
-
 // The launcher of the two older F(4,3) kernels (conv53_wino4_kernel / conv53_wino4v_kernel: the same tile geometry and grid, different staging).
 // names: the noted name of the 64|128 x 512, the 96 x 512 and the 64 x 256 instance.
 struct Wino4Names { const char *plain, *m96, *small; };
@@ -1259,21 +932,11 @@ static int launch_wino4_tiles(Kern kern, const Wino4Names& names, const aid_conv
     constexpr int N_BLK = 128 * NTT * WGN;
     ConvWinoDev a;
     a.p = *p;
-    a.zero = wino_zero_page();
+    a.zero = aid_zero_page();
     if (!a.zero) return AID_E_LAUNCH;
-    int TT = aid_pow2ceil(p->T);
-    if (TT > N_BLK) TT = N_BLK;
-    a.tt_log2 = aid_ilog2(TT);
-    const int ROWS = N_BLK / TT;
-    if (ROWS > RMAX) return 1000;
-    a.rows_log2 = aid_ilog2(ROWS);
-    a.tiles_t = aid_cdiv(p->T, TT);
-    a.nrows = p->B * p->F;
-    a.nchunks = p->Cin / KC;
-    const int rgroups = aid_cdiv(a.nrows, ROWS);
-    a.nx = rgroups * a.tiles_t; a.ny = p->Cout_pad / M_BLK;
-    a.per_xcd = (a.nx * a.ny + 7) / 8;                  // XCD-aware 1-D grid (see the kernel)
-    hipLaunchKernelGGL(kern, dim3((unsigned)(8 * a.per_xcd), 1), dim3(64 * WGM * WGN), 0, st, a);      // LDS is static (see the kernel)
+    dim3 grid;
+    if (conv_tile_geo(&a.g, &grid, p, N_BLK, M_BLK, KC, RMAX, 1, true) == 1000) return 1000;
+    hipLaunchKernelGGL(kern, grid, dim3(64 * WGM * WGN), 0, st, a);      // LDS is static (see the kernel)
     AID_CHECK_LAUNCH();
     aid_note_kernel(M_BLK == 96 ? names.m96 : ((M_BLK == 64 && N_BLK == 256) ? names.small : names.plain));
     return AID_OK;
@@ -1379,7 +1042,7 @@ static int wino_fin_check(const aid_conv2d_params* p) {
 // The launcher of the row-shared kernels, form = 4 (F(4,3)) or 8 (F(8,3)).  F(4,3) returns 1000 when the shape is better served by the 64|96 x 512 kernel.
 // A plan of more than 2^30 tiles is refused whatever the form: W4rGeo counts tiles, and a split launch twice as many, in 32 bits (no shipped shape comes near).
 static int launch_wino_r(int form, const aid_conv2d_params* p, hipStream_t st) {
-    const float* const zero = wino_zero_page();
+    const float* const zero = aid_zero_page();
     if (!zero) return AID_E_LAUNCH;
     const WinoRPlan pl = wino_r_plan(form, p->B, p->Cout_pad, p->F, p->T, p->dilF);
     if (!pl.nl && form == 4) return 1000;

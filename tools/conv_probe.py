@@ -64,7 +64,8 @@ def main():
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / reps
     fl = 2.0 * B * F * T * Cin * Cout * KH * KW
-    print(f"conv {KH}x{KW} d{dil} B{B} Cin{Cin} Cout{Cout} F{F} T{T}: {ms:.3f} ms  {fl / ms / 1e9:.1f} TFLOP/s")
+    kern = L.lib().aid_last_kernel().decode()
+    print(f"conv {KH}x{KW} d{dil} B{B} Cin{Cin} Cout{Cout} F{F} T{T}: {ms:.3f} ms  {fl / ms / 1e9:.1f} TFLOP/s  {kern}")
 
 
 if __name__ == "__main__":
