@@ -488,7 +488,12 @@ ABIS = (
                   # (blind_long.py: rec = recordings, jobs = the job table, y = J doubles, the energy of every job's window)
                   "aid_window_energy": BweGatherParams,
                   # (metrics.py: x = estimate, y = reference, state = region weights or null, h = frame distances [B, K], out = 8 doubles per item)
-                  "aid_eval_sums": FirObservedParams}),
+                  "aid_eval_sums": FirObservedParams,
+                  # (declick.py: rec = recordings, out = ridge, sigma_floor as 2 floats in HOST memory, y = scores [R, N] with row stride out_ld,
+                  #  state = sigma [R, J], L = block, K = order, J = ceil(N / block))
+                  "aid_ar_score": BweGatherParams,
+                  # (declick.py: x = recordings, y = scores, h = threshold, pad, min_run, max_run as 4 floats in HOST memory, out = mask, mode = 0)
+                  "aid_click_mask": FirObservedParams}),
     Abi("aid_lowrate_long.h", "aid_lowrate_long_abi_version", 1,
         structs={"aid_rate_observed_params": RateObservedParams, "aid_lowrate_gather_params": LowrateGatherParams},
         launches={"aid_rate_observed": RateObservedParams, "aid_lowrate_gather": LowrateGatherParams}),

@@ -217,6 +217,45 @@ def restore_long(sampler, files: Sequence[torch.Tensor], masks: Sequence[torch.T
     return _long_groups("restore_long", sampler, files, seeds, max_batch, device, mode, pool)
 
 
+def declick_detect(files: Sequence[torch.Tensor], device="cuda", masks: Optional[Sequence[Optional[torch.Tensor]]] = None, settings=None):
+    """(masks, reports) of declick.detect over 1-D waveforms of any lengths: the files of equal length are stacked for ONE detect call.
+    masks[i] [N_i] on ``device`` is the detected mask times ``masks[i]`` (known gaps, 1 = observed) where one is given; reports[i] is the
+    file's declick.Detection -- that mask and ITS counts (known gaps included), the detector's sigma [J_i], no score plane.  A file of which more than
+    ``max_fraction`` is masked is refused, by its index.  Needs no model."""
+    from . import declick
+    cfg = declick.make_settings(**dict(settings or {}))
+    if masks is not None and len(masks) != len(files):
+        raise ValueError(f"declick_long: {len(masks)} masks for {len(files)} files")
+    groups = {}
+    for i, f in enumerate(files):
+        groups.setdefault(f.numel(), []).append(i)
+    out, reports = [None] * len(files), [None] * len(files)
+    for n, idx in groups.items():
+        det = declick.detect(torch.stack([files[i].reshape(-1).float() for i in idx]).to(device), **cfg._asdict())
+        for j, i in enumerate(idx):
+            counts = det.n_flagged[j], det.n_gaps[j], det.longest_gap[j]
+            m = det.mask[j]
+            if masks is not None and masks[i] is not None:                   # (the report describes the mask that is restored)
+                m = declick.combine(det.mask[j:j + 1], masks[i].reshape(-1))[0]
+                counts = tuple(c[0] for c in declick.report_of(m))
+            out[i] = m
+            reports[i] = declick.Detection(m, None, det.sigma[j], *counts)
+    declick.check_fraction([int(r.n_flagged) for r in reports], [f.numel() for f in files], cfg.max_fraction, "file")
+    return out, reports
+
+
+def declick_long(sampler, files: Sequence[torch.Tensor], seeds: Optional[Sequence[int]] = None, max_batch: int = 8, device="cuda", pool: bool = False,
+                 masks: Optional[Sequence[Optional[torch.Tensor]]] = None, **settings):
+    """Declick every 1-D waveform of ``files`` (any lengths): ``declick_detect`` finds the clicks and dropouts (settings:
+    declick.settings_of(sampler.args), overridden by ``settings``; ``masks``: known gaps per file, or None), then
+    restore_long(sampler, files, the detected masks, seeds, max_batch, device, pool) restores them, so grouping, seeds, process groups and
+    ``pool`` are restore_long's (the pooled task is "inpainting").  -> (the full-length results on ``device``, the reports of declick_detect),
+    both in the order of ``files``."""
+    from . import declick
+    detected, reports = declick_detect(files, device, masks, declick.settings_of(sampler.args, **settings)._asdict())
+    return restore_long(sampler, files, detected, seeds, max_batch, device, pool), reports
+
+
 def declip_long(sampler, files: Sequence[torch.Tensor], clip_values, seeds: Optional[Sequence[int]] = None, max_batch: int = 8,
                 device="cuda", pool: bool = False) -> List[torch.Tensor]:
     """Declip every 1-D waveform of ``files`` (any lengths), clipped at +-clip_values (one float for all files, or one per file), and return the

@@ -571,6 +571,27 @@ class Sampler:
         (restore.run_passes).  ``seeds`` = None is then refused, and ranks that were given different work raise before anything is launched."""
         return self._long("inpainting", [(y, mask)], max_batch, seeds)[0]
 
+    def predict_declicking_long(self, y, max_batch=8, seeds=None, mask=None, **settings):
+        """Declick whole recordings y[R, N] on the GPU -- N any length, clicks and short dropouts at unknown places -> [R, N] (declick.py).
+        A front end of predict_inpainting_long, not a task of its own: declick.detect finds the damage (two launches and one read-back of the
+        mask; settings: declick.settings_of(args), overridden by ``settings``), the detected mask is multiplied by ``mask`` ([N], [1, N] or
+        [R, N]; known gaps, 1 = observed) when one is given, and the result is predict_inpainting_long(y, that mask, max_batch, seeds) --
+        its refusals, grid, seeds and behaviour under a process group, word for word.  Before that call a recording of which more than
+        ``max_fraction`` is masked is refused, by its index.  With nothing flagged the result is a copy of y and no evaluation runs.
+        Afterwards ``declick_report`` holds the declick.Detection without the score plane: the mask that was restored, its counts (known
+        gaps included when ``mask`` was given) and the detector's sigma.  Under a process group every rank detects for itself: the detector is deterministic, nothing is exchanged."""
+        from . import declick
+        cfg = declick.settings_of(self.args, **settings)
+        det = declick.detect(y, **cfg._asdict())
+        m = declick.combine(det.mask, mask)
+        if mask is not None:                                                     # (the report describes the mask that is restored)
+            det = declick.Detection(m, det.score, det.sigma, *declick.report_of(m))
+        declick.check_fraction(det.n_flagged.tolist(), m.shape[1], cfg.max_fraction)
+        self.declick_report = det._replace(score=None)
+        return self.predict_inpainting_long(y, m, max_batch, seeds)
+
+    declick_report = None       # after predict_declicking_long: the declick.Detection of the call, without its score plane
+
     def predict_declipping_long(self, y, clip_value, max_batch=8, seeds=None):
         """Declip whole recordings y[R, N] -- N any length, clipped at +-clip_value (a float, or R floats: one level per recording; rounded to
         float32 as HardClip does) -> [R, N] on y.device (declip_long.py).  The window grid, the two batched passes and the seeds are those of

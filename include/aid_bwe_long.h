@@ -161,6 +161,51 @@ int aid_window_energy(const aid_bwe_gather_params* p, void* stream);
  * ------------------------------------------------------------------------------------------------- */
 int aid_eval_sums(const aid_fir_observed_params* p, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * aid_ar_score -- the outlier score of declicking (declick.py; csrc/aid_declick.hip): every block of a recording is fitted with an
+ *   autoregressive model and every sample scored by its prediction residual over a robust scale.  On the parameter block of
+ *   aid_bwe_gather.  What every field means here:
+ *   rec     the recordings [R, N] fp32, row stride rec_ld >= N                                                              (read)
+ *   out     the scalars: 2 floats in HOST memory, ridge >= 0 and sigma_floor > 0, both finite.  The launcher reads them before it
+ *           returns and hands them to the kernel with its arguments; the memory may be reused as soon as the call returns.    (read)
+ *   y       the scores [R, N] fp32, row stride out_ld >= N                                                                  (written)
+ *   state   sigma [R, J] fp32, contiguous: the scale of every block, 0 where the block was not scored                       (written)
+ *   jobs    not read (may be null)
+ *   L       the block length: 256, 512, 1024, 2048 or 4096;  K  the model order, 1 <= K <= 32 and 8 K <= L
+ *   J       the blocks of a recording: J == ceil(N / L);  R <= 65535
+ *   Block j of a row holds the n samples x[0 .. n) at the positions [j L, min(N, (j + 1) L)).  With n < 8 K it is not scored: its
+ *   scores and its sigma are 0.  Otherwise, in fp64:  r[m] = sum_{i = m}^{n - 1} x[i] x[i - m] for m = 0 .. K, r[0] *= 1 + ridge; with
+ *   r[0] <= 0 the block is not scored either.  Levinson-Durbin on r gives a[1 .. K] with a[0] = 1 (it stops, leaving the remaining
+ *   coefficients 0, once the error power is <= 0).  e[q] = sum_{k = 0}^{K} a[k] rec[q - k] over the RECORDING's samples (those of the
+ *   previous block where q - k falls there, 0 before the first sample).  The scored samples are the block's, but never the first K
+ *   of the recording, whose score is 0.  median = the element of rank n' / 2 (0-based, integer division) of |e| over the n' scored
+ *   samples, sorted ascending; sigma = max(median / 0.6745, sigma_floor); score = |e| / sigma, rounded to fp32 once.
+ *   One workgroup of 256 lanes per (recording, block): the block and K samples of history in LDS; lane l adds the products
+ *   i = l, l + 256, ... ascending (from the first i >= m) and the 256 partial sums are added as a fixed binary tree; one lane runs the
+ *   recursion; the median comes from a bitonic sort of |e|, padded with +inf, in LDS.  Static LDS only, no scratch, no atomics,
+ *   nothing kept between calls: a second launch gives the same bits, and a row does not depend on the other rows.  Non-finite
+ *   samples are outside the contract.
+ *
+ * aid_click_mask -- from the scores to the mask of predict_inpainting_long (1 = observed, 0 = restore).  On the parameter block of
+ *   aid_fir_observed.  What every field means here:
+ *   x       the recordings [B, L] fp32, row stride x_ld >= L                                                                (read)
+ *   y       the scores [B, L] fp32 (aid_ar_score's), row stride y_ld >= L                                                   (read)
+ *   state   not read (may be null)
+ *   h       the settings: 4 floats in HOST memory -- threshold > 0, then the whole numbers pad in [0, 256], min_run (0 = no run rule,
+ *           otherwise 2 <= min_run <= max_run) and max_run in [1, 1024] -- read by the launcher as aid_ar_score reads its scalars (read)
+ *   out     the mask [B, L] fp32, row stride out_ld >= L                                                                    (written)
+ *   K       ignored;  mode  must be 0;  B <= 65535
+ *   A sample is FLAGGED when its score is > threshold (fp32 against fp32), or, with min_run > 0, when it lies in a maximal run of
+ *   bit-identical samples of length l, min_run <= l <= max_run, that holds neither the first nor the last sample of the recording.
+ *   mask[q] = 0 when a sample of [q - pad, q + pad] within [0, L) is flagged, 1 otherwise.
+ *   One workgroup of 256 lanes per tile of 1024 samples; the tile with pad + max_run samples on either side (clamped to the
+ *   recording) in LDS.  Run starts, run ends and the count of flags behind the +-pad window are scans in LDS.  A run that reaches
+ *   the edge of what was loaded without ending is longer than max_run or holds an end of the recording: it is never flagged.
+ *   Compares and integers only: exact.  No atomics; deterministic; a row does not depend on the other rows.
+ * ------------------------------------------------------------------------------------------------- */
+int aid_ar_score(const aid_bwe_gather_params* p, void* stream);
+int aid_click_mask(const aid_fir_observed_params* p, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
